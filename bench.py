@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the batched tinycarlo step() on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -17,13 +17,18 @@ Workloads (BASELINE.json configs):
     cfg2            same, no_observation=True (kinematics + tracking + distances only)
     cfg4            4096 envs/GPU, knuffingen, 128x128 'classes'
     cfg5            8192 envs, knuffingen, 480x640 'rgb'
-Envs are sharded over ranks with no data-path collective (they are independent): `value` is the un-gathered rate.  With
---gpus > 1 the optional exchange step (rewards / flags, and observations, to rank 0 over RCCL) is measured after the
-main region in the same process and reported beside it as `gathered` (separate numbers).  A plain
+Envs are sharded over ranks with no data-path collective (they are independent): `value` is the un-gathered rate.
+A plain run sets up, pre-rolls, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, dtype,
+config); `--full` adds the figures that cost runs or work of their own: `roofline` (HIP events around the timed
+launches), `value_single_step`, `gathered` and `cpu_baseline`.  `--dump-outputs DIR` writes what the last timed step
+computed (see dump_outputs) as DIR/<name>.npy; the pre-roll steps the envs a fixed number of times (PREROLL_STEPS), so
+with the same arguments a run computes the same outputs every time.  With --full and --gpus > 1 the optional exchange
+step (rewards / flags, and observations, to rank 0 over RCCL) is measured after the main region in the same process and
+reported beside it as `gathered` (separate numbers).  A plain
 `python bench.py --gpus N` (no WORLD_SIZE in the environment) starts its own N ranks as a child
 `python -m torch.distributed.run` before anything touches a GPU and exits with the child's code.
 `value` is the open-loop K-step form (tc_step_multi, actions of a call known in advance); the closed-loop form -- one
-tc_step launch per step, what a policy in the loop sees -- is timed in the same run and reported beside it as
+tc_step launch per step, what a policy in the loop sees -- is timed in the same run with --full and reported beside it as
 `value_single_step`.  `config` says what the timed frames drew (mean draw-list length, empty-frame fraction, steps
 since the last re-spawn).
 Prints ONE JSON line on rank 0.
@@ -45,6 +50,10 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 B_STATE = 240          # algorithmic state/action/info bytes per env-step
 PROFILE_ROUND = "r03"  # profiles/<round>/<workload>_pmc.json holds the committed PMC summary of this command
+# steps of the pre-roll (about what the 300 ms pre-roll of cfg3 used to reach when it counted time, not steps): a fixed
+# count makes the timed region start from the same state, and so compute the same outputs, in every run
+PREROLL_STEPS = 1024
+DUMP_BYTES = 48 << 20  # --dump-outputs: at most this many bytes of arrays (a seeded sample of the envs beyond that)
 
 WORKLOADS = {
     "cfg2": dict(map="simple_layout", res=[64, 64], fmt="classes", envs=4096, no_obs=True),
@@ -160,6 +169,32 @@ def cpu_baseline(w, cfg, budget_env_steps):
             "one_thread": {"value": v_one, "unit": "env-steps/s", "cores": 1, "sample": s_one}}
 
 
+def dump_outputs(out_dir, env, last_call, obs_in_out):
+    """What a caller of the timed path holds after its last step, as out_dir/<name>.npy (float64, uint8 as float32):
+    step_<key> = that step's row of the call's rollout, out_<key> / state_<key> = the env's output and state tensors
+    (out_obs only where the step drew into it).  A seeded sample of the envs (env_index) when all would exceed
+    DUMP_BYTES."""
+    arrays = {}
+    r = last_call[2]
+    for k, v in (r or {}).items():
+        arrays["step_" + k] = v[-1]
+    for k, v in env.out.items():
+        if k != "obs" or obs_in_out:
+            arrays["out_" + k] = v
+    for k, v in env.state.items():
+        arrays["state_" + k] = v
+    n = env.num_envs
+    row = sum((4 if v.dtype == torch.uint8 else 8) * (v.numel() // n) for v in arrays.values()) + 8
+    ns = min(n, max(1, DUMP_BYTES // row))
+    idx = np.arange(n) if ns == n else np.sort(np.random.default_rng(0).choice(n, ns, replace=False))
+    idx_t = torch.from_numpy(idx).to(env.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "env_index.npy"), idx.astype(np.float64))
+    for k, v in arrays.items():
+        a = v.index_select(0, idx_t).cpu().numpy()
+        np.save(os.path.join(out_dir, k + ".npy"), a.astype(np.float32 if a.dtype == np.uint8 else np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -171,8 +206,9 @@ def main():
                     help="steps issued per tc_step_multi call (default 128; cfg5: 2 -- its rollout rows are 7.5 GB each); "
                          "0 = one tc_step launch per step")
     ap.add_argument("--preroll-ms", type=float, default=300.0,
-                    help="untimed steps issued for about this long before the warm-up so that a short run is measured at "
-                         "steady clocks (reported as config.preroll_steps)")
+                    help="untimed pre-roll before the warm-up: PREROLL_STEPS steps (config.preroll_steps), then frames of "
+                         "the current state redrawn until about this long has passed, so that a short run is measured at "
+                         "steady clocks; 0 = none")
     ap.add_argument("--no-gathered", action="store_true", help="--gpus > 1: skip the gathered measurements")
     ap.add_argument("--no-rollout", action="store_true",
                     help="diagnostic: K-step launches without per-step rollout rows (only the last step's outputs and frame "
@@ -184,6 +220,10 @@ def main():
                          "that cars which drift off the road re-spawn instead of driving through empty scenery for ever "
                          "(the default env terminates on one side only, env.py:99); NOT the metric's workload")
     ap.add_argument("--cpu-budget", type=int, default=2000000, help="env-steps of the all-cores CPU baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, value_single_step, gathered (--gpus > 1) and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0's envs)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -344,26 +384,28 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device=device)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
-        return dt, ev_ms, nl
+        return dt, ev_ms, nl, calls[-1]
 
     # untimed pre-roll: the driver's short command (20 steps) would otherwise be measured while the clocks ramp up
-    # The seeded spawn queues are topped up ONCE, two thirds into the pre-roll (host work of several milliseconds during
-    # which the GPU idles and its clocks sag), and the GPU is then kept busy without a gap until the timed region starts;
-    # the queue (64 entries per env) is only consumed from there on, never wrapped (`config.spawn` says if it was).
+    # PREROLL_STEPS steps first; the seeded spawn queues are topped up ONCE, two thirds into them (host work of several
+    # milliseconds during which the GPU idles and its clocks sag).  Then the frames of the current state are redrawn
+    # (tc_render: changes no state) until --preroll-ms have passed, and the GPU is kept busy without a gap until the timed
+    # region starts; the queue (64 entries per env) is only consumed from there on, never wrapped (`config.spawn` says if
+    # it was).
     preroll = 0
     if args.preroll_ms > 0:
         chunk = max(M, 32)
         t0_pre = time.perf_counter()
         topped = False
-        while True:
-            el = (time.perf_counter() - t0_pre) * 1e3
-            if el >= args.preroll_ms:
-                break
-            if not topped and el >= args.preroll_ms * 0.66:
+        while preroll < PREROLL_STEPS:
+            if not topped and preroll >= PREROLL_STEPS * 2 // 3:
                 env.top_up_spawn_queue()
                 topped = True
-            issue(preroll % period, chunk)
-            preroll += chunk
+            issue(preroll % period, min(chunk, PREROLL_STEPS - preroll))
+            preroll += min(chunk, PREROLL_STEPS - preroll)
+            torch.cuda.synchronize()
+        while (time.perf_counter() - t0_pre) * 1e3 < args.preroll_ms:
+            env.render_current()
             torch.cuda.synchronize()
     else:
         env.top_up_spawn_queue()
@@ -375,14 +417,16 @@ def main():
     # HIP events on the launch stream around the kernel(s) of sampled launches (every launch of a short run; an
     # event triple on every launch of a long one serialises the queue)
     n_launch = K if M == 0 else -(-K // M)
-    env.profile(1 if n_launch <= 64 else max(1, n_launch // 48))
+    if args.full:
+        env.profile(1 if n_launch <= 64 else max(1, n_launch // 48))
     # the timed region starts on a call boundary of the cyclic action buffer, so that no call is split at its wrap-around
     t_start = W if M == 0 else (-(-W // M) * M) % period
     if flag_rows is not None:
         flag_rows["t0"] = t_start
-    dt, ev_ms, n_l = timed(t_start, K)
-    prof = env.profile_read()
-    env.profile(0)
+    dt, ev_ms, n_l, last_call = timed(t_start, K)
+    if args.full:
+        prof = env.profile_read()
+        env.profile(0)
     drew = env.draw_list_stats() if not w["no_obs"] else None  # what the last frames of the timed region drew
     age_end = None
     if flag_rows is not None:
@@ -392,10 +436,13 @@ def main():
         del fr
     n_resets = int(env._aux["spawn_cursor"].sum().item())
     max_cursor = int(env._aux["spawn_cursor"].max().item())
+    if args.dump_outputs and rank == 0:
+        obs_in_out = not w["no_obs"] and (last_call[2] is None or "obs" not in last_call[2])
+        dump_outputs(args.dump_outputs, env, last_call, obs_in_out)
 
     # --- the closed-loop form: one tc_step launch per step (what a policy in the loop sees), same bracket, same run
     single = None
-    if M >= 1 and not args.no_single_step:
+    if args.full and M >= 1 and not args.no_single_step:
         K1 = min(K, 256)
         env.top_up_spawn_queue()
         t_w = time.perf_counter()  # (the top-up is host work: bring the clocks back up before timing)
@@ -403,7 +450,7 @@ def main():
             issue(0, 64, m=0)
             torch.cuda.synchronize()
         issue(0, min(W, 16), m=0)
-        dt1, ev1_ms, _ = timed(0, K1, m=0)
+        dt1, ev1_ms, _, _ = timed(0, K1, m=0)
         single = {"value": world * n * K1 / dt1, "unit": "env-steps/s", "steps": K1, "ms_per_step": dt1 / K1 * 1e3,
                   "entry_point": "tc_step (one launch per step, closed loop)", "kernel": env.launch_info(1)["kernel"],
                   "step_frac": (B_STATE + (0 if w["no_obs"] else env.obs_bytes_per_env)) * n / (ev1_ms / 1e3 / K1) / 1e9 / HBM_PEAK_GBS}
@@ -412,7 +459,7 @@ def main():
 
     # --- the optional exchange step, measured after the main region (never inside `value`)
     gathered = None
-    if dist is not None and not args.no_gathered:
+    if args.full and dist is not None and not args.no_gathered:
         gathered = {}
         Kg = min(K, 256)
         Mg = max(1, min(M if M >= 1 else 1, 8))  # rank 0 holds world x 2 slots of a launch's rows: keep the slots small
@@ -422,7 +469,7 @@ def main():
             try:
                 g = RankGather(env, what=what, steps_per_launch=Mg)
                 issue(0, 2 * Mg, g, Mg)  # warm the collective up (communicator set-up is not part of the rate)
-                dtg, _, _ = timed(0, Kg, g, Mg)
+                dtg, _, _, _ = timed(0, Kg, g, Mg)
                 last = g.latest()
                 ok = None
                 if rank == 0:
@@ -440,40 +487,6 @@ def main():
     C = env.n_classes
     H, Wd = env.camera.resolution
     b_obs = 0 if w["no_obs"] else (C * H * Wd if w["fmt"] == "classes" else 3 * H * Wd)
-    bytes_per_env_step = B_STATE + b_obs
-    step_s = ev_ms / 1e3 / K  # HIP events on the launch stream around the K timed steps
-    steps_per_call = max(1, int(round(K / max(n_l, 1)))) if M >= 1 else 1
-    info = env.launch_info(steps_per_call)  # what the library really launches for a call of that size (not guessed from timings)
-    kname = info["kernel"]
-    fused = info["fused"]
-    full_launches = (K // M) if M >= 1 else K      # the sampled means below include a short last call if K % M != 0
-    steps_in_sampled = K / max(n_l, 1)             # mean steps per call over the timed region
-    # A K-step call that stores every frame is issued as pipelined chunks (include/tinycarlo_hip.h, tc_step_multi): the
-    # library reports how many steps one kernel DISPATCH covers, and the roofline below is per dispatch, the unit
-    # rocprofv3's kernel trace and PMC counters are in.
-    spd = max(1, min(info["steps_per_dispatch"], steps_per_call))
-    n_disp = -(-int(round(steps_in_sampled)) // spd) if M >= 1 else 1
-    rows_per_dispatch = steps_in_sampled / n_disp
-    two = "+" in kname                             # simulate dispatches + frame (or raster) dispatches
-    if two:
-        # The dominant kernel is the one that writes the observations (tc_frame_kernel: camera + raster of one frame per
-        # workgroup).  Its algorithmic bytes per frame: the observation, written once, plus the 96 bytes of the 3x4 pose
-        # matrix it reads; the 240 B of state / action / info traffic belong to the simulate dispatch in
-        # front of it.
-        # HIP events bracket the call's first..last frame dispatch on the stream they run on; the dispatches follow
-        # each other without a gap there (simulating a chunk is faster than drawing it), so span / dispatches is the
-        # average dispatch duration -- the figure rocprofv3's kernel stats give for the same command.
-        dom = kname.split("+")[-1]
-        kernel_s = prof["raster_us"] * 1e-6 / n_disp
-        sim_s = prof["simulate_us"] * 1e-6 / n_disp
-        dom_bytes_per_frame = b_obs + 96
-    else:
-        dom = kname
-        kernel_s = sim_s = prof["simulate_us"] * 1e-6 / n_disp
-        dom_bytes_per_frame = bytes_per_env_step
-    kbytes = dom_bytes_per_frame * n * rows_per_dispatch
-    achieved = kbytes / kernel_s / 1e9 if kernel_s > 0 else 0.0
-    traffic, traffic_src = pmc_traffic(args.workload, dom, rows_per_dispatch) if n == WORKLOADS[args.workload]["envs"] else (None, None)
     out = {
         "metric": "env-steps/sec (whole node)",
         "value": world * n * K / dt,
@@ -513,30 +526,65 @@ def main():
                    "steps_since_reset_mean": {"timed_region_start": age_start, "timed_region_end": age_end},
                    "on_road_term": bool(args.on_road),
                    "lds_bytes_per_env": env.lds_bytes},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                     "kernel": dom, "kernel_us": kernel_s * 1e6,
-                     "kernel_us_is": ("HIP-event span of the call's frame dispatches / number of dispatches"
-                                      + (" (streamed call: ONE frame dispatch covers the call's steps and runs beside the "
-                                         "simulate launch, its workgroups waiting for their pose rows; the span includes that "
-                                         "wait at the head and the recover pass behind it)" if (two and n_disp == 1 and spd > 1) else
-                                         " (consecutive dispatches alternate between two internal streams and overlap: "
-                                         "a span per dispatch, not one dispatch's duration)" if (two and spd < 8 and n_disp > 1) else
-                                         " (one stream, back to back: the average dispatch duration)") if two else
-                                      "HIP-event duration of the launch"),
-                     "steps_per_dispatch": rows_per_dispatch,
-                     "dispatches_per_call": n_disp, "steps_per_call": steps_in_sampled,
-                     "kernel_us_per_step": kernel_s * 1e6 / rows_per_dispatch,
-                     "algorithmic_bytes_per_launch": kbytes, "algorithmic_bytes_per_unit": dom_bytes_per_frame,
-                     "algorithmic_bytes_per_env_step": bytes_per_env_step,
-                     "launches_per_call": kname,
-                     "kernels_us": ({kname: sim_s * 1e6} if not two else
-                                    {kname.split("+")[0]: sim_s * 1e6, dom: kernel_s * 1e6}),
-                     "event_samples": prof["launches"], "full_launches": full_launches,
-                     # the whole step (all launches, gaps included) against SURVEY 8d's bytes per env-step
-                     "step_us": step_s * 1e6, "step_achieved_GBs": bytes_per_env_step * n / step_s / 1e9,
-                     "step_frac": bytes_per_env_step * n / step_s / 1e9 / HBM_PEAK_GBS},
     }
+    if args.full:
+        bytes_per_env_step = B_STATE + b_obs
+        step_s = ev_ms / 1e3 / K  # HIP events on the launch stream around the K timed steps
+        steps_per_call = max(1, int(round(K / max(n_l, 1)))) if M >= 1 else 1
+        info = env.launch_info(steps_per_call)  # what the library really launches for a call of that size (not guessed from timings)
+        kname = info["kernel"]
+        fused = info["fused"]
+        full_launches = (K // M) if M >= 1 else K      # the sampled means below include a short last call if K % M != 0
+        steps_in_sampled = K / max(n_l, 1)             # mean steps per call over the timed region
+        # A K-step call that stores every frame is issued as pipelined chunks (include/tinycarlo_hip.h, tc_step_multi): the
+        # library reports how many steps one kernel DISPATCH covers, and the roofline below is per dispatch, the unit
+        # rocprofv3's kernel trace and PMC counters are in.
+        spd = max(1, min(info["steps_per_dispatch"], steps_per_call))
+        n_disp = -(-int(round(steps_in_sampled)) // spd) if M >= 1 else 1
+        rows_per_dispatch = steps_in_sampled / n_disp
+        two = "+" in kname                             # simulate dispatches + frame (or raster) dispatches
+        if two:
+            # The dominant kernel is the one that writes the observations (tc_frame_kernel: camera + raster of one frame per
+            # workgroup).  Its algorithmic bytes per frame: the observation, written once, plus the 96 bytes of the 3x4 pose
+            # matrix it reads; the 240 B of state / action / info traffic belong to the simulate dispatch in
+            # front of it.
+            # HIP events bracket the call's first..last frame dispatch on the stream they run on; the dispatches follow
+            # each other without a gap there (simulating a chunk is faster than drawing it), so span / dispatches is the
+            # average dispatch duration -- the figure rocprofv3's kernel stats give for the same command.
+            dom = kname.split("+")[-1]
+            kernel_s = prof["raster_us"] * 1e-6 / n_disp
+            sim_s = prof["simulate_us"] * 1e-6 / n_disp
+            dom_bytes_per_frame = b_obs + 96
+        else:
+            dom = kname
+            kernel_s = sim_s = prof["simulate_us"] * 1e-6 / n_disp
+            dom_bytes_per_frame = bytes_per_env_step
+        kbytes = dom_bytes_per_frame * n * rows_per_dispatch
+        achieved = kbytes / kernel_s / 1e9 if kernel_s > 0 else 0.0
+        traffic, traffic_src = pmc_traffic(args.workload, dom, rows_per_dispatch) if n == WORKLOADS[args.workload]["envs"] else (None, None)
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                           "kernel": dom, "kernel_us": kernel_s * 1e6,
+                           "kernel_us_is": ("HIP-event span of the call's frame dispatches / number of dispatches"
+                                            + (" (streamed call: ONE frame dispatch covers the call's steps and runs beside the "
+                                               "simulate launch, its workgroups waiting for their pose rows; the span includes that "
+                                               "wait at the head and the recover pass behind it)" if (two and n_disp == 1 and spd > 1) else
+                                               " (consecutive dispatches alternate between two internal streams and overlap: "
+                                               "a span per dispatch, not one dispatch's duration)" if (two and spd < 8 and n_disp > 1) else
+                                               " (one stream, back to back: the average dispatch duration)") if two else
+                                            "HIP-event duration of the launch"),
+                           "steps_per_dispatch": rows_per_dispatch,
+                           "dispatches_per_call": n_disp, "steps_per_call": steps_in_sampled,
+                           "kernel_us_per_step": kernel_s * 1e6 / rows_per_dispatch,
+                           "algorithmic_bytes_per_launch": kbytes, "algorithmic_bytes_per_unit": dom_bytes_per_frame,
+                           "algorithmic_bytes_per_env_step": bytes_per_env_step,
+                           "launches_per_call": kname,
+                           "kernels_us": ({kname: sim_s * 1e6} if not two else
+                                          {kname.split("+")[0]: sim_s * 1e6, dom: kernel_s * 1e6}),
+                           "event_samples": prof["launches"], "full_launches": full_launches,
+                           # the whole step (all launches, gaps included) against SURVEY 8d's bytes per env-step
+                           "step_us": step_s * 1e6, "step_achieved_GBs": bytes_per_env_step * n / step_s / 1e9,
+                           "step_frac": bytes_per_env_step * n / step_s / 1e9 / HBM_PEAK_GBS}
     if single is not None:
         out["value_single_step"] = single
         out["entry_points"] = {"value": "tc_step_multi: K-step calls, the actions of a call known in advance (open loop)",
@@ -544,7 +592,7 @@ def main():
     if gathered is not None:
         out["gathered"] = gathered
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(w, cfg, args.cpu_budget)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -1,11 +1,13 @@
 """bench.py's output contract (one JSON line; metric / value / unit / n_gpus / steps / warmup / ms_per_step /
-higher_is_better / scaling / vs_baseline / dtype / data / config.workload + roofline{} + cpu_baseline{}), checked on a
-small run so that a regression in bench.py shows up in the GPU suite and not only when the driver runs it."""
+higher_is_better / scaling / vs_baseline / dtype / data / config.workload, + roofline{} + cpu_baseline{} with --full), and
+--dump-outputs, checked on small runs so that a regression in bench.py shows up in the GPU suite and not only when the
+driver runs it."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +23,7 @@ def _run(*args):
 
 
 def test_default_workload_line():
-    d = _run("--steps", "40", "--warmup", "8", "--cpu-budget", "40000")
+    d = _run("--full", "--steps", "40", "--warmup", "8", "--cpu-budget", "40000")
     assert d["metric"] == "env-steps/sec (whole node)" and d["unit"] == "env-steps/s"
     assert d["n_gpus"] == 1 and d["steps"] == 40 and d["warmup"] == 8
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None
@@ -53,15 +55,38 @@ def test_default_workload_line():
 
 
 def test_other_workloads_and_flags():
-    d = _run("--workload", "cfg2", "--steps", "20", "--warmup", "4", "--no-cpu-baseline")
+    d = _run("--full", "--workload", "cfg2", "--steps", "20", "--warmup", "4", "--no-cpu-baseline")
     assert "cpu_baseline" not in d and d["roofline"]["kernel"] == "tc_env_kernel"
     assert d["roofline"]["algorithmic_bytes_per_launch"] == 20 * 4096 * 240 and d["roofline"]["dispatches_per_call"] == 1
-    d = _run("--workload", "cfg4", "--envs", "256", "--steps", "10", "--warmup", "2", "--no-cpu-baseline")
+    d = _run("--full", "--workload", "cfg4", "--envs", "256", "--steps", "10", "--warmup", "2", "--no-cpu-baseline")
     assert d["config"]["envs_per_gpu"] == 256 and d["roofline"]["traffic"] is None     # PMC summary is for the full size only
     assert d["roofline"]["kernel"] == "tc_frame_kernel"    # knuffingen: the K = 9 variant, two camera layer groups
     assert d["roofline"]["dispatches_per_call"] == 1       # 10 steps, streamed
     assert d["roofline"]["algorithmic_bytes_per_launch"] == 10 * 256 * (5 * 128 * 128 + 96)
     # the single-step entry point stays measurable: one tc_step launch per step
-    d = _run("--steps", "16", "--warmup", "4", "--steps-per-launch", "0", "--no-cpu-baseline")
+    d = _run("--full", "--steps", "16", "--warmup", "4", "--steps-per-launch", "0", "--no-cpu-baseline")
     assert d["config"]["entry_point"] == "tc_step" and d["roofline"]["steps_per_dispatch"] == 1
     assert d["roofline"]["kernel"] == "tc_step_kernel" and d["roofline"]["algorithmic_bytes_per_launch"] == 4096 * (240 + 5 * 64 * 64)
+
+
+def test_plain_run_and_dumped_outputs(tmp_path):
+    """a plain run times exactly --steps steps and prints the headline only; --dump-outputs writes the last timed step's
+    arrays (float32 / float64, at most 64 MB), the same in two runs with the same arguments"""
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        d = _run("--steps", "40", "--warmup", "8", "--dump-outputs", str(out))
+        assert d["steps"] == 40 and d["warmup"] == 8 and d["config"]["launches_timed"] == 1
+        assert d["metric"] == "env-steps/sec (whole node)" and d["unit"] == "env-steps/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f64" and abs(d["value"] - 4096 * 40 / (d["ms_per_step"] * 40 / 1e3)) < 1e-6 * d["value"]
+        assert not {"roofline", "cpu_baseline", "value_single_step", "gathered"} & set(d)
+        files = sorted(p.name for p in out.iterdir())
+        assert {"env_index.npy", "step_obs.npy", "step_reward.npy", "step_terminated.npy", "state_x.npy"} <= set(files)
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64 * 2**20
+        arrs = {f: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["step_obs.npy"].shape[0] == arrs["env_index.npy"].shape[0] and arrs["step_obs.npy"].max() > 0
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f], equal_nan=True), f

@@ -5,6 +5,6 @@ cd $R
 ARGS="$1"; shift
 for rep in 1 2; do
   for lib in "$@"; do
-    TINYCARLO_HIP_LIB=$R/tinycarlo_amd/$lib timeout -k 10 300 python bench.py $ARGS --no-cpu-baseline --no-single-step 2>/dev/null | python tools/ab_line.py $lib
+    TINYCARLO_HIP_LIB=$R/tinycarlo_amd/$lib timeout -k 10 300 python bench.py --full $ARGS --no-cpu-baseline --no-single-step 2>/dev/null | python tools/ab_line.py $lib
   done
 done

@@ -3,7 +3,7 @@
 # entry point, a --preroll-ms 0 line, an on-road line -- the wrapper timings, and the phase clock / ablation tables
 R=$GRAFT_REPO_ROOT
 cd $R && mkdir -p gpurun_out/r3lines && O=gpurun_out/r3lines
-line() { f=$1; shift; timeout -k 10 500 python bench.py "$@" > $O/$f.json 2> $O/$f.err || { tail -3 $O/$f.err; return 1; }; cut -c1-140 $O/$f.json; }
+line() { f=$1; shift; timeout -k 10 500 python bench.py --full "$@" > $O/$f.json 2> $O/$f.err || { tail -3 $O/$f.err; return 1; }; cut -c1-140 $O/$f.json; }
 line cfg3 || exit 1
 line cfg3_driver_style --steps 20 --warmup 5 || exit 1
 line cfg3_single_step --steps-per-launch 0 --no-cpu-baseline || exit 1

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT
 cd $R && mkdir -p gpurun_out/stream && O=gpurun_out/stream
 timeout -k 10 600 python -m pytest tests/test_gpu_bench_shapes.py -x -q -k "${TC_EXP_TESTS:-cfg3 or every_switch or longer}" > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -3 $O/tests.log
-line() { f=$1; shift; timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > $O/$f.json 2> $O/$f.err || { tail -3 $O/$f.err; return 1; }
+line() { f=$1; shift; timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > $O/$f.json 2> $O/$f.err || { tail -3 $O/$f.err; return 1; }
   python - $O/$f.json $f <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); r=d['roofline']

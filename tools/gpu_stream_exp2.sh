@@ -2,7 +2,7 @@
 # env-switch variants of the streamed call: bench default and the 20-step command each
 R=$GRAFT_REPO_ROOT
 cd $R && mkdir -p gpurun_out/stream && O=gpurun_out/stream
-line() { f=$1; shift; timeout -k 10 300 python bench.py --no-cpu-baseline --no-single-step "$@" > $O/$f.json 2> $O/$f.err || { tail -3 $O/$f.err; return 1; }
+line() { f=$1; shift; timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-single-step "$@" > $O/$f.json 2> $O/$f.err || { tail -3 $O/$f.err; return 1; }
   python - $O/$f.json $f <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); r=d['roofline']
