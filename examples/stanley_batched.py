@@ -4,7 +4,12 @@
 controller reads cte / heading_error from the env's device tensors and writes the action tensor, the reference's
 wrappers (CTE sparse reward, CTE and crash termination) run inside the step kernel, finished envs re-spawn on the device.
 
-    python examples/stanley_batched.py [--envs 4096] [--steps 600] [--maneuver 3]
+    python examples/stanley_batched.py [--envs 4096] [--steps 600] [--maneuver 3] [--randomize]
+
+--randomize: every episode of every env drives its own car, drawn on the device at the re-spawn (wheelbase, track width,
+speed and steering limits within +-20 %), plus the steering shift of the reference's TD3 study (examples/train_td3.py:37,
+146-147: STEERING_SHIFT = -0.01, here drawn per episode from [-0.01, 0]); the controller normalises its steering by each
+env's own max_steering_angle, read from the live per-env rows (vec.env_car_params).
 """
 import argparse
 import math
@@ -20,9 +25,14 @@ from tinycarlo_amd.config import bundled_config  # noqa: E402
 from tinycarlo_amd.wrapper import CrashTerminationWrapper, CTESparseRewardWrapper, CTETerminationWrapper  # noqa: E402
 
 
-def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0", seed=2):
+def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0", seed=2, randomize=False):
     vec = TinyCarloVecEnv(bundled_config("config_simple_layout.yaml"), num_envs=num_envs, device=device,
                           autoreset=True, spawn="device")
+    if randomize:
+        p = vec.car_params
+        vec.randomize_cars({name: (0.8 * getattr(p, name), 1.2 * getattr(p, name))
+                            for name in ("wheelbase", "track_width", "max_velocity", "max_steering_angle")}
+                           | {"steering_shift": (-0.01, 0.0)}, seed=seed)
     env = CrashTerminationWrapper(CTETerminationWrapper(CTESparseRewardWrapper(vec, 0.01), 0.07, number_of_steps=5))
     obs, info = env.reset(seed=seed)
     max_steer = math.radians(vec.car_params.max_steering_angle)
@@ -36,6 +46,8 @@ def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0",
     t0 = time.perf_counter()
     for _ in range(steps):
         cte, he = vec.out["cte"], vec.out["heading_error"]          # of the previous step, already on the device
+        if randomize:  # this episode's car of every env (the rows change at each re-spawn)
+            max_steer = torch.deg2rad(vec.env_car_params[:, 3])
         cc[:, 1] = (he + torch.atan2(k * cte, torch.full_like(cte, speed))) / max_steer
         vec.step_device(cc, man)                                      # one kernel: physics, tracking, camera, wrappers
         ret += vec.out["reward"]
@@ -46,6 +58,8 @@ def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0",
     out = {"envs": num_envs, "steps": steps, "env_steps_per_s": num_envs * steps / dt,
            "mean_abs_cte_m": float(cte_abs) / steps, "episodes_ended": int(ended),
            "mean_reward_per_step": float(ret.mean()) / steps, "obs_shape": tuple(vec.out["obs"].shape)}
+    if randomize:
+        out["car_episodes_drawn"] = int(vec.car_episode.sum())
     vec.close()
     return out
 
@@ -55,5 +69,6 @@ if __name__ == "__main__":
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=600)
     ap.add_argument("--maneuver", type=int, default=3)
+    ap.add_argument("--randomize", action="store_true", help="per-episode car constants and steering shift")
     a = ap.parse_args()
-    print(run(a.envs, a.steps, a.maneuver))
+    print(run(a.envs, a.steps, a.maneuver, randomize=a.randomize))

@@ -44,7 +44,9 @@
 extern "C" {
 #endif
 
-#define TC_ABI_VERSION 5
+/* ABI 6: per-env car constants and their per-episode draw (tc_env_set_car, tc_env_set_car_per_env,
+ * tc_env_set_car_randomization, TC_CAR_*) */
+#define TC_ABI_VERSION 6
 #define TC_MAX_LAYERS 16
 
 /* error codes */
@@ -131,6 +133,21 @@ typedef struct {
   int32_t has_steering_speed, has_max_acceleration;
 } tc_car_params;
 
+/* Per-env car constants (tc_env_set_car_per_env): one row of TC_CAR_NP doubles per env, columns below.  T (1/fps) and
+ * the presence flags has_steering_speed / has_max_acceleration stay shared; a column whose presence flag is 0 is
+ * ignored.  The steering input of env i becomes np.clip(st + row[i][TC_CAR_STEERING_SHIFT], -1, 1) (the shift is added
+ * before the clamp, examples/train_td3.py:146-148).  Wheelbase: kinematics, front axle and re-spawn pose; track width:
+ * the base reward / termination (env.py:93,99) and the fused terms; the rest: the kinematic update (car.py:70-125). */
+#define TC_CAR_NP 8
+#define TC_CAR_WHEELBASE 0
+#define TC_CAR_TRACK_WIDTH 1
+#define TC_CAR_MAX_VELOCITY 2
+#define TC_CAR_MAX_STEERING_ANGLE 3
+#define TC_CAR_STEERING_SPEED 4
+#define TC_CAR_MAX_ACCELERATION 5
+#define TC_CAR_MAX_DECELERATION 6
+#define TC_CAR_STEERING_SHIFT 7
+
 /* camera.py:12-24; E and K are computed on the host exactly as camera.py:145-178 does */
 typedef struct {
   int32_t height, width;
@@ -183,6 +200,26 @@ int tc_env_set_camera(tc_env* env, const tc_camera_params* cam);
  * K: device double [N][9], caller owned and read by every launch until replaced; (NULL, NULL) returns to the shared
  * camera of tc_env_create / tc_env_set_camera.  Resolution, max_range, thickness and format stay shared. */
 int tc_env_set_camera_per_env(tc_env* env, const double* E, const double* K);
+/* New shared car (Car constants assigned at run time: the reference's Car.step reads them on every step, car.py:70-125).
+ * Takes effect for launches enqueued afterwards; T must stay the value of tc_env_create. */
+int tc_env_set_car(tc_env* env, const tc_car_params* car);
+/* Per-env cars.  params: device double [N][TC_CAR_NP], caller owned, read (and, with tc_env_set_car_randomization,
+ * written) by every launch until replaced; NULL returns to the shared car and drops the randomisation.  The kernels
+ * that read it are separate instantiations chosen at launch: the shared-car kernels are unchanged. */
+int tc_env_set_car_per_env(tc_env* env, double* params);
+/* Per-episode randomisation of the per-env cars.  On every re-spawn of env i by the library (tc_reset of an env the
+ * mask selects, or a TC_F_AUTORESET re-spawn in either spawn mode), before the new pose is set:
+ *   z = SplitMix64(SplitMix64(seed)[0x636172])[(env_offset + i) << 32 | episode[i]]
+ *   params[i][j] = lo[j] + (hi[j] - lo[j]) * ((SplitMix64(z)[j] >> 11) * 2^-53)   for every column j in column_mask
+ *   episode[i] += 1
+ * (tinycarlo_amd/csrc/tc_rng.h: tc_car_stream, tc_car_draw).  Columns outside the mask keep their values; lo == hi gives
+ * exactly lo.  lo, hi: HOST arrays of TC_CAR_NP, copied into a library-owned device table that is updated in place (a
+ * captured graph sees new ranges, mask and seed without re-capture; the call waits for the device).  episode: device
+ * int32 [N], caller owned.  env_offset: index of env 0 in a larger population (shards of a multi-GPU run draw the rows
+ * one batch would).  column_mask = 0 stops resampling.  TC_E_INVALID without per-env params, with lo > hi, a non-finite
+ * bound, a mask bit >= TC_CAR_NP or a bit for a column whose presence flag is 0. */
+int tc_env_set_car_randomization(tc_env* env, const double* lo, const double* hi, uint32_t column_mask, uint64_t seed,
+                                 uint32_t env_offset, int32_t* episode);
 /* Installs n_terms (0..TC_MAX_TERMS) reward / termination terms; they apply to every tc_step enqueued afterwards
  * (the call waits for earlier launches).  Each term starts from the reward / terminated value left by the one
  * before it, the first from the base values of env.py:136-138 (0 / false under TC_F_WRAPPED, which the reference

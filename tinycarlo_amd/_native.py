@@ -18,7 +18,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # TINYCARLO_HIP_LIB: load another build of the same library (tools/phase_clock.py uses the instrumented one)
 LIB_PATH = os.environ.get("TINYCARLO_HIP_LIB") or os.path.join(_HERE, "libtinycarlo_hip.so")
 
-ABI_VERSION = 5
+ABI_VERSION = 6
+# per-env car parameter rows (tc_env_set_car_per_env): column order of TC_CAR_*
+CAR_NP = 8
+CAR_WHEELBASE, CAR_TRACK_WIDTH, CAR_MAX_VELOCITY, CAR_MAX_STEERING_ANGLE = 0, 1, 2, 3
+CAR_STEERING_SPEED, CAR_MAX_ACCELERATION, CAR_MAX_DECELERATION, CAR_STEERING_SHIFT = 4, 5, 6, 7
+CAR_COLUMNS = ("wheelbase", "track_width", "max_velocity", "max_steering_angle", "steering_speed", "max_acceleration",
+               "max_deceleration", "steering_shift")
 MAX_TERMS, MAX_LAYERS = 8, 16
 FMT_RGB, FMT_CLASSES = 0, 1
 F32, F64 = 0, 1
@@ -26,7 +32,8 @@ F_NO_OBSERVATION, F_WRAPPED, F_AUTORESET, F_DEVICE_SPAWN = 1, 2, 4, 8
 S_UTURN_NO_EDGE, S_PICK_EMPTY, S_BAD_SPAWN, S_NOT_RESET, S_SPAWN_WRAPPED = 1, 2, 4, 8, 16
 
 EXPORTS = ["tc_abi_version", "tc_last_error", "tc_map_create", "tc_map_destroy", "tc_env_create", "tc_env_destroy",
-           "tc_env_bind", "tc_env_set_camera", "tc_env_set_camera_per_env", "tc_env_set_terms", "tc_env_set_spawn_table", "tc_env_set_noise", "tc_noise", "tc_env_obs_bytes", "tc_env_lds_bytes", "tc_env_profile",
+           "tc_env_bind", "tc_env_set_camera", "tc_env_set_camera_per_env", "tc_env_set_car", "tc_env_set_car_per_env",
+           "tc_env_set_car_randomization", "tc_env_set_terms", "tc_env_set_spawn_table", "tc_env_set_noise", "tc_noise", "tc_env_obs_bytes", "tc_env_lds_bytes", "tc_env_profile",
            "tc_env_profile_read", "tc_reset", "tc_step", "tc_step_multi", "tc_env_reserve_steps", "tc_env_launch_info", "tc_env_draw_list_stats", "tc_render",
            "tc_render_segments"]
 
@@ -114,6 +121,9 @@ def lib():
     L.tc_env_bind.argtypes = [C.c_void_p, C.POINTER(Buffers)]
     L.tc_env_set_camera.argtypes = [C.c_void_p, C.POINTER(CameraParamsC)]
     L.tc_env_set_camera_per_env.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tc_env_set_car.argtypes = [C.c_void_p, C.POINTER(CarParamsC)]
+    L.tc_env_set_car_per_env.argtypes = [C.c_void_p, C.c_void_p]
+    L.tc_env_set_car_randomization.argtypes = [C.c_void_p, _dp, _dp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]
     L.tc_env_set_terms.argtypes = [C.c_void_p, C.POINTER(TermC), C.c_int32, C.c_void_p]
     L.tc_env_set_spawn_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64]
     L.tc_env_set_noise.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64]

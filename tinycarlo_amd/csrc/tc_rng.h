@@ -28,6 +28,19 @@ TC_HD uint32_t tc_spawn_index(uint64_t seed, uint32_t env, uint32_t cursor, uint
   return (uint32_t)(((z >> 32) * (uint64_t)count) >> 32);
 }
 
+// Per-episode car parameters (tc_env_set_car_randomization).  Episode `episode` of env `env` (global index: the
+// caller's env_offset + the env's index in the batch) draws column j of its row as lo_j + (hi_j - lo_j) * u_j with
+// u_j = the top 53 bits of output j of the sub-stream SplitMix64(s')[env << 32 | episode], s' = SplitMix64(seed)[0x636172]
+// ("car": a stream of its own, apart from the spawn stream of the same seed).  u_j is in [0, 1), so lo == hi gives lo.
+// Two roundings (the product, then the sum): the library and the oracle are built with -ffp-contract=off.
+TC_HD uint64_t tc_car_stream(uint64_t seed, uint32_t env, uint32_t episode) {
+  return tc_splitmix64_at(tc_splitmix64_at(seed, 0x636172ull), ((uint64_t)env << 32) | episode);
+}
+TC_HD double tc_car_draw(uint64_t z, int j, double lo, double hi) {
+  const double u = (double)(tc_splitmix64_at(z, (uint64_t)j) >> 11) * 0x1p-53;
+  return lo + (hi - lo) * u;
+}
+
 // One blob of NoiseObservationWrapper (wrapper/observation.py:18-20): centre (x, y) inside the frame, radius in
 // [1, max_radius), mode 1 = "copy in" with probability 0.3 (else erase), src = the plane copied from.  Blob k of
 // (env, step) takes two outputs of the sub-stream SplitMix64(seed)[env << 32 | step].  The reference draws these

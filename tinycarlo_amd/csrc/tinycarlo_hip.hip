@@ -320,6 +320,62 @@ __device__ __forceinline__ double uni_d(double v) {
   return __hiloint2double(hi, lo);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Per-env car constants (tc_env_set_car_per_env): row [env][TC_CAR_NP] of a caller-owned device buffer replaces the
+// shared car's wheelbase, track width and limits; T and the two presence flags stay shared.  Only the *_car kernels
+// (the PER instantiations of the simulate stages, chosen at launch) read it: the shared-car kernels compile as before.
+// With tc_env_set_car_randomization, every re-spawn draws the masked columns of the env's next episode first
+// (tc_car_stream / tc_car_draw, tc_rng.h) and writes them back to the row, so the row always holds the constants in force.
+struct CarDrawTab {  // library owned, updated in place by tc_env_set_car_randomization (a captured graph sees new ranges)
+  double lo[TC_CAR_NP], hi[TC_CAR_NP];
+  unsigned long long seed;
+  unsigned int mask, env_offset;  // mask 0: no resampling
+};
+struct CarRows {
+  double* rows;           // [N][TC_CAR_NP] (caller owned)
+  const CarDrawTab* tab;  // NULL: no resampling
+  int* episode;           // [N] episodes drawn so far (caller owned)
+};
+typedef const __attribute__((address_space(4))) CarDrawTab* CarDrawTabConst;  // never written by a kernel: scalar loads
+
+// a constant of the env's row, read where it is used (UNI: the env is wave-uniform, the value goes to SGPRs)
+template <bool UNI>
+__device__ __forceinline__ double car_ld(const double* row, int j) {
+  return UNI ? uni_d(row[j]) : row[j];
+}
+// the env's car: shared T and presence flags, the rest from its row (unused loads are dropped by the compiler)
+template <bool UNI>
+__device__ __forceinline__ DevCar car_of(const DevCar& shared, const double* row) {
+  DevCar c = shared;
+  c.wheelbase = car_ld<UNI>(row, TC_CAR_WHEELBASE);
+  c.track_width = car_ld<UNI>(row, TC_CAR_TRACK_WIDTH);
+  c.max_velocity = car_ld<UNI>(row, TC_CAR_MAX_VELOCITY);
+  c.max_steering_angle = car_ld<UNI>(row, TC_CAR_MAX_STEERING_ANGLE);
+  c.steering_speed = car_ld<UNI>(row, TC_CAR_STEERING_SPEED);
+  c.max_acceleration = car_ld<UNI>(row, TC_CAR_MAX_ACCELERATION);
+  c.max_deceleration = car_ld<UNI>(row, TC_CAR_MAX_DECELERATION);
+  return c;
+}
+// A re-spawn of env `env` (before d_reset): the masked columns of its next episode's row, and the episode counter.  The
+// writer stores them; every lane that reads the row later is of the same wavefront (stores and loads in program order).
+template <bool UNI>
+__device__ __forceinline__ void car_respawn(const CarRows& cr, int env, bool writer) {
+  if (!cr.tab) return;
+  const CarDrawTabConst t = (CarDrawTabConst)(unsigned long long)cr.tab;
+  const unsigned int mask = t->mask;
+  if (mask == 0) return;
+  const int ep = UNI ? uni_i(cr.episode[env]) : cr.episode[env];
+  const uint64_t z = tc_car_stream(t->seed, (uint32_t)(t->env_offset + (unsigned int)env), (uint32_t)ep);
+  double* row = cr.rows + (size_t)env * TC_CAR_NP;
+#pragma unroll
+  for (int j = 0; j < TC_CAR_NP; j++)
+    if ((mask >> j) & 1u) {
+      const double v = tc_car_draw(z, j, t->lo[j], t->hi[j]);
+      if (writer) row[j] = v;
+    }
+  if (writer) cr.episode[env] = ep + 1;
+}
+
 // (scalars by value: a reference to the kernel-argument struct would force a copy of it into scratch)
 // my_cnt: lane t < TC_MAX_TERMS holds steps_true of term slot t (loaded at kernel start, stored by the caller)
 __device__ __forceinline__ void d_apply_terms(const tc_term* terms, int n_terms, int& my_cnt, double tw, int tid, int C,
@@ -908,11 +964,13 @@ struct FramePose {
   double x, y, cth, sth;
 };
 
-template <int K>
+// PER: the env's car constants come from its row of cr.rows (per-env cars, tc_env_set_car_per_env), else a.car.
+template <int K, bool PER = false>
 __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, int env, int mode,
                                 const void* car_control, int cdtype,
                                 const int* maneuver, const int* spawn_nodes, const unsigned char* mask,
-                                unsigned int flags, const RollStep& roll, const int tid, MapCache<K>& mc, FramePose& fp) {
+                                unsigned int flags, const RollStep& roll, const int tid, MapCache<K>& mc, FramePose& fp,
+                                const CarRows& cr = CarRows()) {
 
   TSTAMP(0);
   TSTAMP_REAL(30);
@@ -952,8 +1010,10 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
   pinfo.ax = pinfo.ay = pinfo.bx = pinfo.by = pinfo.ori = 0;
   pinfo.valid = 0;
   bool fresh = false;  // env was (re)spawned in this launch: info is empty (car.py:47-51)
+  const double* crow = PER ? cr.rows + (size_t)env * TC_CAR_NP : nullptr;
   if (mode == MODE_RESET) {
-    d_reset(m, a.car, s, checked_spawn(m, spawn_nodes[env], status));
+    if (PER) car_respawn<true>(cr, env, true);
+    d_reset(m, PER ? car_of<true>(a.car, crow) : a.car, s, checked_spawn(m, spawn_nodes[env], status));
     fresh = true;
     have_trig = true;
   } else if (mode == MODE_STEP) {
@@ -966,7 +1026,8 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
         if ((unsigned)cur >= (unsigned)b.spawn_queue_len) status |= TC_S_SPAWN_WRAPPED;  // replaying the queue
         node = b.spawn_queue[(size_t)env * b.spawn_queue_len + ((unsigned)cur % (unsigned)b.spawn_queue_len)];
       }
-      d_reset(m, a.car, s, checked_spawn(m, node, status));
+      if (PER) car_respawn<true>(cr, env, true);
+      d_reset(m, PER ? car_of<true>(a.car, crow) : a.car, s, checked_spawn(m, node, status));
       fresh = true;
       have_trig = true;
       cursor = cur + 1;
@@ -983,9 +1044,10 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
         st = ((const double*)car_control)[2 * env + 1];
       }
       v = d_np_clip(v, -1.0, 1.0);  // env.py:118
-      st = d_np_clip(st, -1.0, 1.0);
+      // per-env steering shift: added before the clip (examples/train_td3.py:146-148)
+      st = d_np_clip(PER ? st + car_ld<true>(crow, TC_CAR_STEERING_SHIFT) : st, -1.0, 1.0);
       const int man = maneuver[env];
-      d_car_kinematics(a.car, s, v, st, have_trig);
+      d_car_kinematics(PER ? car_of<true>(a.car, crow) : a.car, s, v, st, have_trig);
       TSTAMP(23);
       const FatGlobal fg = {m.lp_fat, m.lp_nodes};
       trunc = d_find_local_path(m, fg, s, man, status, pinfo, tid);
@@ -1013,9 +1075,10 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
     double reward = 0;
     int terminated = 0;
     if (!(flags & TC_F_WRAPPED) && !fresh) {  // env.py:93,99
-      double r = (-1 / a.car.track_width) * cte + 1;
+      const double tw = PER ? car_ld<true>(crow, TC_CAR_TRACK_WIDTH) : a.car.track_width;
+      double r = (-1 / tw) * cte + 1;
       reward = (0 > r) ? 0 : r;
-      terminated = cte > (a.car.track_width * 10);
+      terminated = cte > (tw * 10);
     }
     const bool late = a.n_terms > 0;  // reward / terminated depend on phase B: written after it
     if (tid == 0) {
@@ -1195,8 +1258,8 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
     if (late) {
       // a re-spawned env did not go through Wrapper.step (the reference's reset() bypasses the wrappers)
       if (!fresh) {
-        d_apply_terms(a.terms, a.n_terms, my_cnt, a.car.track_width, tid, C, cte, have_info ? s.velocity : 0.0, dist_l,
-                      reward, terminated);
+        d_apply_terms(a.terms, a.n_terms, my_cnt, PER ? car_ld<true>(crow, TC_CAR_TRACK_WIDTH) : a.car.track_width, tid, C,
+                      cte, have_info ? s.velocity : 0.0, dist_l, reward, terminated);
         if (tid < TC_MAX_TERMS) lv->cnt[tid] = my_cnt;
       }
       if (tid == 0) {
@@ -2277,6 +2340,7 @@ struct StepArgs {
   const int* spawn_nodes;
   const unsigned char* mask;
   const int* env_order;  // tc_step_kernel: workgroup w works on env env_order[w] (a permutation of 0..N-1), or NULL = env w
+  CarRows cr;            // per-env cars: read by the *_car kernels only (last, so every other member keeps its offset)
 };
 
 // The launch arguments, read through a pointer the optimiser cannot see through.  Inside the step loop of tc_step_multi
@@ -2308,8 +2372,8 @@ __device__ __forceinline__ bool wants_frame(const StepArgs& sa) {
 // What becomes of the frames is the launch's choice: nothing (no observation), the camera stage here and a raster
 // launch behind (cam_here; maps of the K = 13 variant, TC_FUSE=0), or -- the K-step default -- only the poses, from which
 // tc_frame_kernel produces every (step, env) frame as a workgroup of its own.
-template <int K, bool CAM>
-__global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) void tc_env_kernel(StepArgs sa_unused) {
+template <int K, bool CAM, bool PER>
+__device__ __forceinline__ void env_kernel_body() {
   extern __shared__ __align__(16) unsigned char smem[];
   // Touching v127 makes the kernel descriptor ask for 128 VGPRs, i.e. caps the SIMD at the 4 wavefronts the launch
   // needs (N = 4096 one-wavefront workgroups = 4 per SIMD).  The camera-less variant uses 74 registers and would fit 6,
@@ -2349,8 +2413,8 @@ __global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) vo
     MapCache<K> mc = {};  // (initialised: a path that leaves it unset would otherwise make it a loop-carried value -- 30
                           // registers per lane held across the whole step body, raster stage included)
     FramePose fp;
-    sim_body<K>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
-                sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp);
+    sim_body<K, PER>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
+                     sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr);
     if (sa.ma.pose_rows) {
       double pose[12];
       cam_pose12(sa.a, env, fp, pose);
@@ -2376,6 +2440,15 @@ __global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) vo
   TSTAMP_END(t_prev);
   const StepArgs& s1 = step_args();
   if (s1.mode != MODE_RENDER) live_out(s1.a, smem, env);
+}
+template <int K, bool CAM>
+__global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) void tc_env_kernel(StepArgs sa_unused) {
+  env_kernel_body<K, CAM, false>();
+}
+// the same with per-env car constants (StepArgs::cr)
+template <int K, bool CAM>
+__global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) void tc_env_kernel_car(StepArgs sa_unused) {
+  env_kernel_body<K, CAM, true>();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2408,7 +2481,8 @@ struct GroupLds {  // per env of the wavefront: what the reward / termination te
 // kernel with its stores switched off).  The edge scan is ~33 loads per lane and step: from LDS it neither waits for
 // the stores nor pays an L2 round trip per batch of loads.
 typedef const __attribute__((address_space(3))) double* LdsDouble;
-__global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel(StepArgs sa_unused) {
+template <bool PER>
+__device__ __forceinline__ void envg_kernel_body() {
   __shared__ GroupLds glds[TC_ENVG_NT / TC_EL];
   extern __shared__ __align__(16) unsigned char gsm[];
   // Highest issue priority: when this kernel shares the chip with the frame kernel of the previous chunk it is the
@@ -2528,7 +2602,8 @@ __global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel(StepArgs sa_unused)
         if ((unsigned)cur >= (unsigned)b.spawn_queue_len) status |= TC_S_SPAWN_WRAPPED;
         node = b.spawn_queue[(size_t)env * b.spawn_queue_len + ((unsigned)cur % (unsigned)b.spawn_queue_len)];
       }
-      d_reset(m, a.car, s, checked_spawn(m, node, status));
+      if (PER) car_respawn<false>(sa.cr, env, live && sub == 0);  // (one lane of the group writes the row and counter)
+      d_reset(m, PER ? car_of<false>(a.car, sa.cr.rows + (size_t)env * TC_CAR_NP) : a.car, s, checked_spawn(m, node, status));
       fresh = true;
       have_trig = true;
       cursor = cur + 1;
@@ -2545,10 +2620,11 @@ __global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel(StepArgs sa_unused)
         st = cur_d.y;
       }
       v = d_np_clip(v, -1.0, 1.0);  // env.py:118
-      st = d_np_clip(st, -1.0, 1.0);
+      const double* crow = PER ? sa.cr.rows + (size_t)env * TC_CAR_NP : nullptr;
+      st = d_np_clip(PER ? st + car_ld<false>(crow, TC_CAR_STEERING_SHIFT) : st, -1.0, 1.0);  // (train_td3.py:146-148)
       const int man = cur_m;
       TSTAMP(25);
-      d_car_kinematics(a.car, s, v, st, have_trig);
+      d_car_kinematics(PER ? car_of<false>(a.car, crow) : a.car, s, v, st, have_trig);
       TSTAMP(26);
       have_trig = true;
       track = true;
@@ -2612,9 +2688,10 @@ __global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel(StepArgs sa_unused)
     reward = 0;
     terminated = 0;
     if (!(flags & TC_F_WRAPPED) && !fresh) {
-      double r = (-1 / a.car.track_width) * cte + 1;
+      const double tw = PER ? car_ld<false>(sa.cr.rows + (size_t)env * TC_CAR_NP, TC_CAR_TRACK_WIDTH) : a.car.track_width;
+      double r = (-1 / tw) * cte + 1;
       reward = (0 > r) ? 0 : r;
-      terminated = cte > (a.car.track_width * 10);
+      terminated = cte > (tw * 10);
     }
     // ---- phase B: nearest lane-line edge and distance per layer (car.py:55-64, layer.py:33-44,126-164)
     const int C = m.C;
@@ -2730,8 +2807,9 @@ __global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel(StepArgs sa_unused)
     TSTAMP(14);
     // ---- reward / termination wrappers (a re-spawned env did not go through Wrapper.step)
     if (a.n_terms > 0 && !fresh)
-      d_apply_terms_mem(a.terms, a.n_terms, gl.cnt, a.car.track_width, C, cte, have_info ? s.velocity : 0.0, gl.dist, reward,
-                        terminated);
+      d_apply_terms_mem(a.terms, a.n_terms, gl.cnt,
+                        PER ? car_ld<false>(sa.cr.rows + (size_t)env * TC_CAR_NP, TC_CAR_TRACK_WIDTH) : a.car.track_width, C,
+                        cte, have_info ? s.velocity : 0.0, gl.dist, reward, terminated);
     nr = (flags & TC_F_AUTORESET) ? (terminated || trunc) : 0;
     // ---- this step's rollout rows and pose row
     if (live && sub == 0) {
@@ -2781,6 +2859,9 @@ __global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel(StepArgs sa_unused)
   }
   if (live && s1.a.term_counters && sub < s1.a.n_terms) s1.a.term_counters[(size_t)env * TC_MAX_TERMS + sub] = gl.cnt[sub];
 }
+__global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel(StepArgs sa_unused) { envg_kernel_body<false>(); }
+// the same with per-env car constants (StepArgs::cr)
+__global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel_car(StepArgs sa_unused) { envg_kernel_body<true>(); }
 
 // One (step, env) frame per workgroup: camera stage from the pose the simulate launch left, then the raster stage.
 // Frames do not depend on each other, a launch has steps x N of them -- many more than the chip holds at once -- and
@@ -2950,8 +3031,8 @@ __global__ __launch_bounds__(TC_NT) void tc_frame_recover_kernel(FrameArgs fa_un
 // All stages in one launch: the same wavefront simulates its env, runs the camera and rasterises the frame.  The form
 // of tc_step / tc_reset / tc_render (one step: nothing to balance, and one kernel boundary less), and of tc_step_multi
 // under TC_MULTI_SPLIT=0.
-template <int K, bool THICK, int FMT, int RBT = RB_OF_K(K)>
-__global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_kernel(StepArgs sa_unused) {
+template <int K, bool THICK, int FMT, int RBT, bool PER>
+__device__ __forceinline__ void step_kernel_body() {
   extern __shared__ __align__(16) unsigned char smem[];
   const StepArgs& s0 = step_args();
   if ((int)blockIdx.x >= s0.a.N) return;
@@ -2975,8 +3056,8 @@ __global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_
     MapCache<K> mc = {};  // (initialised: a path that leaves it unset would otherwise make it a loop-carried value -- 30
                           // registers per lane held across the whole step body, raster stage included)
     FramePose fp;
-    sim_body<K>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
-                sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp);
+    sim_body<K, PER>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
+                     sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr);
     if (wants_frame(sa)) {
       int nseg;
       unsigned int used;
@@ -2999,6 +3080,15 @@ __global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_
   TSTAMP_END(t_prev);
   const StepArgs& s1 = step_args();
   if (s1.mode != MODE_RENDER) live_out(s1.a, smem, env);
+}
+template <int K, bool THICK, int FMT, int RBT = RB_OF_K(K)>
+__global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_kernel(StepArgs sa_unused) {
+  step_kernel_body<K, THICK, FMT, RBT, false>();
+}
+// the same with per-env car constants (StepArgs::cr)
+template <int K, bool THICK, int FMT, int RBT = RB_OF_K(K)>
+__global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_kernel_car(StepArgs sa_unused) {
+  step_kernel_body<K, THICK, FMT, RBT, true>();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3081,12 +3171,31 @@ typedef void (*fused_kern_t)(StepArgs);
 #define TC_DEV_SRB RB_OF_K(TC_DEV_SK)
 #endif
 template <int K, int RBT = RB_OF_K(K)>
-static fused_kern_t pick_fused(bool thick, bool cls) {
+static fused_kern_t pick_fused(bool thick, bool cls, bool per = false) {
 #ifdef TC_DEV_FAST
-  return tc_step_kernel<TC_DEV_SK, true, TC_DEV_FMTV, TC_DEV_SRB>;
+  return per ? tc_step_kernel_car<TC_DEV_SK, true, TC_DEV_FMTV, TC_DEV_SRB> : tc_step_kernel<TC_DEV_SK, true, TC_DEV_FMTV, TC_DEV_SRB>;
 #else
+  if (per)
+    return thick ? (cls ? tc_step_kernel_car<K, true, TC_FMT_CLASSES, RBT> : tc_step_kernel_car<K, true, TC_FMT_RGB, RBT>)
+                 : (cls ? tc_step_kernel_car<K, false, TC_FMT_CLASSES, RBT> : tc_step_kernel_car<K, false, TC_FMT_RGB, RBT>);
   return thick ? (cls ? tc_step_kernel<K, true, TC_FMT_CLASSES, RBT> : tc_step_kernel<K, true, TC_FMT_RGB, RBT>)
                : (cls ? tc_step_kernel<K, false, TC_FMT_CLASSES, RBT> : tc_step_kernel<K, false, TC_FMT_RGB, RBT>);
+#endif
+}
+// simulate stage alone (tc_env_kernel), by register-cache variant; per: the per-env-car instantiation
+typedef void (*env_kern_t)(StepArgs);
+static env_kern_t pick_env(int kv, bool cam, bool per) {
+#ifdef TC_DEV_FAST
+  (void)kv;
+  return per ? (cam ? tc_env_kernel_car<TC_DEV_KV, true> : tc_env_kernel_car<TC_DEV_KV, false>)
+             : (cam ? tc_env_kernel<TC_DEV_KV, true> : tc_env_kernel<TC_DEV_KV, false>);
+#else
+  if (per) {
+    if (cam) return kv == 5 ? tc_env_kernel_car<5, true> : kv == 8 ? tc_env_kernel_car<8, true> : kv == 9 ? tc_env_kernel_car<9, true> : tc_env_kernel_car<13, true>;
+    return kv == 5 ? tc_env_kernel_car<5, false> : kv == 8 ? tc_env_kernel_car<8, false> : kv == 9 ? tc_env_kernel_car<9, false> : tc_env_kernel_car<13, false>;
+  }
+  if (cam) return kv == 5 ? tc_env_kernel<5, true> : kv == 8 ? tc_env_kernel<8, true> : kv == 9 ? tc_env_kernel<9, true> : tc_env_kernel<13, true>;
+  return kv == 5 ? tc_env_kernel<5, false> : kv == 8 ? tc_env_kernel<8, false> : kv == 9 ? tc_env_kernel<9, false> : tc_env_kernel<13, false>;
 #endif
 }
 
@@ -3152,6 +3261,8 @@ struct tc_map {
 struct tc_env {
   const tc_map* map;
   KArgs k;
+  CarRows cr;            // per-env cars (tc_env_set_car_per_env / tc_env_set_car_randomization); rows NULL = shared car
+  CarDrawTab* car_tab;   // device copy of the randomisation ranges (library owned, updated in place), or NULL
   bool bound;
   int64_t obs_bytes;
   int r_off_tab, r_off_bits, r_lds;
@@ -3854,11 +3965,11 @@ extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const 
     if (e->frame_lds > lds) lds = e->frame_lds;
     if (lds > 48 * 1024) {
       for (int t = 0; t < 2; t++)
-        for (int c = 0; c < 2; c++) {
-          (void)hipFuncSetAttribute((const void*)pick_fused<5>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-          (void)hipFuncSetAttribute((const void*)pick_fused<5, 16>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-          (void)hipFuncSetAttribute((const void*)pick_fused<8>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-          (void)hipFuncSetAttribute((const void*)pick_fused<9>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        for (int c = 0; c < 4; c++) {  // (c & 2: the per-env-car instantiation)
+          (void)hipFuncSetAttribute((const void*)pick_fused<5>(t, c & 1, c & 2), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+          (void)hipFuncSetAttribute((const void*)pick_fused<5, 16>(t, c & 1, c & 2), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+          (void)hipFuncSetAttribute((const void*)pick_fused<8>(t, c & 1, c & 2), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+          (void)hipFuncSetAttribute((const void*)pick_fused<9>(t, c & 1, c & 2), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
           (void)hipFuncSetAttribute((const void*)pick_frame<5>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
           (void)hipFuncSetAttribute((const void*)pick_frame<5, 16>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
           (void)hipFuncSetAttribute((const void*)pick_frame<8>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -3869,7 +3980,8 @@ extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const 
   {  // tc_envg_kernel's LDS copies of the map (edge records + fat lanepath nodes, see launch()) can exceed the 48 KB default
     const size_t envg_lds = ((size_t)m.total_edges * 48 + 15) / 16 * 16 + (size_t)m.lpN * sizeof(LpNode);
     if (envg_lds > 40 * 1024)
-      (void)hipFuncSetAttribute((const void*)tc_envg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(envg_lds < 150 * 1024 ? envg_lds : 150 * 1024));
+      for (const void* g : {(const void*)tc_envg_kernel, (const void*)tc_envg_kernel_car})
+        (void)hipFuncSetAttribute(g, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(envg_lds < 150 * 1024 ? envg_lds : 150 * 1024));
   }
 #ifndef TC_DEV_FAST
   if (e->r_lds > 48 * 1024) {
@@ -3880,10 +3992,10 @@ extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const 
   }
   if (L.total > 48 * 1024) {
     hipError_t he = hipSuccess;
-    const void* ek[8] = {(const void*)tc_env_kernel<5, true>,  (const void*)tc_env_kernel<8, true>,  (const void*)tc_env_kernel<9, true>,
-                         (const void*)tc_env_kernel<13, true>, (const void*)tc_env_kernel<5, false>, (const void*)tc_env_kernel<8, false>,
-                         (const void*)tc_env_kernel<9, false>, (const void*)tc_env_kernel<13, false>};
-    for (int i = 0; i < 8 && he == hipSuccess; i++) he = hipFuncSetAttribute(ek[i], hipFuncAttributeMaxDynamicSharedMemorySize, L.total);
+    static const int kvs[4] = {5, 8, 9, 13};
+    for (int i = 0; i < 16 && he == hipSuccess; i++)  // every tc_env_kernel / tc_env_kernel_car variant
+      he = hipFuncSetAttribute((const void*)pick_env(kvs[i & 3], (i & 4) == 0, (i & 8) != 0),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, L.total);
     if (he != hipSuccess) {
       set_err(std::string("hipFuncSetAttribute: ") + hipGetErrorString(he));
       delete e;
@@ -4012,6 +4124,7 @@ extern "C" int tc_env_destroy(tc_env* e) {
   if (e && e->k.terms) (void)hipFree((void*)e->k.terms);
   if (e && e->k.spawn_tab) (void)hipFree((void*)e->k.spawn_tab);
   if (e && e->noise_hw) (void)hipFree(e->noise_hw);
+  if (e && e->car_tab) (void)hipFree(e->car_tab);
   if (e && e->noise_step) (void)hipFree(e->noise_step);
   delete e;
   return TC_OK;
@@ -4034,6 +4147,87 @@ extern "C" int tc_env_bind(tc_env* e, const tc_buffers* b) {
   }
   e->k.b = *b;
   e->bound = true;
+  return TC_OK;
+}
+
+static bool car_ok(const tc_car_params* c) {
+  const double v[7] = {c->wheelbase, c->track_width, c->max_velocity, c->max_steering_angle, c->steering_speed,
+                       c->max_acceleration, c->max_deceleration};
+  for (int i = 0; i < 7; i++)
+    if (!isfinite(v[i])) return false;
+  return true;
+}
+
+extern "C" int tc_env_set_car(tc_env* e, const tc_car_params* car) {
+  if (!e || !car) return TC_E_INVALID;
+  if (car->T != e->k.car.T || car->has_steering_speed != e->k.car.has_steering_speed ||
+      car->has_max_acceleration != e->k.car.has_max_acceleration || !car_ok(car)) {
+    set_err("tc_env_set_car: T and the presence flags are fixed at tc_env_create, and every constant must be finite");
+    return TC_E_INVALID;
+  }
+  DevCar& c = e->k.car;
+  c.wheelbase = car->wheelbase;
+  c.track_width = car->track_width;
+  c.max_velocity = car->max_velocity;
+  c.max_steering_angle = car->max_steering_angle;
+  c.steering_speed = car->steering_speed;
+  c.max_acceleration = car->max_acceleration;
+  c.max_deceleration = car->max_deceleration;
+  return TC_OK;
+}
+
+extern "C" int tc_env_set_car_per_env(tc_env* e, double* params) {
+  if (!e) return TC_E_INVALID;
+  e->cr.rows = params;
+  if (!params) {  // back to the shared car: nothing left to randomise
+    e->cr.tab = nullptr;
+    e->cr.episode = nullptr;
+  }
+  return TC_OK;
+}
+
+extern "C" int tc_env_set_car_randomization(tc_env* e, const double* lo, const double* hi, uint32_t column_mask,
+                                            uint64_t seed, uint32_t env_offset, int32_t* episode) {
+  if (!e) return TC_E_INVALID;
+  if (!e->cr.rows) {
+    set_err("tc_env_set_car_randomization: no per-env car params installed (tc_env_set_car_per_env)");
+    return TC_E_INVALID;
+  }
+  if (column_mask >> TC_CAR_NP) {
+    set_err("tc_env_set_car_randomization: column mask has bits beyond TC_CAR_NP");
+    return TC_E_INVALID;
+  }
+  const uint32_t absent = (e->k.car.has_steering_speed ? 0u : 1u << TC_CAR_STEERING_SPEED) |
+                          (e->k.car.has_max_acceleration ? 0u : (1u << TC_CAR_MAX_ACCELERATION) | (1u << TC_CAR_MAX_DECELERATION));
+  if (column_mask & absent) {
+    set_err("tc_env_set_car_randomization: a range for a column the car does not have (steering_speed / max_acceleration)");
+    return TC_E_INVALID;
+  }
+  if (column_mask && (!lo || !hi || !episode)) return TC_E_INVALID;
+  CarDrawTab t;
+  memset(&t, 0, sizeof(t));
+  for (int j = 0; j < TC_CAR_NP; j++) {
+    if (!((column_mask >> j) & 1u)) continue;
+    if (!isfinite(lo[j]) || !isfinite(hi[j]) || lo[j] > hi[j]) {
+      set_err("tc_env_set_car_randomization: every range must be finite with lo <= hi");
+      return TC_E_INVALID;
+    }
+    t.lo[j] = lo[j];
+    t.hi[j] = hi[j];
+  }
+  t.seed = seed;
+  t.mask = column_mask;
+  t.env_offset = env_offset;
+  if (!e->car_tab) {
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, sizeof(CarDrawTab)));
+    e->car_tab = (CarDrawTab*)p;
+  }
+  // (in place: a graph captured earlier keeps reading this table; the copy waits for launches that may still read it)
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(e->car_tab, &t, sizeof(t), hipMemcpyHostToDevice));
+  e->cr.tab = e->car_tab;
+  e->cr.episode = column_mask ? episode : e->cr.episode;
   return TC_OK;
 }
 
@@ -4471,13 +4665,11 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
   const int slot = e->prof_n % TC_PROF_RING;
   const int kv = e->kvar;
   // simulate stage alone, with or without the camera stage compiled in (without: fewer registers, half the code)
-#ifdef TC_DEV_FAST
-  auto kern = tc_env_kernel<TC_DEV_KV, true>;
-  auto kern_nocam = tc_env_kernel<TC_DEV_KV, false>;
-#else
-  auto kern = kv == 5 ? tc_env_kernel<5, true> : kv == 8 ? tc_env_kernel<8, true> : kv == 9 ? tc_env_kernel<9, true> : tc_env_kernel<13, true>;
-  auto kern_nocam = kv == 5 ? tc_env_kernel<5, false> : kv == 8 ? tc_env_kernel<8, false> : kv == 9 ? tc_env_kernel<9, false> : tc_env_kernel<13, false>;
-#endif
+  // per-env cars (tc_env_set_car_per_env): the *_car instantiations of the simulate stages, the same launches otherwise
+  const bool per = e->cr.rows != nullptr;
+  auto kern = pick_env(kv, true, per);
+  auto kern_nocam = pick_env(kv, false, per);
+  auto envg = per ? tc_envg_kernel_car : tc_envg_kernel;
   const bool do_raster = !(flags & (TC_F_NO_OBSERVATION | DBG_SKIP_CAMERA)) && (e->k.b.obs || (roll && roll->obs));
   const int N = e->k.N;
   MultiArgs ma;
@@ -4549,6 +4741,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
         StepArgs sa;
         memset(&sa, 0, sizeof(sa));
         sa.a = e->k;
+        sa.cr = e->cr;
         sa.a.env0 = 0;
         sa.a.seg_g = e->st_segm_g;
         sa.a.seg_n = e->st_segm_n;
@@ -4587,7 +4780,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
         sa.ma.map_lds = (e->envg_map_lds && map_bytes <= 40 * 1024) ? 1 : 0;
         sa.ma.fat_lds = (e->envg_map_lds && fat_bytes <= 56 * 1024) ? 1 : 0;
         const unsigned int sim_wgs = (unsigned int)((N + TC_ENVG_NT / TC_EL - 1) / (TC_ENVG_NT / TC_EL));
-        hipLaunchKernelGGL(tc_envg_kernel, dim3(sim_wgs), dim3(TC_ENVG_NT), (sa.ma.map_lds ? map_bytes : 0) + (sa.ma.fat_lds ? fat_bytes : 0),
+        hipLaunchKernelGGL(envg, dim3(sim_wgs), dim3(TC_ENVG_NT), (sa.ma.map_lds ? map_bytes : 0) + (sa.ma.fat_lds ? fat_bytes : 0),
                            main, sa);
         HIP_TRY(hipGetLastError());
         if (prof && c0 + cn >= nsteps) HIP_TRY(hipEventRecord(e->ev[1][slot], main));
@@ -4659,6 +4852,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
       StepArgs sa;
       memset(&sa, 0, sizeof(sa));
       sa.a = e->k;
+      sa.cr = e->cr;
       sa.a.env0 = 0;
       sa.a.seg_g = e->segm_g + rb * N * e->k.seg_cap * 5;
       sa.a.seg_n = e->segm_n + rb * N;
@@ -4703,7 +4897,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
         const size_t map_bytes = ((size_t)e->k.m.total_edges * 48 + 15) / 16 * 16, fat_bytes = (size_t)e->k.m.lpN * sizeof(LpNode);
         sa.ma.map_lds = (e->envg_map_lds && map_bytes <= 40 * 1024) ? 1 : 0;
         sa.ma.fat_lds = (e->envg_map_lds && fat_bytes <= 56 * 1024) ? 1 : 0;
-        hipLaunchKernelGGL(tc_envg_kernel, dim3((N + TC_ENVG_NT / TC_EL - 1) / (TC_ENVG_NT / TC_EL)), dim3(TC_ENVG_NT),
+        hipLaunchKernelGGL(envg, dim3((N + TC_ENVG_NT / TC_EL - 1) / (TC_ENVG_NT / TC_EL)), dim3(TC_ENVG_NT),
                            (sa.ma.map_lds ? map_bytes : 0) + (sa.ma.fat_lds ? fat_bytes : 0), main, sa);
       }
       else
@@ -4801,10 +4995,10 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     const bool thick = e->k.cam.thickness > 1, cls = e->k.cam.format == TC_FMT_CLASSES;
     // (component groups that fit the K = 5 register cache: the K = 5 kernel with 16-segment batches, as for the frame kernel --
     // its simulate stage then walks the map's lane-line nodes in windows of 320 instead of 576)
-    fused_kern_t fk = e->kframe == 516 ? pick_fused<5, 16>(thick, cls)
-                      : kv == 5        ? pick_fused<5>(thick, cls)
-                      : kv == 8        ? pick_fused<8>(thick, cls)
-                                       : pick_fused<9>(thick, cls);
+    fused_kern_t fk = e->kframe == 516 ? pick_fused<5, 16>(thick, cls, per)
+                      : kv == 5        ? pick_fused<5>(thick, cls, per)
+                      : kv == 8        ? pick_fused<8>(thick, cls, per)
+                                       : pick_fused<9>(thick, cls, per);
     KArgs k = e->k;
     k.env0 = 0;
     RArgs r = make_rargs(e, e->k.seg_g, e->k.seg_n, e->k.seg_cap, nullptr, flags, 0, nullptr, mode == MODE_STEP);
@@ -4817,6 +5011,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     StepArgs sa;
     memset(&sa, 0, sizeof(sa));
     sa.a = k;
+    sa.cr = e->cr;
     sa.r = r;
     sa.ma = ma;
     sa.mode = mode;
@@ -4851,6 +5046,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     StepArgs sa;
     memset(&sa, 0, sizeof(sa));
     sa.a = k;
+    sa.cr = e->cr;
     sa.ma = ma;
     sa.ma.cam_here = do_raster ? 1 : 0;
     sa.mode = mode;

@@ -28,20 +28,24 @@ from .vec_env import TinyCarloVecEnv
 
 class _LiveCar:
     """``env.unwrapped.car``: constants (``car.py:12-19``) plus live read-only views of the simulated
-    state (``car.py:25-32``), fetched from the device on access."""
+    state (``car.py:25-32``), fetched from the device on access.  The constants are the engine's own
+    (``TinyCarloVecEnv.car``): ``env.unwrapped.car.max_velocity = 0.2`` takes effect on the next step,
+    as in the reference, whose ``Car.step`` reads them on every step (``car.py:70-125``)."""
 
     def __init__(self, vec: TinyCarloVecEnv):
-        self._v = vec
-        p = vec.car_params
-        self.T = p.T
-        self.track_width = p.track_width
-        self.wheelbase = p.wheelbase
-        self.max_velocity = p.max_velocity
-        self.max_steering_angle = p.max_steering_angle
-        self.steering_speed = p.steering_speed
-        self.max_acceleration = p.max_acceleration
-        self.max_deceleration = p.max_deceleration
-        self.map = vec.map
+        object.__setattr__(self, "_v", vec)
+        object.__setattr__(self, "map", vec.map)
+
+    def __getattr__(self, k: str):
+        if k == "T" or k in self._v.car.CONSTANTS:
+            return getattr(self._v.car, k)
+        raise AttributeError(k)
+
+    def __setattr__(self, k: str, v) -> None:
+        if k == "T" or k in self._v.car.CONSTANTS:
+            setattr(self._v.car, k, v)
+        else:
+            object.__setattr__(self, k, v)
 
     def _f(self, k: str) -> float:
         return float(self._v.state[k][0].item())

@@ -1,0 +1,116 @@
+"""Per-env car constants and their per-episode draw, restated on the host.
+
+The device draws the row of an env's next episode at every re-spawn (``tc_env_set_car_randomization``,
+``csrc/tc_rng.h``: ``tc_car_stream`` / ``tc_car_draw``).  ``draw_car_params`` is the same arithmetic in numpy uint64 /
+float64, so the constants of any past episode can be recomputed on the host -- and tests use it as the check.
+
+The other two helpers turn the user-facing arguments of ``TinyCarloVecEnv.set_env_cars`` / ``randomize_cars`` into
+the library's [N, 8] rows and (lo, hi, mask) tables, with the validation both need (no GPU involved).
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+
+CAR_COLUMNS = ("wheelbase", "track_width", "max_velocity", "max_steering_angle", "steering_speed", "max_acceleration",
+               "max_deceleration", "steering_shift")
+CAR_NP = len(CAR_COLUMNS)
+CAR_STREAM = 0x636172  # "car": the sub-stream of the seed the draws come from (apart from the device spawn stream)
+_GOLDEN, _M1, _M2 = np.uint64(0x9E3779B97F4A7C15), np.uint64(0xBF58476D1CE4E5B9), np.uint64(0x94D049BB133111EB)
+
+
+def splitmix64_at(seed, n):
+    """output n of the SplitMix64 sequence started at `seed` (tc_rng.h: tc_splitmix64_at), elementwise on uint64"""
+    with np.errstate(over="ignore"):
+        z = np.asarray(seed, dtype=np.uint64) + (np.asarray(n, dtype=np.uint64) + np.uint64(1)) * _GOLDEN
+        z = (z ^ (z >> np.uint64(30))) * _M1
+        z = (z ^ (z >> np.uint64(27))) * _M2
+        return z ^ (z >> np.uint64(31))
+
+
+def draw_car_params(seed: int, env_index, episode, lo, hi, mask: int = (1 << CAR_NP) - 1, base=None) -> np.ndarray:
+    """The row env `env_index` (global index: env_offset + index in the batch) draws for episode `episode` (its value
+    of the episode counter at the re-spawn).  env_index / episode may be arrays (broadcast); returns float64
+    [..., 8].  Columns outside `mask` are taken from `base` ([8] or [..., 8]; NaN when not given)."""
+    env = np.asarray(env_index, dtype=np.int64).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    ep = np.asarray(episode, dtype=np.int64).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    env, ep = np.broadcast_arrays(env, ep)
+    s2 = splitmix64_at(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), np.uint64(CAR_STREAM))
+    z = splitmix64_at(s2, (env << np.uint64(32)) | ep)
+    lo = np.asarray(lo, dtype=np.float64).reshape(CAR_NP)
+    hi = np.asarray(hi, dtype=np.float64).reshape(CAR_NP)
+    out = np.full(env.shape + (CAR_NP,), np.nan) if base is None else \
+        np.array(np.broadcast_to(np.asarray(base, dtype=np.float64), env.shape + (CAR_NP,)))
+    for j in range(CAR_NP):
+        if (int(mask) >> j) & 1:
+            u = (splitmix64_at(z, np.uint64(j)) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+            out[..., j] = lo[j] + (hi[j] - lo[j]) * u
+    return out
+
+
+def config_row(p) -> np.ndarray:
+    """[8] row of a CarParams (absent optional constants as 0, steering shift 0)"""
+    return np.array([p.wheelbase, p.track_width, p.max_velocity, p.max_steering_angle,
+                     p.steering_speed if p.steering_speed is not None else 0.0,
+                     p.max_acceleration if p.max_acceleration is not None else 0.0,
+                     p.max_deceleration if p.max_deceleration is not None else 0.0, 0.0], dtype=np.float64)
+
+
+def _absent(p) -> set:
+    a = set()
+    if p.steering_speed is None:
+        a.add("steering_speed")
+    if p.max_acceleration is None:
+        a |= {"max_acceleration", "max_deceleration"}
+    return a
+
+
+def car_rows(p, num_envs: int, values: Dict[str, object]) -> np.ndarray:
+    """[num_envs, 8] rows from the config's car `p` and per-column overrides (a scalar or an [num_envs] sequence /
+    tensor each; None = the config value, shift 0).  Raises ValueError on unknown names, wrong lengths, non-finite
+    values, non-positive constants (the shift may be any finite number) and values for constants the config lacks."""
+    rows = np.tile(config_row(p), (num_envs, 1))
+    absent = _absent(p)
+    for name, v in values.items():
+        if name not in CAR_COLUMNS:
+            raise ValueError(f"unknown car parameter {name!r}; choose from {CAR_COLUMNS}")
+        if v is None:
+            continue
+        if name in absent:
+            raise ValueError(f"car.{name} is not set in the config: the kernel has no such limit to vary")
+        if hasattr(v, "detach"):
+            v = v.detach().cpu().numpy()
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != num_envs):
+            raise ValueError(f"{name}: expected a scalar or {num_envs} values, got shape {a.shape}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"{name}: values must be finite")
+        if name != "steering_shift" and not np.all(a > 0):
+            raise ValueError(f"{name}: values must be positive")
+        rows[:, CAR_COLUMNS.index(name)] = a
+    return rows
+
+
+def car_ranges(p, ranges: Optional[Dict[str, Sequence[float]]]) -> Tuple[np.ndarray, np.ndarray, int]:
+    """(lo[8], hi[8], column mask) of `ranges` = {name: (lo, hi)}; None or {} = no resampling (mask 0)."""
+    lo, hi = np.zeros(CAR_NP), np.zeros(CAR_NP)
+    mask = 0
+    absent = _absent(p)
+    for name, r in (ranges or {}).items():
+        if name not in CAR_COLUMNS:
+            raise ValueError(f"unknown car parameter {name!r}; choose from {CAR_COLUMNS}")
+        if name in absent:
+            raise ValueError(f"car.{name} is not set in the config: no range can be drawn for it")
+        r = np.asarray(r, dtype=np.float64).reshape(-1)
+        if r.shape != (2,):
+            raise ValueError(f"{name}: a range is (lo, hi), got {r.size} values")
+        if not np.all(np.isfinite(r)) or r[0] > r[1]:
+            raise ValueError(f"{name}: range must be finite with lo <= hi, got ({r[0]}, {r[1]})")
+        if name != "steering_shift" and r[0] <= 0:
+            raise ValueError(f"{name}: range must be positive, got ({r[0]}, {r[1]})")
+        j = CAR_COLUMNS.index(name)
+        lo[j], hi[j] = r
+        mask |= 1 << j
+    return lo, hi, mask
+

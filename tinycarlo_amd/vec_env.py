@@ -38,17 +38,37 @@ def _default_device() -> torch.device:
 
 
 class CarView:
-    """What wrappers read from ``env.unwrapped.car`` (``wrapper/reward.py:21,41``): the car constants."""
+    """``env.unwrapped.car``: the car constants (``car.py:12-19``), live like the reference's ``Car`` attributes, which
+    ``Car.step`` reads on every step (``car.py:70-125``).
 
-    def __init__(self, p: CarParams):
-        self.T = p.T
-        self.track_width = p.track_width
-        self.wheelbase = p.wheelbase
-        self.max_velocity = p.max_velocity
-        self.max_steering_angle = p.max_steering_angle
-        self.steering_speed = p.steering_speed
-        self.max_acceleration = p.max_acceleration
-        self.max_deceleration = p.max_deceleration
+    Reading a constant gives the shared car's value -- or, while per-env cars are installed (``set_env_cars`` /
+    ``randomize_cars``), the env's ``[N]`` column of ``env_car_params`` (a view of the live device rows: the torch-side
+    wrappers, ``wrapper/reward.py:20,33``, then broadcast each env's ``track_width``).  Assigning one pushes a new shared
+    car to the engine (``tc_env_set_car``) for the steps that follow; with per-env cars installed it raises."""
+
+    CONSTANTS = ("wheelbase", "track_width", "max_velocity", "max_steering_angle", "steering_speed", "max_acceleration",
+                 "max_deceleration")
+
+    def __init__(self, p: CarParams, env: Optional["TinyCarloVecEnv"] = None):
+        object.__setattr__(self, "_p", p)
+        object.__setattr__(self, "_env", env)
+
+    def __getattr__(self, k: str):
+        if k.startswith("_"):
+            raise AttributeError(k)
+        env = self._env
+        if env is not None and k in self.CONSTANTS and env._car_rows is not None:
+            return env._car_rows[:, nat.CAR_COLUMNS.index(k)]
+        p = env.car_params if env is not None else self._p
+        return getattr(p, k)
+
+    def __setattr__(self, k: str, v) -> None:
+        if k in self.CONSTANTS and self._env is not None:
+            self._env._set_shared_car(**{k: v})
+        elif k == "T":
+            raise AttributeError("car.T is 1 / sim.fps, fixed when the env is created")
+        else:
+            object.__setattr__(self, k, v)
 
 
 class LazyInfo(dict):
@@ -179,7 +199,11 @@ class TinyCarloVecEnv(gym.Env):
 
         self.map = Map(self.config["map"], base_path=self.config_path)
         self.car_params = CarParams.from_config(self.T, self.config["car"])
-        self.car = CarView(self.car_params)
+        self.car = CarView(self.car_params, self)
+        # per-env cars (set_env_cars / randomize_cars): live [N, 8] f64 rows the kernels read and re-draw, or None
+        self._car_rows: Optional[torch.Tensor] = None
+        self._car_episode: Optional[torch.Tensor] = None  # [N] int32 episodes drawn per env (randomize_cars)
+        self._car_rand: Optional[Dict[str, Any]] = None   # lo, hi, mask, seed, env_offset of randomize_cars
         self.camera = Camera(self.config["camera"], on_update=self._push_camera)
         self.layer_names: List[str] = self.map.get_laneline_names()
         self.n_classes = len(self.layer_names)
@@ -313,6 +337,93 @@ class TinyCarloVecEnv(gym.Env):
         Kt = torch.as_tensor(K, dtype=torch.float64).to(self.device).contiguous()
         self._env_cams = (Et, Kt)  # keep the device copies alive: the library reads them on every launch
         nat.check(nat.lib().tc_env_set_camera_per_env(self._h, Et.data_ptr(), Kt.data_ptr()), "tc_env_set_camera_per_env")
+
+    # ------------------------------------------------------------------ car constants: shared, per env, per episode
+    def _set_shared_car(self, **values) -> None:
+        """env.unwrapped.car.<constant> = v: a new shared car for the steps that follow (tc_env_set_car)."""
+        if self._car_rows is not None:
+            raise RuntimeError("per-env car params are installed: change them with set_env_cars(...) / randomize_cars(...), "
+                               "or call set_env_cars() with no argument to return to the shared car first")
+        import dataclasses
+        for k, v in values.items():
+            if getattr(self.car_params, k) is None:
+                raise ValueError(f"car.{k} is not set in the config: the engine has no such limit to change")
+            v = float(v)
+            if not (np.isfinite(v) and v > 0):
+                raise ValueError(f"car.{k} must be a positive finite number, got {v}")
+            values[k] = v
+        p = dataclasses.replace(self.car_params, **values)
+        self._push_car(p)
+        self.car_params = p
+
+    def _push_car(self, p: CarParams) -> None:
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().tc_env_set_car(self._h, C.byref(nat.make_car_params(p))), "tc_env_set_car")
+
+    @property
+    def env_car_params(self) -> Optional[torch.Tensor]:
+        """The live [N, 8] float64 device rows of the per-env cars (columns: ``_native.CAR_COLUMNS``), or None while
+        every env runs the shared car.  With ``randomize_cars`` the engine rewrites an env's row at each re-spawn."""
+        return self._car_rows
+
+    def set_env_cars(self, wheelbase=None, track_width=None, max_velocity=None, max_steering_angle=None,
+                     steering_speed=None, max_acceleration=None, max_deceleration=None, steering_shift=None) -> None:
+        """Per-env car constants: each argument a scalar or an [N] sequence / tensor, None = the config's value (shift 0).
+        The steering input of env i becomes clip(st + steering_shift[i], -1, 1).  With no argument at all: back to the
+        shared car (and no randomisation).  T (fps) stays shared; steering_speed / the acceleration limits only where the
+        config has them."""
+        from .randomization import car_rows
+        vals = dict(wheelbase=wheelbase, track_width=track_width, max_velocity=max_velocity,
+                    max_steering_angle=max_steering_angle, steering_speed=steering_speed, max_acceleration=max_acceleration,
+                    max_deceleration=max_deceleration, steering_shift=steering_shift)
+        if all(v is None for v in vals.values()):
+            self._install_car_rows(None)
+            return
+        self._install_car_rows(torch.as_tensor(car_rows(self.car_params, self.num_envs, vals), dtype=torch.float64))
+
+    def _install_car_rows(self, rows: Optional[torch.Tensor]) -> None:
+        with torch.cuda.device(self.device):
+            if rows is None:
+                nat.check(nat.lib().tc_env_set_car_per_env(self._h, None), "tc_env_set_car_per_env")
+                self._car_rows = self._car_episode = self._car_rand = None
+                return
+            if self._car_rows is None:
+                self._car_rows = torch.empty((self.num_envs, nat.CAR_NP), dtype=torch.float64, device=self.device)
+            self._car_rows.copy_(rows)
+            nat.check(nat.lib().tc_env_set_car_per_env(self._h, self._car_rows.data_ptr()), "tc_env_set_car_per_env")
+
+    def randomize_cars(self, ranges: Optional[Dict[str, Sequence[float]]], seed: int = 0, env_offset: int = 0) -> None:
+        """Per-episode car constants drawn on the device: ranges = {name: (lo, hi)} over ``_native.CAR_COLUMNS``.  Every
+        re-spawn of env i (reset, or an autoreset re-spawn inside step / step_multi) first draws the named columns of
+        its next episode -- ``randomization.draw_car_params(seed, env_offset + i, episode[i], ...)`` -- into its row of
+        ``env_car_params``; the other columns keep their values.  Installs per-env rows from the config when there are
+        none yet and zeroes the episode counters, so ``reset(seed=...)`` afterwards gives every env its episode-0 draw.
+        ``env_offset``: index of env 0 in a larger population (``distributed.shard_range``).  ranges None / {}: no more
+        resampling (the rows keep their last values)."""
+        from .randomization import car_ranges, config_row
+        lo, hi, mask = car_ranges(self.car_params, ranges)
+        if not 0 <= int(env_offset) < 2 ** 32:
+            raise ValueError("env_offset must be in [0, 2^32)")
+        if self._car_rows is None:
+            self._install_car_rows(torch.as_tensor(np.tile(config_row(self.car_params), (self.num_envs, 1))))
+        with torch.cuda.device(self.device):
+            if self._car_episode is None:
+                self._car_episode = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+            self._car_episode.zero_()
+            self._push_car_rand(lo, hi, mask, int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset))
+        self._car_rand = {"lo": lo, "hi": hi, "mask": mask, "seed": int(seed) & 0xFFFFFFFFFFFFFFFF,
+                          "env_offset": int(env_offset)}
+
+    def _push_car_rand(self, lo: np.ndarray, hi: np.ndarray, mask: int, seed: int, env_offset: int) -> None:
+        lo_c, hi_c = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+        nat.check(nat.lib().tc_env_set_car_randomization(
+            self._h, lo_c.ctypes.data_as(C.POINTER(C.c_double)), hi_c.ctypes.data_as(C.POINTER(C.c_double)), mask, seed,
+            env_offset, self._car_episode.data_ptr()), "tc_env_set_car_randomization")
+
+    @property
+    def car_episode(self) -> Optional[torch.Tensor]:
+        """[N] int32 device counter of the episodes each env has drawn since randomize_cars (None without it)."""
+        return self._car_episode
 
     # ------------------------------------------------------------------ fused reward / termination wrappers
     def set_terms(self, terms: Sequence[Term]) -> None:
@@ -628,7 +739,12 @@ class TinyCarloVecEnv(gym.Env):
                 "aux": {k: v.detach().cpu().clone() for k, v in self._aux.items()},
                 "term_counters": self.term_counters.detach().cpu().clone(),
                 "rng": [None if g is None else g.bit_generator.state for g in self._rngs],
-                "was_reset": self._was_reset}
+                "was_reset": self._was_reset,
+                # per-env cars: the rows in force, and the randomisation (ranges, mask, seed, offset, episode counters)
+                "car_per_env": None if self._car_rows is None else {
+                    "rows": self._car_rows.detach().cpu().clone(),
+                    "episode": None if self._car_episode is None else self._car_episode.detach().cpu().clone(),
+                    "randomization": None if self._car_rand is None else dict(self._car_rand)}}
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
         if int(sd["num_envs"]) != self.num_envs:
@@ -647,6 +763,22 @@ class TinyCarloVecEnv(gym.Env):
                 g.bit_generator.state = st
                 self._rngs[i] = g
         self._was_reset = bool(sd["was_reset"])
+        cpe = sd.get("car_per_env")
+        if cpe is None:
+            if self._car_rows is not None:
+                self._install_car_rows(None)
+        else:
+            rows = cpe["rows"]
+            if tuple(rows.shape) != (self.num_envs, nat.CAR_NP):
+                raise ValueError(f"car_per_env rows: shape {tuple(rows.shape)} does not fit ({self.num_envs}, {nat.CAR_NP})")
+            self._install_car_rows(rows)
+            rnd = cpe.get("randomization")
+            if rnd is not None:
+                self.randomize_cars(None)  # (allocates the counters)
+                with torch.cuda.device(self.device):
+                    self._car_episode.copy_(cpe["episode"])
+                    self._push_car_rand(rnd["lo"], rnd["hi"], rnd["mask"], rnd["seed"], rnd["env_offset"])
+                self._car_rand = dict(rnd)
         self._step_serial += 1
 
     def request_reset(self, mask: torch.Tensor) -> None:
