@@ -4,12 +4,16 @@
 controller reads cte / heading_error from the env's device tensors and writes the action tensor, the reference's
 wrappers (CTE sparse reward, CTE and crash termination) run inside the step kernel, finished envs re-spawn on the device.
 
-    python examples/stanley_batched.py [--envs 4096] [--steps 600] [--maneuver 3] [--randomize]
+    python examples/stanley_batched.py [--envs 4096] [--steps 600] [--maneuver 3] [--randomize] [--max-episode-steps N]
 
 --randomize: every episode of every env drives its own car, drawn on the device at the re-spawn (wheelbase, track width,
 speed and steering limits within +-20 %), plus the steering shift of the reference's TD3 study (examples/train_td3.py:37,
 146-147: STEERING_SHIFT = -0.01, here drawn per episode from [-0.01, 0]); the controller normalises its steering by each
 env's own max_steering_angle, read from the live per-env rows (vec.env_car_params).
+
+--max-episode-steps N: a controller that drives this well never ends an episode, so nothing would ever re-spawn (or draw
+a new car).  The time limit truncates every episode after N steps inside the step kernel (starts staggered over the
+envs); the episodes finished and their mean length / return are read from vec.episode_stats afterwards.
 """
 import argparse
 import math
@@ -25,7 +29,8 @@ from tinycarlo_amd.config import bundled_config  # noqa: E402
 from tinycarlo_amd.wrapper import CrashTerminationWrapper, CTESparseRewardWrapper, CTETerminationWrapper  # noqa: E402
 
 
-def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0", seed=2, randomize=False):
+def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0", seed=2, randomize=False,
+        max_episode_steps=None):
     vec = TinyCarloVecEnv(bundled_config("config_simple_layout.yaml"), num_envs=num_envs, device=device,
                           autoreset=True, spawn="device")
     if randomize:
@@ -34,7 +39,11 @@ def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0",
                             for name in ("wheelbase", "track_width", "max_velocity", "max_steering_angle")}
                            | {"steering_shift": (-0.01, 0.0)}, seed=seed)
     env = CrashTerminationWrapper(CTETerminationWrapper(CTESparseRewardWrapper(vec, 0.01), 0.07, number_of_steps=5))
+    if max_episode_steps:
+        vec.set_time_limit(max_episode_steps)
     obs, info = env.reset(seed=seed)
+    if max_episode_steps:  # staggered first episodes: the envs do not all reach the limit on the same step
+        vec.episode_stats["length"].copy_((torch.arange(num_envs, device=device) * max_episode_steps // num_envs).to(torch.int32))
     max_steer = math.radians(vec.car_params.max_steering_angle)
     cc = torch.zeros((num_envs, 2), dtype=torch.float64, device=device)
     cc[:, 0] = speed
@@ -60,6 +69,11 @@ def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0",
            "mean_reward_per_step": float(ret.mean()) / steps, "obs_shape": tuple(vec.out["obs"].shape)}
     if randomize:
         out["car_episodes_drawn"] = int(vec.car_episode.sum())
+    if max_episode_steps:
+        es = vec.episode_stats
+        n_ep = int(es["count"].sum())
+        out.update(episodes_finished=n_ep, mean_episode_length=float(es["length_sum"].sum()) / max(n_ep, 1),
+                   mean_episode_return=float(es["return_sum"].sum()) / max(n_ep, 1))
     vec.close()
     return out
 
@@ -70,5 +84,6 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=600)
     ap.add_argument("--maneuver", type=int, default=3)
     ap.add_argument("--randomize", action="store_true", help="per-episode car constants and steering shift")
+    ap.add_argument("--max-episode-steps", type=int, default=None, help="time limit per episode (kept by the step kernel)")
     a = ap.parse_args()
-    print(run(a.envs, a.steps, a.maneuver, randomize=a.randomize))
+    print(run(a.envs, a.steps, a.maneuver, randomize=a.randomize, max_episode_steps=a.max_episode_steps))

@@ -47,6 +47,9 @@ extern "C" {
 /* ABI 6: per-env car constants and their per-episode draw (tc_env_set_car, tc_env_set_car_per_env,
  * tc_env_set_car_randomization, TC_CAR_*) */
 #define TC_ABI_VERSION 6
+/* Additive within ABI 6 (new entry points only, no struct changed): tc_env_set_episodes, tc_env_set_episode_rollout,
+ * TC_S_TIME_LIMIT.  Callers that must run against an older ABI-6 library test for this macro / the symbols. */
+#define TC_HAS_EPISODES 1
 #define TC_MAX_LAYERS 16
 
 /* error codes */
@@ -84,6 +87,7 @@ extern "C" {
 #define TC_S_SPAWN_WRAPPED 16 /* TC_F_AUTORESET without TC_F_DEVICE_SPAWN: this re-spawn read spawn_queue past its end
                                  (cursor >= spawn_queue_len, the queue is consumed cyclically): from here on the env
                                  replays spawn nodes it already used -- refill the queue and clear spawn_cursor */
+#define TC_S_TIME_LIMIT 32   /* tc_env_set_episodes: the episode reached its time limit in this step: truncated */
 
 /* Reward / termination terms: the wrappers of tinycarlo/wrapper/reward.py and termination.py, evaluated in the
  * epilogue of the step kernel in the order given (= the order the wrappers are stacked, innermost first; reward
@@ -220,6 +224,42 @@ int tc_env_set_car_per_env(tc_env* env, double* params);
  * bound, a mask bit >= TC_CAR_NP or a bit for a column whose presence flag is 0. */
 int tc_env_set_car_randomization(tc_env* env, const double* lo, const double* hi, uint32_t column_mask, uint64_t seed,
                                  uint32_t env_offset, int32_t* episode);
+/* Episode time limit and per-env episode statistics, kept by the step kernels (gymnasium's TimeLimit and
+ * RecordEpisodeStatistics; `for ep_step in range(MAX_STEPS)` / `ep_rew += rew` of examples/train_td3.py:181,199).
+ * All members are DEVICE arrays of N, caller owned, read and written by every tc_reset / tc_step / tc_step_multi until
+ * replaced.  length and ret are required, the others may be NULL.  bufs = NULL switches the feature off (and drops the
+ * per-step rows below); without it nothing changes, and the kernels that do the accounting are separate instantiations
+ * chosen at launch (*_ep): the others are untouched.
+ * Per env i; limit_i = limit[i] when limit is given, else max_episode_steps; a value <= 0 means no limit:
+ *   1. (re)spawned by tc_reset (mask) or by a TC_F_AUTORESET re-spawn at the start of a step: length = 0, ret = 0.0.  The
+ *      re-spawn step itself counts nothing; count, last_* and *_sum are not touched.
+ *   2. any other step of an env that has been reset: length += 1; if limit_i > 0 and length >= limit_i: truncated = 1,
+ *      status |= TC_S_TIME_LIMIT, whatever `terminated` is.  Then ret = ret + reward with the step's final reward (after
+ *      the fused terms): one double add per step, in step order.
+ *   3. if terminated | truncated after that: last_length = length, last_return = ret, count += 1, length_sum += length,
+ *      return_sum += ret.  length and ret keep their values until the re-spawn (without TC_F_AUTORESET they go on counting).
+ *   4. a time-limit truncation is an ordinary truncation: under TC_F_AUTORESET it sets needs_reset, and the next step --
+ *      of the same K-step launch too -- re-spawns the env (spawn queue entry / device draw, new car with randomisation).
+ *   5. envs with TC_S_NOT_RESET are left alone.
+ * length is an ordinary in/out array: writing to it between calls staggers the episodes.
+ * max_episode_steps sits in a library-owned device word updated in place (a captured graph sees a new value without
+ * re-capture; the call waits for the device). */
+typedef struct {
+  int32_t* length;      /* [N] running episode: steps so far */
+  double* ret;          /* [N] running episode: sum of rewards so far */
+  int32_t* count;       /* [N] episodes finished */
+  int32_t* last_length; /* [N] most recent finished episode */
+  double* last_return;
+  int64_t* length_sum;  /* [N] over all finished episodes of env i */
+  double* return_sum;
+  const int32_t* limit; /* [N] per-env limit, or NULL */
+} tc_episode_buffers;
+int tc_env_set_episodes(tc_env* env, const tc_episode_buffers* bufs, int32_t max_episode_steps);
+/* Per-step rows of tc_step_multi calls: after step k of a call, length_rows[k][i] / return_rows[k][i] hold env i's
+ * length / ret (the episode's totals on a row where it ended, 0 / 0.0 on a re-spawn row).  [n_rows][N] each, device,
+ * caller owned, either may be NULL; (NULL, NULL, 0) removes them.  TC_E_INVALID for n_rows < 0, for rows without episode
+ * buffers, and from a tc_step_multi call of more than n_rows steps. */
+int tc_env_set_episode_rollout(tc_env* env, int32_t* length_rows, double* return_rows, int32_t n_rows);
 /* Installs n_terms (0..TC_MAX_TERMS) reward / termination terms; they apply to every tc_step enqueued afterwards
  * (the call waits for earlier launches).  Each term starts from the reward / terminated value left by the one
  * before it, the first from the base values of env.py:136-138 (0 / false under TC_F_WRAPPED, which the reference

@@ -1,0 +1,112 @@
+"""CPU checks of the episode time limit / statistics API: header, binding and library agree, the argument validation
+that needs no device, set_time_limit's input checks, and the compiler's resource figures of the *_ep kernels."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tinycarlo_amd import _native as nat
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = "/opt/rocm/bin/hipcc"
+NEW = ("tc_env_set_episodes", "tc_env_set_episode_rollout")
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "tinycarlo_hip.h")).read()
+
+
+def test_header_binding_and_library_agree():
+    h = _header()
+    d = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define (TC_\w+) (-?\d+)\s", h, re.M)}
+    assert d["TC_ABI_VERSION"] == nat.ABI_VERSION == 6  # additive: the ABI number does not move
+    assert d["TC_HAS_EPISODES"] == nat.HAS_EPISODES == 1
+    assert d["TC_S_TIME_LIMIT"] == nat.S_TIME_LIMIT == 32
+    others = [v for k, v in d.items() if k.startswith("TC_S_") and k != "TC_S_TIME_LIMIT"]
+    assert all(v & 32 == 0 for v in others) and max(others) == 16  # the next free status bit
+    L = nat.lib()
+    for f in NEW:
+        assert f in nat.EXPORTS and re.search(r"\bint " + f + r"\(", h) and hasattr(L, f)
+    assert L.tc_abi_version() == 6
+
+
+def test_struct_size_equals_the_headers_field_count():
+    h = _header()
+    body = re.search(r"typedef struct \{([^}]*)\} tc_episode_buffers;", h).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = [f for f in body.split(";") if f.strip()]
+    assert all("*" in f for f in fields)  # pointers only
+    assert len(fields) == len(nat.EpisodeBuffers._fields_) == 8
+    assert C.sizeof(nat.EpisodeBuffers) == 8 * len(fields)
+    names = [re.search(r"(\w+)\s*$", f).group(1) for f in fields]
+    assert names == [n for n, _ in nat.EpisodeBuffers._fields_]
+    # the structs out-of-tree callers were compiled against did not grow
+    assert C.sizeof(nat.Buffers) == 23 * 8 + 8 and C.sizeof(nat.Rollout) == 15 * 8
+
+
+def test_argument_validation_needs_no_device():
+    L = nat.lib()
+    assert L.tc_env_set_episodes(None, None, 0) == -1  # TC_E_INVALID
+    assert L.tc_env_set_episodes(None, None, 100) == -1
+    b = nat.EpisodeBuffers()  # length / ret missing: refused before the handle is looked at
+    assert L.tc_env_set_episodes(None, C.byref(b), 10) == -1
+    assert b"length and ret are required" in L.tc_last_error()
+    assert L.tc_env_set_episode_rollout(None, None, None, 0) == -1
+    assert L.tc_env_set_episode_rollout(None, None, None, -1) == -1
+    assert b"n_rows" in L.tc_last_error()
+
+
+def _host_env(n=4):
+    from oracle_backend import OracleVecEnv
+    from tinycarlo_amd.config import bundled_config
+    return OracleVecEnv(bundled_config("config_simple_layout.yaml"), num_envs=n)
+
+
+def test_set_time_limit_rejects_bad_input():
+    env = _host_env(4)
+    assert env.episode_stats is None
+    for bad in (-1, 2.5, "10", True):
+        with pytest.raises(ValueError):
+            env.set_time_limit(bad)
+    for bad in ([1, 2, 3], [1, 2, 3, -4], [1.0, 2.0, 3.0, 4.0], np.ones((2, 2), np.int32)):
+        with pytest.raises(ValueError):
+            env.set_time_limit(10, per_env=bad)
+    import torch
+    with pytest.raises(ValueError):
+        env.set_time_limit(None, per_env=torch.ones(4))
+    with pytest.raises(ValueError):
+        env.alloc_rollout(2, keys=("episode_length",))  # needs tracking
+    assert env.episode_stats is None  # nothing was switched on by a refused call
+    assert "episode_length" not in env.alloc_rollout(2, keys="all")
+    env.reset(seed=0)
+    _, _, _, _, info = env.step({"car_control": np.zeros((4, 2), np.float32), "maneuver": np.zeros(4, np.int32)})
+    assert "episode_length" not in info and "episode_return" not in info  # existing users' key set is unchanged
+    assert "episodes" in env.state_dict() and env.state_dict()["episodes"] is None
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_episode_kernels_keep_their_registers(tmp_path):
+    """the *_ep instantiations (cfg3's K = 5 variants): no VGPR spill, no scratch, at most 128 VGPRs (4 waves / SIMD)"""
+    out = tmp_path / "tc.s"
+    cmd = [HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-mllvm", "-disable-machine-licm", "-std=c++17",
+           "-DTC_DEV_FAST", "-S", "--cuda-device-only", "-o", str(out),
+           os.path.join(ROOT, "tinycarlo_amd", "csrc", "tinycarlo_hip.hip")]
+    subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL, timeout=600)
+    s = out.read_text()
+    seen = {}
+    for b in s.split("  - .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", b).group(1)
+        g = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", b).group(1))  # noqa: E731
+        seen[name] = (g("vgpr_count"), g("vgpr_spill_count"), g("private_segment_fixed_size"))
+    ep = [n for n in seen if re.search(r"tc_(step|envg|env)_kernel_ep", n)]
+    # tc_step_kernel_ep / _ep_car <5,...>, tc_env_kernel_ep / _ep_car <5, true|false>, tc_envg_kernel_ep / _ep_car
+    assert len(ep) == 8, sorted(seen)
+    assert len([n for n in ep if "_ep_car" in n]) == 4
+    assert not [n for n in ep if re.search(r"tc_(step|envg|env)_kernel_car", n)]  # the car test counts exactly four of those
+    for n in ep:
+        vgpr, spill, scratch = seen[n]
+        assert spill == 0 and scratch == 0, (n, "spills VGPRs / uses scratch", seen[n])
+        assert vgpr <= 128, (n, "more than 128 VGPRs", vgpr)

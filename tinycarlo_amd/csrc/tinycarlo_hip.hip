@@ -235,9 +235,12 @@ struct LiveLds {
   int needs_reset;  // TC_F_AUTORESET: re-spawn at the start of the next step
   int cursor;       // spawn_cursor: re-spawns of this env so far
   int cursor0;      // its value in the caller's buffer (stored back only when it changed)
-  int trunc, status, terminated, pad[3];
+  int trunc, status, terminated;
+  int ep_len;  // running episode's length (tc_env_set_episodes; touched by the *_ep kernels only)
+  int pad[2];
   int cnt[TC_MAX_TERMS];  // steps_true of the consecutive-step terms
   int ne[TC_MAX_LAYERS];
+  double ep_ret;  // running episode's return (likewise)
 };
 #define TC_LIVE_BYTES 416
 static_assert(sizeof(LiveLds) <= TC_LIVE_BYTES, "LiveLds must fit its LDS slot");
@@ -374,6 +377,66 @@ __device__ __forceinline__ void car_respawn(const CarRows& cr, int env, bool wri
       if (writer) row[j] = v;
     }
   if (writer) cr.episode[env] = ep + 1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Episode time limit and per-env episode statistics (tc_env_set_episodes).  Only the *_ep kernels (the EP instantiations
+// of the simulate stages, chosen at launch) touch any of this: every other kernel compiles as before.  Per env and step:
+//   re-spawned in this step (tc_reset, autoreset)  length = 0, ret = 0.0, nothing else
+//   TC_S_NOT_RESET                                 left alone
+//   else  length += 1; limit > 0 && length >= limit: truncated = 1, status |= TC_S_TIME_LIMIT   (ep_count, every lane)
+//         ret = ret + reward, with the step's FINAL reward: one double add per step, in step order
+//         terminated | truncated: last_* = (length, ret), count += 1, *_sum += (length, ret)   (ep_close, one lane)
+// length / ret stay on chip across the steps of a launch (LiveLds, or registers in the grouped kernel) and go back to the
+// caller's buffers once; the finished-episode statistics are rare and go straight to memory.
+struct EpArgs {
+  int* length;           // [N] caller owned, as are the next seven
+  double* ret;
+  int* count;            // (count .. return_sum: each may be NULL)
+  int* last_length;
+  double* last_return;
+  long long* length_sum;
+  double* return_sum;
+  const int* limit;      // [N] per-env limit, or NULL: *shared
+  const int* shared;     // library owned, updated in place by tc_env_set_episodes (a captured graph sees a new limit)
+  int* len_rows;         // [K][N] rows of a K-step call (tc_env_set_episode_rollout), first row of this launch; or NULL
+  double* ret_rows;
+};
+typedef const __attribute__((address_space(4))) int* EpIntConst;  // never written by a kernel: scalar load
+// first half, before truncated / status are stored: the length, and the time limit (gymnasium TimeLimit: whatever
+// `terminated` turns out to be).  Every lane that works on the env runs it, so truncated stays uniform among them.
+template <bool UNI>
+__device__ __forceinline__ void ep_count(const EpArgs& ep, int env, bool fresh, int& len, int& trunc, int& status) {
+  if (fresh) {
+    len = 0;
+    return;
+  }
+  if (status & TC_S_NOT_RESET) return;
+  len += 1;
+  const int lim = ep.limit ? (UNI ? uni_i(ep.limit[env]) : ep.limit[env]) : *(EpIntConst)(unsigned long long)ep.shared;
+  if (lim > 0 && len >= lim) {
+    trunc = 1;
+    status |= TC_S_TIME_LIMIT;
+  }
+}
+// second half, by the one lane that stores the env's outputs, once reward / terminated are final; row: (step, env) of
+// the launch's per-step rows
+__device__ __forceinline__ void ep_close(const EpArgs& ep, int env, size_t row, bool fresh, int status, int len, double& ret,
+                                         double reward, int done) {
+  if (fresh) {
+    ret = 0.0;
+  } else if (!(status & TC_S_NOT_RESET)) {
+    ret = ret + reward;
+    if (done) {
+      if (ep.last_length) ep.last_length[env] = len;
+      if (ep.last_return) ep.last_return[env] = ret;
+      if (ep.count) ep.count[env] += 1;
+      if (ep.length_sum) ep.length_sum[env] += (long long)len;
+      if (ep.return_sum) ep.return_sum[env] = ep.return_sum[env] + ret;
+    }
+  }
+  if (ep.len_rows) ep.len_rows[row] = len;
+  if (ep.ret_rows) ep.ret_rows[row] = ret;
 }
 
 // (scalars by value: a reference to the kernel-argument struct would force a copy of it into scratch)
@@ -951,6 +1014,23 @@ __device__ __forceinline__ void live_out(const KArgs& a, unsigned char* smem, in
   }
 }
 
+// The running episode of an env: caller's buffers -> LiveLds before live_in (whose barrier covers it), and back after
+// live_out, by one lane that live_in / live_out leave idle.
+__device__ __forceinline__ void ep_in(const KArgs& a, const EpArgs& ep, unsigned char* smem, int env, const int tid = threadIdx.x) {
+  LiveLds* lv = (LiveLds*)(smem + a.lds.off_live);
+  if (tid == 50) {
+    lv->ep_len = ep.length[env];
+    lv->ep_ret = ep.ret[env];
+  }
+}
+__device__ __forceinline__ void ep_out(const KArgs& a, const EpArgs& ep, unsigned char* smem, int env, const int tid = threadIdx.x) {
+  const LiveLds* lv = (const LiveLds*)(smem + a.lds.off_live);
+  if (tid == 50) {
+    ep.length[env] = lv->ep_len;
+    ep.ret[env] = lv->ep_ret;
+  }
+}
+
 #ifndef TC_MIN_WAVES
 #define TC_MIN_WAVES 4
 #endif
@@ -965,12 +1045,13 @@ struct FramePose {
 };
 
 // PER: the env's car constants come from its row of cr.rows (per-env cars, tc_env_set_car_per_env), else a.car.
-template <int K, bool PER = false>
+// EP: episode length / return / time limit (tc_env_set_episodes); the running pair lives in LiveLds (ep_len, ep_ret).
+template <int K, bool PER = false, bool EP = false>
 __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, int env, int mode,
                                 const void* car_control, int cdtype,
                                 const int* maneuver, const int* spawn_nodes, const unsigned char* mask,
                                 unsigned int flags, const RollStep& roll, const int tid, MapCache<K>& mc, FramePose& fp,
-                                const CarRows& cr = CarRows()) {
+                                const CarRows& cr = CarRows(), const EpArgs& ep = EpArgs()) {
 
   TSTAMP(0);
   TSTAMP_REAL(30);
@@ -1004,6 +1085,7 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
   const int nr = uni_i(lv->needs_reset);
   int cursor = uni_i(lv->cursor);
   int my_cnt = tid < TC_MAX_TERMS ? lv->cnt[tid] : 0;  // lane t: steps_true of term slot t
+  int ep_len = EP ? uni_i(lv->ep_len) : 0;
 
   int status = 0, trunc = 0;
   PathInfo pinfo;
@@ -1081,6 +1163,7 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
       terminated = cte > (tw * 10);
     }
     const bool late = a.n_terms > 0;  // reward / terminated depend on phase B: written after it
+    if (EP) ep_count<true>(ep, env, fresh, ep_len, trunc, status);  // (the time limit: before trunc / status are stored)
     if (tid == 0) {
       lv->d[0] = s.x;
       lv->d[1] = s.y;
@@ -1109,12 +1192,14 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
       if (roll.theta) roll.theta[roll.row0 + env] = s.theta;
       if (roll.velocity) roll.velocity[roll.row0 + env] = s.velocity;
       if (roll.lp_len) roll.lp_len[roll.row0 + env] = s.lp_len;
+      if (EP) lv->ep_len = ep_len;
       if (!late) {
         lv->reward = reward;
         lv->terminated = terminated;
         lv->needs_reset = (flags & TC_F_AUTORESET) ? (terminated || trunc) : 0;
         if (roll.reward) roll.reward[roll.row0 + env] = reward;
         if (roll.terminated) roll.terminated[roll.row0 + env] = (unsigned char)terminated;
+        if (EP) ep_close(ep, env, roll.row0 + env, fresh, status, ep_len, lv->ep_ret, reward, terminated | trunc);
       }
     }
     if (tid < 8) {  // register-resident select (a runtime-indexed s.lp[tid] would live in scratch)
@@ -1268,6 +1353,7 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
         lv->needs_reset = (flags & TC_F_AUTORESET) ? (terminated || trunc) : 0;
         if (roll.reward) roll.reward[roll.row0 + env] = reward;
         if (roll.terminated) roll.terminated[roll.row0 + env] = (unsigned char)terminated;
+        if (EP) ep_close(ep, env, roll.row0 + env, fresh, status, ep_len, lv->ep_ret, reward, terminated | trunc);
       }
     }
   }
@@ -2341,6 +2427,7 @@ struct StepArgs {
   const unsigned char* mask;
   const int* env_order;  // tc_step_kernel: workgroup w works on env env_order[w] (a permutation of 0..N-1), or NULL = env w
   CarRows cr;            // per-env cars: read by the *_car kernels only (last, so every other member keeps its offset)
+  EpArgs ep;             // episodes: read by the *_ep kernels only (behind it, for the same reason)
 };
 
 // The launch arguments, read through a pointer the optimiser cannot see through.  Inside the step loop of tc_step_multi
@@ -2372,7 +2459,7 @@ __device__ __forceinline__ bool wants_frame(const StepArgs& sa) {
 // What becomes of the frames is the launch's choice: nothing (no observation), the camera stage here and a raster
 // launch behind (cam_here; maps of the K = 13 variant, TC_FUSE=0), or -- the K-step default -- only the poses, from which
 // tc_frame_kernel produces every (step, env) frame as a workgroup of its own.
-template <int K, bool CAM, bool PER>
+template <int K, bool CAM, bool PER, bool EP>
 __device__ __forceinline__ void env_kernel_body() {
   extern __shared__ __align__(16) unsigned char smem[];
   // Touching v127 makes the kernel descriptor ask for 128 VGPRs, i.e. caps the SIMD at the 4 wavefronts the launch
@@ -2385,6 +2472,7 @@ __device__ __forceinline__ void env_kernel_body() {
   const int env = s0.a.env0 + blockIdx.x;
   if (env >= s0.a.N) return;
   if (s0.mode == MODE_RESET && s0.mask && !s0.mask[env]) return;  // whole workgroup skips
+  if (EP) ep_in(s0.a, s0.ep, smem, env);
   live_in(s0.a, smem, env, s0.mode, s0.flags);
   const int nsteps = s0.ma.nsteps;
   long long t_prev = 0;
@@ -2413,8 +2501,8 @@ __device__ __forceinline__ void env_kernel_body() {
     MapCache<K> mc = {};  // (initialised: a path that leaves it unset would otherwise make it a loop-carried value -- 30
                           // registers per lane held across the whole step body, raster stage included)
     FramePose fp;
-    sim_body<K, PER>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
-                     sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr);
+    sim_body<K, PER, EP>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
+                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr, sa.ep);
     if (sa.ma.pose_rows) {
       double pose[12];
       cam_pose12(sa.a, env, fp, pose);
@@ -2439,16 +2527,28 @@ __device__ __forceinline__ void env_kernel_body() {
   }
   TSTAMP_END(t_prev);
   const StepArgs& s1 = step_args();
-  if (s1.mode != MODE_RENDER) live_out(s1.a, smem, env);
+  if (s1.mode != MODE_RENDER) {
+    live_out(s1.a, smem, env);
+    if (EP) ep_out(s1.a, s1.ep, smem, env);
+  }
 }
 template <int K, bool CAM>
 __global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) void tc_env_kernel(StepArgs sa_unused) {
-  env_kernel_body<K, CAM, false>();
+  env_kernel_body<K, CAM, false, false>();
 }
 // the same with per-env car constants (StepArgs::cr)
 template <int K, bool CAM>
 __global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) void tc_env_kernel_car(StepArgs sa_unused) {
-  env_kernel_body<K, CAM, true>();
+  env_kernel_body<K, CAM, true, false>();
+}
+// the two with the episode accounting (StepArgs::ep)
+template <int K, bool CAM>
+__global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) void tc_env_kernel_ep(StepArgs sa_unused) {
+  env_kernel_body<K, CAM, false, true>();
+}
+template <int K, bool CAM>
+__global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) void tc_env_kernel_ep_car(StepArgs sa_unused) {
+  env_kernel_body<K, CAM, true, true>();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2481,7 +2581,7 @@ struct GroupLds {  // per env of the wavefront: what the reward / termination te
 // kernel with its stores switched off).  The edge scan is ~33 loads per lane and step: from LDS it neither waits for
 // the stores nor pays an L2 round trip per batch of loads.
 typedef const __attribute__((address_space(3))) double* LdsDouble;
-template <bool PER>
+template <bool PER, bool EP>
 __device__ __forceinline__ void envg_kernel_body() {
   __shared__ GroupLds glds[TC_ENVG_NT / TC_EL];
   extern __shared__ __align__(16) unsigned char gsm[];
@@ -2550,6 +2650,16 @@ __device__ __forceinline__ void envg_kernel_body() {
     }
     if (sub < TC_MAX_TERMS) gl.cnt[sub] = (s0.a.n_terms > 0 && s0.a.term_counters) ? s0.a.term_counters[(size_t)env * TC_MAX_TERMS + sub] : 0;
     static_assert(TC_EL >= TC_MAX_TERMS, "one lane per term counter");
+  }
+  // the running episode (EP) waits in LDS between its two uses per step (three registers per lane across the whole step
+  // took the kernel from 125 to 129 VGPRs): the length is read and rewritten by every lane of the group with the same
+  // value (the time limit decides `truncated`, which all of them branch on), the return by the lane that stores the
+  // env's outputs
+  __shared__ int g_ep_len[EP ? TC_ENVG_NT / TC_EL : 1];
+  __shared__ double g_ep_ret[EP ? TC_ENVG_NT / TC_EL : 1];
+  if (EP) {
+    g_ep_len[grp] = s0.ep.length[env];
+    if (sub == 0) g_ep_ret[grp] = s0.ep.ret[env];
   }
   double cte = 0, he = 0, reward = 0;
   int terminated = 0, trunc = 0, status = 0;
@@ -2810,9 +2920,16 @@ __device__ __forceinline__ void envg_kernel_body() {
       d_apply_terms_mem(a.terms, a.n_terms, gl.cnt,
                         PER ? car_ld<false>(sa.cr.rows + (size_t)env * TC_CAR_NP, TC_CAR_TRACK_WIDTH) : a.car.track_width, C,
                         cte, have_info ? s.velocity : 0.0, gl.dist, reward, terminated);
+    int ep_len = 0;
+    if (EP) {
+      ep_len = g_ep_len[grp];
+      ep_count<false>(sa.ep, env, fresh, ep_len, trunc, status);
+      g_ep_len[grp] = ep_len;
+    }
     nr = (flags & TC_F_AUTORESET) ? (terminated || trunc) : 0;
     // ---- this step's rollout rows and pose row
     if (live && sub == 0) {
+      if (EP) ep_close(sa.ep, env, row0 + env, fresh, status, ep_len, g_ep_ret[grp], reward, terminated | trunc);
       if (roll.cte) roll.cte[roll.row0 + env] = cte;
       if (roll.heading_error) roll.heading_error[roll.row0 + env] = he;
       if (roll.truncated) roll.truncated[roll.row0 + env] = (unsigned char)trunc;
@@ -2856,12 +2973,20 @@ __device__ __forceinline__ void envg_kernel_body() {
     b.status[env] = status;
     if (b.needs_reset) b.needs_reset[env] = (unsigned char)nr;
     if (cursor != cursor0) b.spawn_cursor[env] = cursor;
+    if (EP) {
+      s1.ep.length[env] = g_ep_len[grp];
+      s1.ep.ret[env] = g_ep_ret[grp];
+    }
   }
   if (live && s1.a.term_counters && sub < s1.a.n_terms) s1.a.term_counters[(size_t)env * TC_MAX_TERMS + sub] = gl.cnt[sub];
 }
-__global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel(StepArgs sa_unused) { envg_kernel_body<false>(); }
+__global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel(StepArgs sa_unused) { envg_kernel_body<false, false>(); }
 // the same with per-env car constants (StepArgs::cr)
-__global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel_car(StepArgs sa_unused) { envg_kernel_body<true>(); }
+__global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel_car(StepArgs sa_unused) { envg_kernel_body<true, false>(); }
+// the two with the episode accounting (StepArgs::ep).  (4 wavefronts per SIMD asked for: left to itself the allocator
+// takes 129 / 131 VGPRs here, whatever the episode state is kept in; held to the 128 of the other two it spills nothing)
+__global__ __launch_bounds__(TC_ENVG_NT, 4) void tc_envg_kernel_ep(StepArgs sa_unused) { envg_kernel_body<false, true>(); }
+__global__ __launch_bounds__(TC_ENVG_NT, 4) void tc_envg_kernel_ep_car(StepArgs sa_unused) { envg_kernel_body<true, true>(); }
 
 // One (step, env) frame per workgroup: camera stage from the pose the simulate launch left, then the raster stage.
 // Frames do not depend on each other, a launch has steps x N of them -- many more than the chip holds at once -- and
@@ -3031,7 +3156,7 @@ __global__ __launch_bounds__(TC_NT) void tc_frame_recover_kernel(FrameArgs fa_un
 // All stages in one launch: the same wavefront simulates its env, runs the camera and rasterises the frame.  The form
 // of tc_step / tc_reset / tc_render (one step: nothing to balance, and one kernel boundary less), and of tc_step_multi
 // under TC_MULTI_SPLIT=0.
-template <int K, bool THICK, int FMT, int RBT, bool PER>
+template <int K, bool THICK, int FMT, int RBT, bool PER, bool EP>
 __device__ __forceinline__ void step_kernel_body() {
   extern __shared__ __align__(16) unsigned char smem[];
   const StepArgs& s0 = step_args();
@@ -3040,6 +3165,7 @@ __device__ __forceinline__ void step_kernel_body() {
   const int env = s0.env_order ? uni_i(((const __attribute__((address_space(4))) int*)(unsigned long long)s0.env_order)[blockIdx.x])
                                : s0.a.env0 + (int)blockIdx.x;
   if (s0.mode == MODE_RESET && s0.mask && !s0.mask[env]) return;  // whole workgroup skips
+  if (EP) ep_in(s0.a, s0.ep, smem, env);
   live_in(s0.a, smem, env, s0.mode, s0.flags);
   const int nsteps = s0.ma.nsteps;
   long long t_prev = 0;
@@ -3056,8 +3182,8 @@ __device__ __forceinline__ void step_kernel_body() {
     MapCache<K> mc = {};  // (initialised: a path that leaves it unset would otherwise make it a loop-carried value -- 30
                           // registers per lane held across the whole step body, raster stage included)
     FramePose fp;
-    sim_body<K, PER>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
-                     sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr);
+    sim_body<K, PER, EP>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
+                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr, sa.ep);
     if (wants_frame(sa)) {
       int nseg;
       unsigned int used;
@@ -3079,16 +3205,28 @@ __device__ __forceinline__ void step_kernel_body() {
   }
   TSTAMP_END(t_prev);
   const StepArgs& s1 = step_args();
-  if (s1.mode != MODE_RENDER) live_out(s1.a, smem, env);
+  if (s1.mode != MODE_RENDER) {
+    live_out(s1.a, smem, env);
+    if (EP) ep_out(s1.a, s1.ep, smem, env);
+  }
 }
 template <int K, bool THICK, int FMT, int RBT = RB_OF_K(K)>
 __global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_kernel(StepArgs sa_unused) {
-  step_kernel_body<K, THICK, FMT, RBT, false>();
+  step_kernel_body<K, THICK, FMT, RBT, false, false>();
 }
 // the same with per-env car constants (StepArgs::cr)
 template <int K, bool THICK, int FMT, int RBT = RB_OF_K(K)>
 __global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_kernel_car(StepArgs sa_unused) {
-  step_kernel_body<K, THICK, FMT, RBT, true>();
+  step_kernel_body<K, THICK, FMT, RBT, true, false>();
+}
+// the two with the episode accounting (StepArgs::ep)
+template <int K, bool THICK, int FMT, int RBT = RB_OF_K(K)>
+__global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_kernel_ep(StepArgs sa_unused) {
+  step_kernel_body<K, THICK, FMT, RBT, false, true>();
+}
+template <int K, bool THICK, int FMT, int RBT = RB_OF_K(K)>
+__global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_kernel_ep_car(StepArgs sa_unused) {
+  step_kernel_body<K, THICK, FMT, RBT, true, true>();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3171,10 +3309,17 @@ typedef void (*fused_kern_t)(StepArgs);
 #define TC_DEV_SRB RB_OF_K(TC_DEV_SK)
 #endif
 template <int K, int RBT = RB_OF_K(K)>
-static fused_kern_t pick_fused(bool thick, bool cls, bool per = false) {
+static fused_kern_t pick_fused(bool thick, bool cls, bool per = false, bool ep = false) {
 #ifdef TC_DEV_FAST
+  if (ep) return per ? tc_step_kernel_ep_car<TC_DEV_SK, true, TC_DEV_FMTV, TC_DEV_SRB> : tc_step_kernel_ep<TC_DEV_SK, true, TC_DEV_FMTV, TC_DEV_SRB>;
   return per ? tc_step_kernel_car<TC_DEV_SK, true, TC_DEV_FMTV, TC_DEV_SRB> : tc_step_kernel<TC_DEV_SK, true, TC_DEV_FMTV, TC_DEV_SRB>;
 #else
+  if (ep && per)
+    return thick ? (cls ? tc_step_kernel_ep_car<K, true, TC_FMT_CLASSES, RBT> : tc_step_kernel_ep_car<K, true, TC_FMT_RGB, RBT>)
+                 : (cls ? tc_step_kernel_ep_car<K, false, TC_FMT_CLASSES, RBT> : tc_step_kernel_ep_car<K, false, TC_FMT_RGB, RBT>);
+  if (ep)
+    return thick ? (cls ? tc_step_kernel_ep<K, true, TC_FMT_CLASSES, RBT> : tc_step_kernel_ep<K, true, TC_FMT_RGB, RBT>)
+                 : (cls ? tc_step_kernel_ep<K, false, TC_FMT_CLASSES, RBT> : tc_step_kernel_ep<K, false, TC_FMT_RGB, RBT>);
   if (per)
     return thick ? (cls ? tc_step_kernel_car<K, true, TC_FMT_CLASSES, RBT> : tc_step_kernel_car<K, true, TC_FMT_RGB, RBT>)
                  : (cls ? tc_step_kernel_car<K, false, TC_FMT_CLASSES, RBT> : tc_step_kernel_car<K, false, TC_FMT_RGB, RBT>);
@@ -3182,14 +3327,26 @@ static fused_kern_t pick_fused(bool thick, bool cls, bool per = false) {
                : (cls ? tc_step_kernel<K, false, TC_FMT_CLASSES, RBT> : tc_step_kernel<K, false, TC_FMT_RGB, RBT>);
 #endif
 }
-// simulate stage alone (tc_env_kernel), by register-cache variant; per: the per-env-car instantiation
+// simulate stage alone (tc_env_kernel), by register-cache variant; per: the per-env-car instantiation; ep: the one with
+// the episode accounting
 typedef void (*env_kern_t)(StepArgs);
-static env_kern_t pick_env(int kv, bool cam, bool per) {
+static env_kern_t pick_env(int kv, bool cam, bool per, bool ep = false) {
 #ifdef TC_DEV_FAST
   (void)kv;
+  if (ep)
+    return per ? (cam ? tc_env_kernel_ep_car<TC_DEV_KV, true> : tc_env_kernel_ep_car<TC_DEV_KV, false>)
+               : (cam ? tc_env_kernel_ep<TC_DEV_KV, true> : tc_env_kernel_ep<TC_DEV_KV, false>);
   return per ? (cam ? tc_env_kernel_car<TC_DEV_KV, true> : tc_env_kernel_car<TC_DEV_KV, false>)
              : (cam ? tc_env_kernel<TC_DEV_KV, true> : tc_env_kernel<TC_DEV_KV, false>);
 #else
+  if (ep && per) {
+    if (cam) return kv == 5 ? tc_env_kernel_ep_car<5, true> : kv == 8 ? tc_env_kernel_ep_car<8, true> : kv == 9 ? tc_env_kernel_ep_car<9, true> : tc_env_kernel_ep_car<13, true>;
+    return kv == 5 ? tc_env_kernel_ep_car<5, false> : kv == 8 ? tc_env_kernel_ep_car<8, false> : kv == 9 ? tc_env_kernel_ep_car<9, false> : tc_env_kernel_ep_car<13, false>;
+  }
+  if (ep) {
+    if (cam) return kv == 5 ? tc_env_kernel_ep<5, true> : kv == 8 ? tc_env_kernel_ep<8, true> : kv == 9 ? tc_env_kernel_ep<9, true> : tc_env_kernel_ep<13, true>;
+    return kv == 5 ? tc_env_kernel_ep<5, false> : kv == 8 ? tc_env_kernel_ep<8, false> : kv == 9 ? tc_env_kernel_ep<9, false> : tc_env_kernel_ep<13, false>;
+  }
   if (per) {
     if (cam) return kv == 5 ? tc_env_kernel_car<5, true> : kv == 8 ? tc_env_kernel_car<8, true> : kv == 9 ? tc_env_kernel_car<9, true> : tc_env_kernel_car<13, true>;
     return kv == 5 ? tc_env_kernel_car<5, false> : kv == 8 ? tc_env_kernel_car<8, false> : kv == 9 ? tc_env_kernel_car<9, false> : tc_env_kernel_car<13, false>;
@@ -3263,6 +3420,9 @@ struct tc_env {
   KArgs k;
   CarRows cr;            // per-env cars (tc_env_set_car_per_env / tc_env_set_car_randomization); rows NULL = shared car
   CarDrawTab* car_tab;   // device copy of the randomisation ranges (library owned, updated in place), or NULL
+  EpArgs ep;             // episodes (tc_env_set_episodes / tc_env_set_episode_rollout); length NULL = feature off
+  int* ep_tab;           // device word holding max_episode_steps (library owned, updated in place), or NULL
+  int ep_rows;           // rows of ep.len_rows / ep.ret_rows
   bool bound;
   int64_t obs_bytes;
   int r_off_tab, r_off_bits, r_lds;
@@ -3966,10 +4126,12 @@ extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const 
     if (lds > 48 * 1024) {
       for (int t = 0; t < 2; t++)
         for (int c = 0; c < 4; c++) {  // (c & 2: the per-env-car instantiation)
-          (void)hipFuncSetAttribute((const void*)pick_fused<5>(t, c & 1, c & 2), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-          (void)hipFuncSetAttribute((const void*)pick_fused<5, 16>(t, c & 1, c & 2), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-          (void)hipFuncSetAttribute((const void*)pick_fused<8>(t, c & 1, c & 2), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-          (void)hipFuncSetAttribute((const void*)pick_fused<9>(t, c & 1, c & 2), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+          for (int ep = 0; ep < 2; ep++) {  // (and the ones with the episode accounting)
+            (void)hipFuncSetAttribute((const void*)pick_fused<5>(t, c & 1, c & 2, ep), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            (void)hipFuncSetAttribute((const void*)pick_fused<5, 16>(t, c & 1, c & 2, ep), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            (void)hipFuncSetAttribute((const void*)pick_fused<8>(t, c & 1, c & 2, ep), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            (void)hipFuncSetAttribute((const void*)pick_fused<9>(t, c & 1, c & 2, ep), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+          }
           (void)hipFuncSetAttribute((const void*)pick_frame<5>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
           (void)hipFuncSetAttribute((const void*)pick_frame<5, 16>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
           (void)hipFuncSetAttribute((const void*)pick_frame<8>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -3980,7 +4142,8 @@ extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const 
   {  // tc_envg_kernel's LDS copies of the map (edge records + fat lanepath nodes, see launch()) can exceed the 48 KB default
     const size_t envg_lds = ((size_t)m.total_edges * 48 + 15) / 16 * 16 + (size_t)m.lpN * sizeof(LpNode);
     if (envg_lds > 40 * 1024)
-      for (const void* g : {(const void*)tc_envg_kernel, (const void*)tc_envg_kernel_car})
+      for (const void* g : {(const void*)tc_envg_kernel, (const void*)tc_envg_kernel_car, (const void*)tc_envg_kernel_ep,
+                            (const void*)tc_envg_kernel_ep_car})
         (void)hipFuncSetAttribute(g, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(envg_lds < 150 * 1024 ? envg_lds : 150 * 1024));
   }
 #ifndef TC_DEV_FAST
@@ -3993,8 +4156,8 @@ extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const 
   if (L.total > 48 * 1024) {
     hipError_t he = hipSuccess;
     static const int kvs[4] = {5, 8, 9, 13};
-    for (int i = 0; i < 16 && he == hipSuccess; i++)  // every tc_env_kernel / tc_env_kernel_car variant
-      he = hipFuncSetAttribute((const void*)pick_env(kvs[i & 3], (i & 4) == 0, (i & 8) != 0),
+    for (int i = 0; i < 32 && he == hipSuccess; i++)  // every tc_env_kernel / _car / _ep / _ep_car variant
+      he = hipFuncSetAttribute((const void*)pick_env(kvs[i & 3], (i & 4) == 0, (i & 8) != 0, (i & 16) != 0),
                                hipFuncAttributeMaxDynamicSharedMemorySize, L.total);
     if (he != hipSuccess) {
       set_err(std::string("hipFuncSetAttribute: ") + hipGetErrorString(he));
@@ -4125,6 +4288,7 @@ extern "C" int tc_env_destroy(tc_env* e) {
   if (e && e->k.spawn_tab) (void)hipFree((void*)e->k.spawn_tab);
   if (e && e->noise_hw) (void)hipFree(e->noise_hw);
   if (e && e->car_tab) (void)hipFree(e->car_tab);
+  if (e && e->ep_tab) (void)hipFree(e->ep_tab);
   if (e && e->noise_step) (void)hipFree(e->noise_step);
   delete e;
   return TC_OK;
@@ -4228,6 +4392,61 @@ extern "C" int tc_env_set_car_randomization(tc_env* e, const double* lo, const d
   HIP_TRY(hipMemcpy(e->car_tab, &t, sizeof(t), hipMemcpyHostToDevice));
   e->cr.tab = e->car_tab;
   e->cr.episode = column_mask ? episode : e->cr.episode;
+  return TC_OK;
+}
+
+extern "C" int tc_env_set_episodes(tc_env* e, const tc_episode_buffers* bufs, int32_t max_episode_steps) {
+  if (bufs && (!bufs->length || !bufs->ret)) {
+    set_err("tc_env_set_episodes: length and ret are required");
+    return TC_E_INVALID;
+  }
+  if (!e) return TC_E_INVALID;
+  if (!bufs) {  // feature off: the per-step rows go with it
+    const int* tab = e->ep_tab;
+    memset(&e->ep, 0, sizeof(e->ep));
+    e->ep.shared = tab;
+    e->ep_rows = 0;
+    return TC_OK;
+  }
+  if (!e->ep_tab) {
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, sizeof(int)));
+    e->ep_tab = (int*)p;
+  }
+  // (in place: a graph captured earlier keeps reading this word; the copy waits for launches that may still read it)
+  const int lim = max_episode_steps > 0 ? max_episode_steps : 0;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(e->ep_tab, &lim, sizeof(lim), hipMemcpyHostToDevice));
+  e->ep.length = bufs->length;
+  e->ep.ret = bufs->ret;
+  e->ep.count = bufs->count;
+  e->ep.last_length = bufs->last_length;
+  e->ep.last_return = bufs->last_return;
+  e->ep.length_sum = (long long*)bufs->length_sum;
+  e->ep.return_sum = bufs->return_sum;
+  e->ep.limit = bufs->limit;
+  e->ep.shared = e->ep_tab;
+  return TC_OK;
+}
+
+extern "C" int tc_env_set_episode_rollout(tc_env* e, int32_t* length_rows, double* return_rows, int32_t n_rows) {
+  if (n_rows < 0) {
+    set_err("tc_env_set_episode_rollout: n_rows must not be negative");
+    return TC_E_INVALID;
+  }
+  if (!e) return TC_E_INVALID;
+  const bool any = length_rows || return_rows;
+  if (any && !e->ep.length) {
+    set_err("tc_env_set_episode_rollout: no episode buffers installed (tc_env_set_episodes)");
+    return TC_E_INVALID;
+  }
+  if (any && n_rows < 1) {
+    set_err("tc_env_set_episode_rollout: rows given with n_rows = 0");
+    return TC_E_INVALID;
+  }
+  e->ep.len_rows = length_rows;
+  e->ep.ret_rows = return_rows;
+  e->ep_rows = any ? n_rows : 0;
   return TC_OK;
 }
 
@@ -4641,7 +4860,8 @@ extern "C" int tc_env_reserve_steps(tc_env* e, int32_t max_call_steps) {
 }
 
 static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t* man, const int32_t* spawn,
-                  const uint8_t* mask, uint32_t flags, void* stream, int nsteps = 1, const tc_rollout* roll = nullptr) {
+                  const uint8_t* mask, uint32_t flags, void* stream, int nsteps = 1, const tc_rollout* roll = nullptr,
+                  bool ep_rows = false) {
   if (!e) return TC_E_INVALID;
   if (!e->bound) {
     set_err("tc_env_bind has not been called");
@@ -4667,9 +4887,19 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
   // simulate stage alone, with or without the camera stage compiled in (without: fewer registers, half the code)
   // per-env cars (tc_env_set_car_per_env): the *_car instantiations of the simulate stages, the same launches otherwise
   const bool per = e->cr.rows != nullptr;
-  auto kern = pick_env(kv, true, per);
-  auto kern_nocam = pick_env(kv, false, per);
-  auto envg = per ? tc_envg_kernel_car : tc_envg_kernel;
+  // episodes (tc_env_set_episodes): the *_ep instantiations, likewise; the per-step rows belong to K-step calls only
+  const bool epk = e->ep.length != nullptr && mode != MODE_RENDER;
+  EpArgs ep0 = e->ep;
+  if (!ep_rows) ep0.len_rows = nullptr, ep0.ret_rows = nullptr;
+  auto ep_at = [&](size_t r0) {  // the launch whose first step is row r0 / N of the call
+    EpArgs q = ep0;
+    if (q.len_rows) q.len_rows += r0;
+    if (q.ret_rows) q.ret_rows += r0;
+    return q;
+  };
+  auto kern = pick_env(kv, true, per, epk);
+  auto kern_nocam = pick_env(kv, false, per, epk);
+  auto envg = epk ? (per ? tc_envg_kernel_ep_car : tc_envg_kernel_ep) : (per ? tc_envg_kernel_car : tc_envg_kernel);
   const bool do_raster = !(flags & (TC_F_NO_OBSERVATION | DBG_SKIP_CAMERA)) && (e->k.b.obs || (roll && roll->obs));
   const int N = e->k.N;
   MultiArgs ma;
@@ -4742,6 +4972,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
         memset(&sa, 0, sizeof(sa));
         sa.a = e->k;
         sa.cr = e->cr;
+        sa.ep = ep_at(r0);
         sa.a.env0 = 0;
         sa.a.seg_g = e->st_segm_g;
         sa.a.seg_n = e->st_segm_n;
@@ -4853,6 +5084,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
       memset(&sa, 0, sizeof(sa));
       sa.a = e->k;
       sa.cr = e->cr;
+      sa.ep = ep_at(r0);
       sa.a.env0 = 0;
       sa.a.seg_g = e->segm_g + rb * N * e->k.seg_cap * 5;
       sa.a.seg_n = e->segm_n + rb * N;
@@ -4995,10 +5227,10 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     const bool thick = e->k.cam.thickness > 1, cls = e->k.cam.format == TC_FMT_CLASSES;
     // (component groups that fit the K = 5 register cache: the K = 5 kernel with 16-segment batches, as for the frame kernel --
     // its simulate stage then walks the map's lane-line nodes in windows of 320 instead of 576)
-    fused_kern_t fk = e->kframe == 516 ? pick_fused<5, 16>(thick, cls, per)
-                      : kv == 5        ? pick_fused<5>(thick, cls, per)
-                      : kv == 8        ? pick_fused<8>(thick, cls, per)
-                                       : pick_fused<9>(thick, cls, per);
+    fused_kern_t fk = e->kframe == 516 ? pick_fused<5, 16>(thick, cls, per, epk)
+                      : kv == 5        ? pick_fused<5>(thick, cls, per, epk)
+                      : kv == 8        ? pick_fused<8>(thick, cls, per, epk)
+                                       : pick_fused<9>(thick, cls, per, epk);
     KArgs k = e->k;
     k.env0 = 0;
     RArgs r = make_rargs(e, e->k.seg_g, e->k.seg_n, e->k.seg_cap, nullptr, flags, 0, nullptr, mode == MODE_STEP);
@@ -5012,6 +5244,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     memset(&sa, 0, sizeof(sa));
     sa.a = k;
     sa.cr = e->cr;
+    sa.ep = ep_at(0);
     sa.r = r;
     sa.ma = ma;
     sa.mode = mode;
@@ -5047,6 +5280,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     memset(&sa, 0, sizeof(sa));
     sa.a = k;
     sa.cr = e->cr;
+    sa.ep = ep_at(0);
     sa.ma = ma;
     sa.ma.cam_here = do_raster ? 1 : 0;
     sa.mode = mode;
@@ -5095,7 +5329,11 @@ extern "C" int tc_step_multi(tc_env* e, const void* car_control, int32_t control
   }
   const bool want_obs = !(flags & (TC_F_NO_OBSERVATION | DBG_SKIP_CAMERA)) && (e->k.b.obs || (rollout && rollout->obs));
   (void)want_obs;
-  return launch(e, MODE_STEP, car_control, control_dtype, maneuver, nullptr, nullptr, flags, stream, n_steps, rollout);
+  if ((e->ep.len_rows || e->ep.ret_rows) && n_steps > e->ep_rows) {
+    set_err("tc_step_multi: more steps than the episode rows hold (tc_env_set_episode_rollout)");
+    return TC_E_INVALID;
+  }
+  return launch(e, MODE_STEP, car_control, control_dtype, maneuver, nullptr, nullptr, flags, stream, n_steps, rollout, true);
 }
 
 // Workload descriptor for benchmark lines: what the most recent frames actually drew.  Waits for the device and copies

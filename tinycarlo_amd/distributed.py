@@ -49,6 +49,11 @@ class RankGather:
     what = "flags": reward (f64), terminated (u8), truncated (u8) per env and step  -> 10 bytes / env-step
     what = "obs":   the above plus the observation tensor
     steps_per_launch: K of `launch()` (rows of a slot); `step()` uses row 0 only.
+
+    The wrapper only forwards `step_multi`; everything else is set on the shard itself, `.env`: the episode time limit
+    and statistics are `gather.env.set_time_limit(n, per_env=...)` and `gather.env.episode_stats`.  A per-env limit is
+    given PER SHARD (the shard's own num_envs entries, i.e. rows `shard_range(...)` of a global table), and the
+    statistics are per shard too: sum them over the ranks in torch if one figure is wanted.
     """
 
     def __init__(self, env, what: str = "flags", steps_per_launch: int = 1, group=None):

@@ -90,7 +90,7 @@ class TinyCarloEnv(gym.Env):
     _vec_cls = TinyCarloVecEnv  # the batched engine underneath (always the HIP one in the product)
 
     def __init__(self, render_mode: Optional[str] = None, config: Optional[Union[str, Dict[str, Any]]] = None,
-                 device: Union[None, str, torch.device] = None):
+                 device: Union[None, str, torch.device] = None, max_episode_steps: Optional[int] = None):
         if config is None:
             raise ValueError("config (path to a yaml file or a dict) is required")
         if render_mode == "human":
@@ -111,6 +111,10 @@ class TinyCarloEnv(gym.Env):
         self.action_space = v.single_action_space
         self.observation_space = v.single_observation_space
         self._rgb_vec: Optional[TinyCarloVecEnv] = None
+        # gym.make("tinycarlo-v2", ..., max_episode_steps=n): truncated after n steps, as gymnasium's make does with its
+        # TimeLimit wrapper (which consumes the argument itself when the real gymnasium is installed); kept by the step kernel
+        if max_episode_steps is not None:
+            v.set_time_limit(max_episode_steps)
         self.reset()  # env.py:75
 
     # flags the reference keeps on the env object (env.py:56,60)

@@ -92,6 +92,10 @@ class LazyInfo(dict):
         st, o = env.state, env.out
         super().__init__(cte=o["cte"], heading_error=o["heading_error"], orientation=st["theta"], status=o["status"],
                          laneline_distances={name: o["laneline_distances"][:, i] for i, name in enumerate(env.layer_names)})
+        ep = getattr(env, "_episodes", None)
+        if ep is not None:  # track_episodes / set_time_limit: the running episode (views, like the rest)
+            dict.__setitem__(self, "episode_length", ep["length"])
+            dict.__setitem__(self, "episode_return", ep["ret"])
         self._env = env
         self._serial = env._step_serial
         self._valid = None
@@ -221,6 +225,11 @@ class TinyCarloVecEnv(gym.Env):
 
         self.spawn_queue_len = int(spawn_queue_len)
         self._obs_shape = obs_shape
+        # episode time limit / statistics (set_time_limit / track_episodes): the live device tensors, or None = off
+        self._episodes: Optional[Dict[str, torch.Tensor]] = None
+        self._time_limit = 0                                   # shared max_episode_steps, 0 = none
+        self._time_limit_per_env: Optional[torch.Tensor] = None  # [N] int32 device tensor, or None
+        self._ep_rows: Tuple[int, int] = (0, 0)                # data pointers of the episode rows installed last
         self._setup_device()
         self._rngs: List[Optional[np.random.Generator]] = [None] * self.num_envs
         self._was_reset = False
@@ -424,6 +433,88 @@ class TinyCarloVecEnv(gym.Env):
     def car_episode(self) -> Optional[torch.Tensor]:
         """[N] int32 device counter of the episodes each env has drawn since randomize_cars (None without it)."""
         return self._car_episode
+
+    # ------------------------------------------------------------------ episode time limit and statistics
+    EPISODE_KEYS = ("length", "ret", "count", "last_length", "last_return", "length_sum", "return_sum")
+    EPISODE_ROLLOUT_KEYS = ("episode_length", "episode_return")
+
+    def track_episodes(self, on: bool = True) -> None:
+        """Per-env episode statistics kept by the step kernels (tc_env_set_episodes; gymnasium's
+        RecordEpisodeStatistics): ``episode_stats`` then holds the live device tensors and ``info`` carries
+        ``episode_length`` / ``episode_return``.  ``track_episodes(False)`` switches it off again, time limit included:
+        every result is then what it was before.  Turning it on starts from zeroed tensors."""
+        if not on:
+            if self._episodes is not None:
+                with torch.cuda.device(self.device):
+                    nat.check(nat.lib().tc_env_set_episodes(self._h, None, 0), "tc_env_set_episodes")
+            self._episodes, self._time_limit, self._time_limit_per_env, self._ep_rows = None, 0, None, (0, 0)
+            return
+        if self._episodes is None:
+            N, dev = self.num_envs, self.device
+            dts = {"length": torch.int32, "ret": torch.float64, "count": torch.int32, "last_length": torch.int32,
+                   "last_return": torch.float64, "length_sum": torch.int64, "return_sum": torch.float64}
+            self._episodes = {k: torch.zeros(N, dtype=dts[k], device=dev) for k in self.EPISODE_KEYS}
+            self._push_episodes()
+
+    def _push_episodes(self) -> None:
+        b = nat.EpisodeBuffers()
+        for k in self.EPISODE_KEYS:
+            setattr(b, k, self._episodes[k].data_ptr())
+        b.limit = self._time_limit_per_env.data_ptr() if self._time_limit_per_env is not None else None
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().tc_env_set_episodes(self._h, C.byref(b), int(self._time_limit)), "tc_env_set_episodes")
+
+    def set_time_limit(self, max_episode_steps: Optional[int], per_env=None) -> None:
+        """Truncates every episode after ``max_episode_steps`` steps (gymnasium's TimeLimit) inside the step kernels, so
+        it also acts between the steps of one ``step_multi`` call: the step that reaches the limit reports
+        ``truncated`` with ``TC_S_TIME_LIMIT`` in ``status``, and with autoreset the next step re-spawns the env.
+        ``None`` or 0: no shared limit.  ``per_env``: an [N] int tensor / sequence of limits that replaces the shared one
+        (entries <= 0: no limit for that env; None: back to the shared limit).  Implies ``track_episodes()``.
+        ``episode_stats["length"]`` is an ordinary tensor: write to it to stagger the first episodes, so that the envs
+        do not all reach the limit on the same step."""
+        lim = 0 if max_episode_steps is None else max_episode_steps
+        if isinstance(lim, bool) or not isinstance(lim, (int, np.integer)):
+            raise ValueError(f"max_episode_steps must be an int or None, got {max_episode_steps!r}")
+        if lim < 0:
+            raise ValueError(f"max_episode_steps must not be negative, got {lim}")
+        pe = None
+        if per_env is not None:
+            if isinstance(per_env, torch.Tensor):
+                if per_env.is_floating_point() or per_env.dtype == torch.bool:
+                    raise ValueError("per_env limits must be integers")
+                pe = per_env.detach().to("cpu", torch.int64)
+            else:
+                a = np.asarray(per_env)
+                if a.dtype.kind not in "iu":
+                    raise ValueError("per_env limits must be integers")
+                pe = torch.from_numpy(a.astype(np.int64))
+            if tuple(pe.shape) != (self.num_envs,):
+                raise ValueError(f"per_env must have {self.num_envs} entries, got shape {tuple(pe.shape)}")
+            if int(pe.min()) < 0 or int(pe.max()) >= 2 ** 31:
+                raise ValueError("per_env limits must be in [0, 2^31)")
+        self._time_limit = int(lim)
+        self._time_limit_per_env = None if pe is None else pe.to(self.device, torch.int32).contiguous()
+        if self._episodes is None:
+            self.track_episodes(True)
+        else:
+            self._push_episodes()
+
+    @property
+    def episode_stats(self) -> Optional[Dict[str, torch.Tensor]]:
+        """The live device tensors of the episode accounting, each [N] (None while it is off): ``length`` / ``ret`` of
+        the running episode, ``count`` of finished ones, ``last_length`` / ``last_return`` of the most recent,
+        ``length_sum`` / ``return_sum`` over all finished episodes of the env.  Sum them in torch for batch figures."""
+        return self._episodes
+
+    def _install_episode_rows(self, rollout: Optional[Dict[str, torch.Tensor]], K: int) -> None:
+        """the per-step episode rows of the K-step call about to be issued (host-side bookkeeping only)"""
+        lt = rollout.get("episode_length") if rollout else None
+        rt = rollout.get("episode_return") if rollout else None
+        ptrs = (lt.data_ptr() if lt is not None else 0, rt.data_ptr() if rt is not None else 0)
+        if ptrs != self._ep_rows:
+            nat.check(nat.lib().tc_env_set_episode_rollout(self._h, ptrs[0] or None, ptrs[1] or None,
+                                                           K if (ptrs[0] or ptrs[1]) else 0), "tc_env_set_episode_rollout")
+            self._ep_rows = ptrs
 
     # ------------------------------------------------------------------ fused reward / termination wrappers
     def set_terms(self, terms: Sequence[Term]) -> None:
@@ -631,7 +722,8 @@ class TinyCarloVecEnv(gym.Env):
                 "truncated": ((K, N), u8), "cte": ((K, N), f64), "heading_error": ((K, N), f64),
                 "status": ((K, N), i32), "x": ((K, N), f64), "y": ((K, N), f64), "theta": ((K, N), f64),
                 "velocity": ((K, N), f64), "laneline_distances": ((K, N, Cn), f64), "nearest_edge": ((K, N, Cn), i32),
-                "local_path": ((K, N, 8), i32), "lp_len": ((K, N), i32)}
+                "local_path": ((K, N, 8), i32), "lp_len": ((K, N), i32),
+                "episode_length": ((K, N), i32), "episode_return": ((K, N), f64)}
 
     def reserve_steps(self, n_steps: int) -> None:
         """Sizes the library's scratch ring for K-step calls that render observations (tc_env_reserve_steps): done
@@ -646,11 +738,14 @@ class TinyCarloVecEnv(gym.Env):
         """Device tensors for the per-step outputs of `step_multi`: [n_steps, num_envs, ...] each."""
         K, dev = int(n_steps), self.device
         shapes = self._rollout_shapes(K)
-        if keys == "all":
-            keys = self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS
+        if keys == "all":  # (the episode rows only while the accounting is on)
+            keys = self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS + (self.EPISODE_ROLLOUT_KEYS if self._episodes is not None else ())
         for k in keys:
             if k not in shapes:
-                raise ValueError(f"unknown rollout key {k!r}; choose from {self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS}")
+                raise ValueError(f"unknown rollout key {k!r}; choose from "
+                                 f"{self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS + self.EPISODE_ROLLOUT_KEYS}")
+            if k in self.EPISODE_ROLLOUT_KEYS and self._episodes is None:
+                raise ValueError(f"rollout key {k!r} needs track_episodes() / set_time_limit() first")
         return {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=dev) for k in keys}
 
     def rollout_info(self, rollout: Dict[str, torch.Tensor], k: int) -> Dict[str, Any]:
@@ -664,7 +759,8 @@ class TinyCarloVecEnv(gym.Env):
         coords = self._lp_nodes[idx]
         keep = (torch.arange(4, device=coords.device)[None, :] < n[:, None])
         vel = rollout["velocity"][k]
-        return {"cte": rollout["cte"][k], "heading_error": rollout["heading_error"][k],
+        ep = {key: rollout[key][k] for key in self.EPISODE_ROLLOUT_KEYS if key in rollout}
+        return {**ep, "cte": rollout["cte"][k], "heading_error": rollout["heading_error"][k],
                 "position": torch.stack([rollout["x"][k], rollout["y"][k]], dim=1), "orientation": rollout["theta"][k],
                 "laneline_distances": {name: rollout["laneline_distances"][k][:, i] for i, name in enumerate(self.layer_names)},
                 "local_path": coords * keep[:, :, None], "local_path_len": n,
@@ -707,6 +803,10 @@ class TinyCarloVecEnv(gym.Env):
                 shp, dt_ = want[k]
                 if t.dtype != dt_ or tuple(t.shape) != shp or t.device != self.device or not t.is_contiguous():
                     raise ValueError(f"rollout[{k!r}] must be a contiguous {dt_} tensor of shape {shp} on {self.device}")
+                if k in self.EPISODE_ROLLOUT_KEYS:  # not part of tc_rollout: installed per call (tc_env_set_episode_rollout)
+                    if self._episodes is None:
+                        raise ValueError(f"rollout[{k!r}] needs track_episodes() / set_time_limit() first")
+                    continue
                 setattr(r, k, t.data_ptr())
         if K > 1 and not (self.no_observation and self.render_mode is None):
             self.reserve_steps(K)  # (no-op once the scratch covers K: the call itself never allocates)
@@ -744,7 +844,12 @@ class TinyCarloVecEnv(gym.Env):
                 "car_per_env": None if self._car_rows is None else {
                     "rows": self._car_rows.detach().cpu().clone(),
                     "episode": None if self._car_episode is None else self._car_episode.detach().cpu().clone(),
-                    "randomization": None if self._car_rand is None else dict(self._car_rand)}}
+                    "randomization": None if self._car_rand is None else dict(self._car_rand)},
+                # episode accounting: the limits and every tensor of episode_stats
+                "episodes": None if self._episodes is None else {
+                    "max_episode_steps": int(self._time_limit),
+                    "per_env": None if self._time_limit_per_env is None else self._time_limit_per_env.detach().cpu().clone(),
+                    "stats": {k: v.detach().cpu().clone() for k, v in self._episodes.items()}}}
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
         if int(sd["num_envs"]) != self.num_envs:
@@ -779,6 +884,14 @@ class TinyCarloVecEnv(gym.Env):
                     self._car_episode.copy_(cpe["episode"])
                     self._push_car_rand(rnd["lo"], rnd["hi"], rnd["mask"], rnd["seed"], rnd["env_offset"])
                 self._car_rand = dict(rnd)
+        eps = sd.get("episodes")  # (absent in older checkpoints: off)
+        if eps is None:
+            if self._episodes is not None:
+                self.track_episodes(False)
+        else:
+            self.set_time_limit(int(eps["max_episode_steps"]), per_env=eps.get("per_env"))
+            for k, v in eps["stats"].items():
+                self._episodes[k].copy_(v)
         self._step_serial += 1
 
     def request_reset(self, mask: torch.Tensor) -> None:
@@ -890,6 +1003,8 @@ class PreparedStepMulti:
             t_dbg = time.perf_counter()
             env.profile(1)
         a = self._args
+        if env._episodes is not None:
+            env._install_episode_rows(self._keep[2], self.K)
         if torch.cuda.current_device() == env.device.index:
             rc = nat.lib().tc_step_multi(env._h, a[0], a[1], a[2], a[3], env._flags(), a[4], env._stream())
         else:
