@@ -229,7 +229,7 @@ int tc_env_set_car_randomization(tc_env* env, const double* lo, const double* hi
  * All members are DEVICE arrays of N, caller owned, read and written by every tc_reset / tc_step / tc_step_multi until
  * replaced.  length and ret are required, the others may be NULL.  bufs = NULL switches the feature off (and drops the
  * per-step rows below); without it nothing changes, and the kernels that do the accounting are separate instantiations
- * chosen at launch (*_ep): the others are untouched.
+ * chosen at launch (the TC_FEAT_EP bit of their feature mask): the others are untouched.
  * Per env i; limit_i = limit[i] when limit is given, else max_episode_steps; a value <= 0 means no limit:
  *   1. (re)spawned by tc_reset (mask) or by a TC_F_AUTORESET re-spawn at the start of a step: length = 0, ret = 0.0.  The
  *      re-spawn step itself counts nothing; count, last_* and *_sum are not touched.

@@ -1,6 +1,9 @@
 """Shared helpers for the test-suite: bundled configs -> Map / CarParams / Camera, golden loaders."""
 import copy
+import functools
 import os
+import re
+import subprocess
 
 import numpy as np
 import yaml
@@ -15,6 +18,49 @@ CFG = {"simple_layout": "config_simple_layout.yaml", "knuffingen": "config_knuff
        "formula_student_track": "config_formula_student_track.yaml"}
 
 _cache = {}
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = "/opt/rocm/bin/hipcc"
+TC_FEAT_CAR, TC_FEAT_EP = 1, 2  # tinycarlo_hip.hip: the feature mask of the kernels that simulate
+
+
+@functools.lru_cache(maxsize=None)
+def dev_kernel_resources():
+    """The compiler's own figures of every kernel of the -DTC_DEV_FAST build (cfg3's K = 5 variants), cross-compiled to
+    gfx950 assembly once per test run (no GPU needed): {mangled name: (vgpr_count, vgpr_spill_count, scratch bytes)}."""
+    import tempfile
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, "tc.s")
+        cmd = [HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-mllvm", "-disable-machine-licm", "-std=c++17",
+               "-DTC_DEV_FAST", "-S", "--cuda-device-only", "-o", out,
+               os.path.join(ROOT, "tinycarlo_amd", "csrc", "tinycarlo_hip.hip")]
+        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL, timeout=600)
+        with open(out) as f:
+            s = f.read()
+    seen = {}
+    for b in s.split("  - .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", b).group(1)
+        g = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", b).group(1))  # noqa: E731
+        seen[name] = (g("vgpr_count"), g("vgpr_spill_count"), g("private_segment_fixed_size"))
+    return seen
+
+
+def kernel_variant(name):
+    """(family, feature mask) of a simulate kernel's mangled name, else None.  The mask (TC_FEAT_* bits) is the last
+    template argument, an unsigned: _Z13tc_env_kernelILi5ELb1ELj3EEv8StepArgs is tc_env_kernel<5, true, 3u> -> ("env", 3)"""
+    m = re.match(r"_Z\d+tc_(step|envg|env)_kernelI(?:L\w+E)*Lj(\d+)EEv8StepArgs$", name)
+    return (m.group(1), int(m.group(2))) if m else None
+
+
+def assert_one_variant_set(seen, names):
+    """`names` are the four kernels of one feature mask: the step kernel, tc_env_kernel<.., true> and <.., false>, the
+    grouped kernel; none spills VGPRs or uses scratch, none has more than 128 VGPRs (4 wavefronts per SIMD)."""
+    assert sorted(kernel_variant(n)[0] for n in names) == ["env", "env", "envg", "step"], sorted(seen)
+    assert sorted(re.search(r"Lb([01])ELj", n).group(1) for n in names if kernel_variant(n)[0] == "env") == ["0", "1"], names
+    for n in names:
+        vgpr, spill, scratch = seen[n]
+        assert spill == 0 and scratch == 0, (n, "spills VGPRs / uses scratch", seen[n])
+        assert vgpr <= 128, (n, "more than 128 VGPRs", vgpr)
 
 
 # configs that are test inputs only (tests/golden/): the synthetic maps of make_stress_map.py

@@ -3,18 +3,16 @@ against the oracle's SplitMix64, the argument validation of set_env_cars / rando
 compiler's resource figures of the per-env-car kernel instantiations."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import orc
+from common import HIPCC, ROOT, TC_FEAT_CAR, assert_one_variant_set, dev_kernel_resources, kernel_variant
 from tinycarlo_amd import _native as nat
 from tinycarlo_amd.config import CarParams
 from tinycarlo_amd.randomization import CAR_COLUMNS, car_ranges, car_rows, config_row, draw_car_params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 M64 = (1 << 64) - 1
 
 
@@ -133,22 +131,9 @@ def test_header_constants_match_the_binding():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_per_env_car_kernels_keep_their_registers(tmp_path):
-    """the *_car instantiations (cfg3's K = 5 variants): no VGPR spill, no scratch, at most 128 VGPRs (4 waves / SIMD)"""
-    out = tmp_path / "tc.s"
-    cmd = [HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-mllvm", "-disable-machine-licm", "-std=c++17",
-           "-DTC_DEV_FAST", "-S", "--cuda-device-only", "-o", str(out),
-           os.path.join(ROOT, "tinycarlo_amd", "csrc", "tinycarlo_hip.hip")]
-    subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL, timeout=600)
-    s = out.read_text()
-    seen = {}
-    for b in s.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", b).group(1)
-        g = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", b).group(1))  # noqa: E731
-        seen[name] = (g("vgpr_count"), g("vgpr_spill_count"), g("private_segment_fixed_size"))
-    car = [n for n in seen if re.search(r"tc_(step|envg|env)_kernel_car", n)]
-    assert len(car) == 4, sorted(seen)  # tc_step_kernel_car<5,...>, tc_env_kernel_car<5, true|false>, tc_envg_kernel_car
-    for n in car:
-        vgpr, spill, scratch = seen[n]
-        assert spill == 0 and scratch == 0, (n, "spills VGPRs / uses scratch", seen[n])
-        assert vgpr <= 128, (n, "more than 128 VGPRs", vgpr)
+def test_per_env_car_kernels_keep_their_registers():
+    """the kernels with the car bit alone (cfg3's K = 5 variants): no VGPR spill, no scratch, at most 128 VGPRs (4 waves / SIMD)"""
+    seen = dev_kernel_resources()
+    car = [n for n in seen if (kernel_variant(n) or (None, 0))[1] == TC_FEAT_CAR]
+    assert len(car) == 4, sorted(seen)  # tc_step_kernel<5, .., 1u>, tc_env_kernel<5, true|false, 1u>, tc_envg_kernel<1u>
+    assert_one_variant_set(seen, car)

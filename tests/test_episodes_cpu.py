@@ -1,17 +1,15 @@
 """CPU checks of the episode time limit / statistics API: header, binding and library agree, the argument validation
-that needs no device, set_time_limit's input checks, and the compiler's resource figures of the *_ep kernels."""
+that needs no device, set_time_limit's input checks, and the compiler's resource figures of the kernels with the episode bit."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from common import HIPCC, ROOT, TC_FEAT_CAR, TC_FEAT_EP, assert_one_variant_set, dev_kernel_resources, kernel_variant
 from tinycarlo_amd import _native as nat
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 NEW = ("tc_env_set_episodes", "tc_env_set_episode_rollout")
 
 
@@ -88,25 +86,16 @@ def test_set_time_limit_rejects_bad_input():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_episode_kernels_keep_their_registers(tmp_path):
-    """the *_ep instantiations (cfg3's K = 5 variants): no VGPR spill, no scratch, at most 128 VGPRs (4 waves / SIMD)"""
-    out = tmp_path / "tc.s"
-    cmd = [HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-mllvm", "-disable-machine-licm", "-std=c++17",
-           "-DTC_DEV_FAST", "-S", "--cuda-device-only", "-o", str(out),
-           os.path.join(ROOT, "tinycarlo_amd", "csrc", "tinycarlo_hip.hip")]
-    subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL, timeout=600)
-    s = out.read_text()
-    seen = {}
-    for b in s.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", b).group(1)
-        g = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", b).group(1))  # noqa: E731
-        seen[name] = (g("vgpr_count"), g("vgpr_spill_count"), g("private_segment_fixed_size"))
-    ep = [n for n in seen if re.search(r"tc_(step|envg|env)_kernel_ep", n)]
-    # tc_step_kernel_ep / _ep_car <5,...>, tc_env_kernel_ep / _ep_car <5, true|false>, tc_envg_kernel_ep / _ep_car
+def test_episode_kernels_keep_their_registers():
+    """the kernels with the episode bit (cfg3's K = 5 variants): no VGPR spill, no scratch, at most 128 VGPRs (4 waves / SIMD)"""
+    seen = dev_kernel_resources()
+    feat = {n: kernel_variant(n)[1] for n in seen if kernel_variant(n)}
+    # every kernel that simulates carries a mask: the twelve below and the four without a feature
+    assert len(feat) == 16 and len(feat) == len([n for n in seen if re.search(r"tc_(step|envg|env)_kernel", n)]), sorted(seen)
+    ep = [n for n in feat if feat[n] & TC_FEAT_EP]
+    # tc_step_kernel<5, .., 2u | 3u>, tc_env_kernel<5, true|false, 2u | 3u>, tc_envg_kernel<2u | 3u>
     assert len(ep) == 8, sorted(seen)
-    assert len([n for n in ep if "_ep_car" in n]) == 4
-    assert not [n for n in ep if re.search(r"tc_(step|envg|env)_kernel_car", n)]  # the car test counts exactly four of those
-    for n in ep:
-        vgpr, spill, scratch = seen[n]
-        assert spill == 0 and scratch == 0, (n, "spills VGPRs / uses scratch", seen[n])
-        assert vgpr <= 128, (n, "more than 128 VGPRs", vgpr)
+    both = [n for n in ep if feat[n] == TC_FEAT_EP | TC_FEAT_CAR]
+    assert len(both) == 4
+    assert_one_variant_set(seen, both)
+    assert_one_variant_set(seen, [n for n in ep if n not in both])

@@ -6,28 +6,15 @@ step) with every parity test still green.  This keeps that from going unnoticed:
 most 128 VGPRs in the kernels of the benchmark's path."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+from common import HIPCC, dev_kernel_resources
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_no_vgpr_spills_in_the_hot_kernels(tmp_path):
-    out = tmp_path / "tc.s"
-    cmd = [HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-mllvm", "-disable-machine-licm", "-std=c++17",
-           "-DTC_DEV_FAST", "-S", "--cuda-device-only", "-o", str(out),
-           os.path.join(ROOT, "tinycarlo_amd", "csrc", "tinycarlo_hip.hip")]
-    subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL, timeout=600)
-    s = out.read_text()
-    seen = {}
-    for b in s.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", b).group(1)
-        g = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", b).group(1))  # noqa: E731
-        seen[name] = (g("vgpr_count"), g("vgpr_spill_count"), g("private_segment_fixed_size"))
+def test_no_vgpr_spills_in_the_hot_kernels():
+    seen = dev_kernel_resources()
     hot = [n for n in seen if re.search(r"tc_(frame|frame_recover|step|envg|env|raster)_kernel", n)]
     assert len(hot) >= 5, sorted(seen)
     for n in hot:

@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/tinycarlo_hip.h"
@@ -236,7 +237,7 @@ struct LiveLds {
   int cursor;       // spawn_cursor: re-spawns of this env so far
   int cursor0;      // its value in the caller's buffer (stored back only when it changed)
   int trunc, status, terminated;
-  int ep_len;  // running episode's length (tc_env_set_episodes; touched by the *_ep kernels only)
+  int ep_len;  // running episode's length (tc_env_set_episodes; touched by the TC_FEAT_EP kernels only)
   int pad[2];
   int cnt[TC_MAX_TERMS];  // steps_true of the consecutive-step terms
   int ne[TC_MAX_LAYERS];
@@ -324,8 +325,18 @@ __device__ __forceinline__ double uni_d(double v) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-env features of the simulate stages: ONE template parameter (FEAT, a mask of these bits) of sim_body and of the
+// three kernels that simulate -- tc_step_kernel<.., FEAT>, tc_env_kernel<.., FEAT>, tc_envg_kernel<FEAT>; a kernel trace
+// shows the mask as a number (tc_envg_kernel<3u>: both).  launch() sets the bits of a call (`feat`).
+//   bit              compiles in                                                           reads
+//   TC_FEAT_CAR (1)  car constants from the env's row, re-drawn at every re-spawn          StepArgs::cr
+//   TC_FEAT_EP  (2)  episode length / return / time limit and the finished-episode sums    StepArgs::ep
+// A kernel without a bit contains none of that feature's code and compiles as if the feature did not exist.
+enum : unsigned { TC_FEAT_CAR = 1, TC_FEAT_EP = 2, TC_FEAT_ALL = TC_FEAT_CAR | TC_FEAT_EP };
+
+// ---------------------------------------------------------------------------------------------
 // Per-env car constants (tc_env_set_car_per_env): row [env][TC_CAR_NP] of a caller-owned device buffer replaces the
-// shared car's wheelbase, track width and limits; T and the two presence flags stay shared.  Only the *_car kernels
+// shared car's wheelbase, track width and limits; T and the two presence flags stay shared.  Only the TC_FEAT_CAR kernels
 // (the PER instantiations of the simulate stages, chosen at launch) read it: the shared-car kernels compile as before.
 // With tc_env_set_car_randomization, every re-spawn draws the masked columns of the env's next episode first
 // (tc_car_stream / tc_car_draw, tc_rng.h) and writes them back to the row, so the row always holds the constants in force.
@@ -380,7 +391,7 @@ __device__ __forceinline__ void car_respawn(const CarRows& cr, int env, bool wri
 }
 
 // ---------------------------------------------------------------------------------------------
-// Episode time limit and per-env episode statistics (tc_env_set_episodes).  Only the *_ep kernels (the EP instantiations
+// Episode time limit and per-env episode statistics (tc_env_set_episodes).  Only the TC_FEAT_EP kernels (the EP instantiations
 // of the simulate stages, chosen at launch) touch any of this: every other kernel compiles as before.  Per env and step:
 //   re-spawned in this step (tc_reset, autoreset)  length = 0, ret = 0.0, nothing else
 //   TC_S_NOT_RESET                                 left alone
@@ -1046,12 +1057,13 @@ struct FramePose {
 
 // PER: the env's car constants come from its row of cr.rows (per-env cars, tc_env_set_car_per_env), else a.car.
 // EP: episode length / return / time limit (tc_env_set_episodes); the running pair lives in LiveLds (ep_len, ep_ret).
-template <int K, bool PER = false, bool EP = false>
+template <int K, unsigned FEAT = 0>
 __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, int env, int mode,
                                 const void* car_control, int cdtype,
                                 const int* maneuver, const int* spawn_nodes, const unsigned char* mask,
                                 unsigned int flags, const RollStep& roll, const int tid, MapCache<K>& mc, FramePose& fp,
                                 const CarRows& cr = CarRows(), const EpArgs& ep = EpArgs()) {
+  constexpr bool PER = (FEAT & TC_FEAT_CAR) != 0, EP = (FEAT & TC_FEAT_EP) != 0;
 
   TSTAMP(0);
   TSTAMP_REAL(30);
@@ -2426,8 +2438,8 @@ struct StepArgs {
   const int* spawn_nodes;
   const unsigned char* mask;
   const int* env_order;  // tc_step_kernel: workgroup w works on env env_order[w] (a permutation of 0..N-1), or NULL = env w
-  CarRows cr;            // per-env cars: read by the *_car kernels only (last, so every other member keeps its offset)
-  EpArgs ep;             // episodes: read by the *_ep kernels only (behind it, for the same reason)
+  CarRows cr;            // per-env cars: read by the TC_FEAT_CAR kernels only (last, so every other member keeps its offset)
+  EpArgs ep;             // episodes: read by the TC_FEAT_EP kernels only (behind it, for the same reason)
 };
 
 // The launch arguments, read through a pointer the optimiser cannot see through.  Inside the step loop of tc_step_multi
@@ -2459,8 +2471,9 @@ __device__ __forceinline__ bool wants_frame(const StepArgs& sa) {
 // What becomes of the frames is the launch's choice: nothing (no observation), the camera stage here and a raster
 // launch behind (cam_here; maps of the K = 13 variant, TC_FUSE=0), or -- the K-step default -- only the poses, from which
 // tc_frame_kernel produces every (step, env) frame as a workgroup of its own.
-template <int K, bool CAM, bool PER, bool EP>
+template <int K, bool CAM, unsigned FEAT>
 __device__ __forceinline__ void env_kernel_body() {
+  constexpr bool EP = (FEAT & TC_FEAT_EP) != 0;
   extern __shared__ __align__(16) unsigned char smem[];
   // Touching v127 makes the kernel descriptor ask for 128 VGPRs, i.e. caps the SIMD at the 4 wavefronts the launch
   // needs (N = 4096 one-wavefront workgroups = 4 per SIMD).  The camera-less variant uses 74 registers and would fit 6,
@@ -2501,7 +2514,7 @@ __device__ __forceinline__ void env_kernel_body() {
     MapCache<K> mc = {};  // (initialised: a path that leaves it unset would otherwise make it a loop-carried value -- 30
                           // registers per lane held across the whole step body, raster stage included)
     FramePose fp;
-    sim_body<K, PER, EP>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
+    sim_body<K, FEAT>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
                          sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr, sa.ep);
     if (sa.ma.pose_rows) {
       double pose[12];
@@ -2532,23 +2545,9 @@ __device__ __forceinline__ void env_kernel_body() {
     if (EP) ep_out(s1.a, s1.ep, smem, env);
   }
 }
-template <int K, bool CAM>
+template <int K, bool CAM, unsigned FEAT>
 __global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) void tc_env_kernel(StepArgs sa_unused) {
-  env_kernel_body<K, CAM, false, false>();
-}
-// the same with per-env car constants (StepArgs::cr)
-template <int K, bool CAM>
-__global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) void tc_env_kernel_car(StepArgs sa_unused) {
-  env_kernel_body<K, CAM, true, false>();
-}
-// the two with the episode accounting (StepArgs::ep)
-template <int K, bool CAM>
-__global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) void tc_env_kernel_ep(StepArgs sa_unused) {
-  env_kernel_body<K, CAM, false, true>();
-}
-template <int K, bool CAM>
-__global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) void tc_env_kernel_ep_car(StepArgs sa_unused) {
-  env_kernel_body<K, CAM, true, true>();
+  env_kernel_body<K, CAM, FEAT>();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2581,8 +2580,9 @@ struct GroupLds {  // per env of the wavefront: what the reward / termination te
 // kernel with its stores switched off).  The edge scan is ~33 loads per lane and step: from LDS it neither waits for
 // the stores nor pays an L2 round trip per batch of loads.
 typedef const __attribute__((address_space(3))) double* LdsDouble;
-template <bool PER, bool EP>
+template <unsigned FEAT>
 __device__ __forceinline__ void envg_kernel_body() {
+  constexpr bool PER = (FEAT & TC_FEAT_CAR) != 0, EP = (FEAT & TC_FEAT_EP) != 0;
   __shared__ GroupLds glds[TC_ENVG_NT / TC_EL];
   extern __shared__ __align__(16) unsigned char gsm[];
   // Highest issue priority: when this kernel shares the chip with the frame kernel of the previous chunk it is the
@@ -2980,13 +2980,13 @@ __device__ __forceinline__ void envg_kernel_body() {
   }
   if (live && s1.a.term_counters && sub < s1.a.n_terms) s1.a.term_counters[(size_t)env * TC_MAX_TERMS + sub] = gl.cnt[sub];
 }
-__global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel(StepArgs sa_unused) { envg_kernel_body<false, false>(); }
-// the same with per-env car constants (StepArgs::cr)
-__global__ __launch_bounds__(TC_ENVG_NT) void tc_envg_kernel_car(StepArgs sa_unused) { envg_kernel_body<true, false>(); }
-// the two with the episode accounting (StepArgs::ep).  (4 wavefronts per SIMD asked for: left to itself the allocator
-// takes 129 / 131 VGPRs here, whatever the episode state is kept in; held to the 128 of the other two it spills nothing)
-__global__ __launch_bounds__(TC_ENVG_NT, 4) void tc_envg_kernel_ep(StepArgs sa_unused) { envg_kernel_body<false, true>(); }
-__global__ __launch_bounds__(TC_ENVG_NT, 4) void tc_envg_kernel_ep_car(StepArgs sa_unused) { envg_kernel_body<true, true>(); }
+// (Launch bounds: with the episode accounting 4 wavefronts per SIMD are asked for -- left to itself the allocator takes
+// 129 / 131 VGPRs there, whatever the episode state is kept in; held to the 128 of the other variants it spills nothing.
+// 0 = nothing asked for, as for the variants without it.)
+template <unsigned FEAT>
+__global__ __launch_bounds__(TC_ENVG_NT, ((FEAT & TC_FEAT_EP) ? 4 : 0)) void tc_envg_kernel(StepArgs sa_unused) {
+  envg_kernel_body<FEAT>();
+}
 
 // One (step, env) frame per workgroup: camera stage from the pose the simulate launch left, then the raster stage.
 // Frames do not depend on each other, a launch has steps x N of them -- many more than the chip holds at once -- and
@@ -3156,8 +3156,9 @@ __global__ __launch_bounds__(TC_NT) void tc_frame_recover_kernel(FrameArgs fa_un
 // All stages in one launch: the same wavefront simulates its env, runs the camera and rasterises the frame.  The form
 // of tc_step / tc_reset / tc_render (one step: nothing to balance, and one kernel boundary less), and of tc_step_multi
 // under TC_MULTI_SPLIT=0.
-template <int K, bool THICK, int FMT, int RBT, bool PER, bool EP>
+template <int K, bool THICK, int FMT, int RBT, unsigned FEAT>
 __device__ __forceinline__ void step_kernel_body() {
+  constexpr bool EP = (FEAT & TC_FEAT_EP) != 0;
   extern __shared__ __align__(16) unsigned char smem[];
   const StepArgs& s0 = step_args();
   if ((int)blockIdx.x >= s0.a.N) return;
@@ -3182,7 +3183,7 @@ __device__ __forceinline__ void step_kernel_body() {
     MapCache<K> mc = {};  // (initialised: a path that leaves it unset would otherwise make it a loop-carried value -- 30
                           // registers per lane held across the whole step body, raster stage included)
     FramePose fp;
-    sim_body<K, PER, EP>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
+    sim_body<K, FEAT>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
                          sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr, sa.ep);
     if (wants_frame(sa)) {
       int nseg;
@@ -3210,23 +3211,9 @@ __device__ __forceinline__ void step_kernel_body() {
     if (EP) ep_out(s1.a, s1.ep, smem, env);
   }
 }
-template <int K, bool THICK, int FMT, int RBT = RB_OF_K(K)>
+template <int K, bool THICK, int FMT, int RBT, unsigned FEAT>
 __global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_kernel(StepArgs sa_unused) {
-  step_kernel_body<K, THICK, FMT, RBT, false, false>();
-}
-// the same with per-env car constants (StepArgs::cr)
-template <int K, bool THICK, int FMT, int RBT = RB_OF_K(K)>
-__global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_kernel_car(StepArgs sa_unused) {
-  step_kernel_body<K, THICK, FMT, RBT, true, false>();
-}
-// the two with the episode accounting (StepArgs::ep)
-template <int K, bool THICK, int FMT, int RBT = RB_OF_K(K)>
-__global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_kernel_ep(StepArgs sa_unused) {
-  step_kernel_body<K, THICK, FMT, RBT, false, true>();
-}
-template <int K, bool THICK, int FMT, int RBT = RB_OF_K(K)>
-__global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_kernel_ep_car(StepArgs sa_unused) {
-  step_kernel_body<K, THICK, FMT, RBT, true, true>();
+  step_kernel_body<K, THICK, FMT, RBT, FEAT>();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3292,10 +3279,34 @@ __global__ __launch_bounds__(64) void tc_gate_kernel(const unsigned int* residen
     __builtin_amdgcn_s_sleep(2);
 }
 
-typedef void (*fused_kern_t)(StepArgs);
+// ---------------------------------------------------------------------------------------------
+// From run-time choices to a kernel: lift(f, Among<T, ..>{v}, ..) calls f with one std::integral_constant per choice --
+// the value of the list that v equals, the LAST of the list when it equals none -- so f can use them as template arguments.
+template <class T, T V, T... Vs>
+struct Among {
+  T v;
+};
+template <class F>
+static auto lift(F&& f) {
+  return f();
+}
+template <class F, class T, T V, T... Vs, class... More>
+static auto lift(F&& f, Among<T, V, Vs...> c, More... more) {
+  auto with = [&](auto... rest) { return f(std::integral_constant<T, V>{}, rest...); };
+  if constexpr (sizeof...(Vs) == 0)
+    return lift(with, more...);
+  else
+    return c.v == V ? lift(with, more...) : lift(f, Among<T, Vs...>{c.v}, more...);
+}
+
+// The variants compiled, per template parameter.  Kcode names a (K, RB) pair of tc_step_kernel / tc_frame_kernel: K itself
+// with the batch size that goes with it, or 516 = K 5 with batches of 16 (tc_env::kframe).
 // TC_DEV_FAST (make dev): only the K = 5 / thick / classes variants are instantiated -- a compile of seconds instead of
-// minutes for kernel work on cfg3 (make dev DEVK=9 DEVFMT=TC_FMT_RGB: the variants of cfg5; DEVK=9 alone: cfg4).  Never
-// shipped: the default build has no such macro.
+// minutes for kernel work on cfg3 (make dev DEVK=9 DEVFMT=TC_FMT_RGB: the variants of cfg5; DEVK=9 alone: cfg4) -- and
+// every request maps to them (one-element lists).  Never shipped: the default build has no such macro.
+using Feats = Among<unsigned, 0u, TC_FEAT_CAR, TC_FEAT_EP, TC_FEAT_ALL>;
+using Bools = Among<bool, true, false>;
+#ifdef TC_DEV_FAST
 #ifndef TC_DEV_KV
 #define TC_DEV_KV 5
 #endif
@@ -3308,86 +3319,54 @@ typedef void (*fused_kern_t)(StepArgs);
 #ifndef TC_DEV_SRB
 #define TC_DEV_SRB RB_OF_K(TC_DEV_SK)
 #endif
-template <int K, int RBT = RB_OF_K(K)>
-static fused_kern_t pick_fused(bool thick, bool cls, bool per = false, bool ep = false) {
-#ifdef TC_DEV_FAST
-  if (ep) return per ? tc_step_kernel_ep_car<TC_DEV_SK, true, TC_DEV_FMTV, TC_DEV_SRB> : tc_step_kernel_ep<TC_DEV_SK, true, TC_DEV_FMTV, TC_DEV_SRB>;
-  return per ? tc_step_kernel_car<TC_DEV_SK, true, TC_DEV_FMTV, TC_DEV_SRB> : tc_step_kernel<TC_DEV_SK, true, TC_DEV_FMTV, TC_DEV_SRB>;
-#else
-  if (ep && per)
-    return thick ? (cls ? tc_step_kernel_ep_car<K, true, TC_FMT_CLASSES, RBT> : tc_step_kernel_ep_car<K, true, TC_FMT_RGB, RBT>)
-                 : (cls ? tc_step_kernel_ep_car<K, false, TC_FMT_CLASSES, RBT> : tc_step_kernel_ep_car<K, false, TC_FMT_RGB, RBT>);
-  if (ep)
-    return thick ? (cls ? tc_step_kernel_ep<K, true, TC_FMT_CLASSES, RBT> : tc_step_kernel_ep<K, true, TC_FMT_RGB, RBT>)
-                 : (cls ? tc_step_kernel_ep<K, false, TC_FMT_CLASSES, RBT> : tc_step_kernel_ep<K, false, TC_FMT_RGB, RBT>);
-  if (per)
-    return thick ? (cls ? tc_step_kernel_car<K, true, TC_FMT_CLASSES, RBT> : tc_step_kernel_car<K, true, TC_FMT_RGB, RBT>)
-                 : (cls ? tc_step_kernel_car<K, false, TC_FMT_CLASSES, RBT> : tc_step_kernel_car<K, false, TC_FMT_RGB, RBT>);
-  return thick ? (cls ? tc_step_kernel<K, true, TC_FMT_CLASSES, RBT> : tc_step_kernel<K, true, TC_FMT_RGB, RBT>)
-               : (cls ? tc_step_kernel<K, false, TC_FMT_CLASSES, RBT> : tc_step_kernel<K, false, TC_FMT_RGB, RBT>);
-#endif
-}
-// simulate stage alone (tc_env_kernel), by register-cache variant; per: the per-env-car instantiation; ep: the one with
-// the episode accounting
-typedef void (*env_kern_t)(StepArgs);
-static env_kern_t pick_env(int kv, bool cam, bool per, bool ep = false) {
-#ifdef TC_DEV_FAST
-  (void)kv;
-  if (ep)
-    return per ? (cam ? tc_env_kernel_ep_car<TC_DEV_KV, true> : tc_env_kernel_ep_car<TC_DEV_KV, false>)
-               : (cam ? tc_env_kernel_ep<TC_DEV_KV, true> : tc_env_kernel_ep<TC_DEV_KV, false>);
-  return per ? (cam ? tc_env_kernel_car<TC_DEV_KV, true> : tc_env_kernel_car<TC_DEV_KV, false>)
-             : (cam ? tc_env_kernel<TC_DEV_KV, true> : tc_env_kernel<TC_DEV_KV, false>);
-#else
-  if (ep && per) {
-    if (cam) return kv == 5 ? tc_env_kernel_ep_car<5, true> : kv == 8 ? tc_env_kernel_ep_car<8, true> : kv == 9 ? tc_env_kernel_ep_car<9, true> : tc_env_kernel_ep_car<13, true>;
-    return kv == 5 ? tc_env_kernel_ep_car<5, false> : kv == 8 ? tc_env_kernel_ep_car<8, false> : kv == 9 ? tc_env_kernel_ep_car<9, false> : tc_env_kernel_ep_car<13, false>;
-  }
-  if (ep) {
-    if (cam) return kv == 5 ? tc_env_kernel_ep<5, true> : kv == 8 ? tc_env_kernel_ep<8, true> : kv == 9 ? tc_env_kernel_ep<9, true> : tc_env_kernel_ep<13, true>;
-    return kv == 5 ? tc_env_kernel_ep<5, false> : kv == 8 ? tc_env_kernel_ep<8, false> : kv == 9 ? tc_env_kernel_ep<9, false> : tc_env_kernel_ep<13, false>;
-  }
-  if (per) {
-    if (cam) return kv == 5 ? tc_env_kernel_car<5, true> : kv == 8 ? tc_env_kernel_car<8, true> : kv == 9 ? tc_env_kernel_car<9, true> : tc_env_kernel_car<13, true>;
-    return kv == 5 ? tc_env_kernel_car<5, false> : kv == 8 ? tc_env_kernel_car<8, false> : kv == 9 ? tc_env_kernel_car<9, false> : tc_env_kernel_car<13, false>;
-  }
-  if (cam) return kv == 5 ? tc_env_kernel<5, true> : kv == 8 ? tc_env_kernel<8, true> : kv == 9 ? tc_env_kernel<9, true> : tc_env_kernel<13, true>;
-  return kv == 5 ? tc_env_kernel<5, false> : kv == 8 ? tc_env_kernel<8, false> : kv == 9 ? tc_env_kernel<9, false> : tc_env_kernel<13, false>;
-#endif
-}
-
-typedef void (*frame_kern_t)(FrameArgs);
-#ifndef TC_DEV_FK   // dev builds: K / batch size of the one frame kernel variant compiled (cfg4, cfg5: DEVFK=5 DEVFRB=16)
+#ifndef TC_DEV_FK   // K / batch size of the one frame kernel variant compiled (cfg4, cfg5: DEVFK=5 DEVFRB=16)
 #define TC_DEV_FK TC_DEV_KV
 #endif
 #ifndef TC_DEV_FRB
 #define TC_DEV_FRB RB_OF_K(TC_DEV_FK)
 #endif
-template <int K, int RBT = RB_OF_K(K)>
-static frame_kern_t pick_frame(bool thick, bool cls) {
-#ifdef TC_DEV_FAST
-  return tc_frame_kernel<TC_DEV_FK, true, TC_DEV_FMTV, TC_DEV_FRB>;
+using Kvars = Among<int, TC_DEV_KV>;
+using Kcodes = Among<int, 0>;
+using Thicks = Among<bool, true>;
+using Fmts = Among<int, TC_DEV_FMTV>;
+template <int> struct StepKRb { static constexpr int K = TC_DEV_SK, RB = TC_DEV_SRB; };
+template <int> struct FrameKRb { static constexpr int K = TC_DEV_FK, RB = TC_DEV_FRB; };
 #else
-  return thick ? (cls ? tc_frame_kernel<K, true, TC_FMT_CLASSES, RBT> : tc_frame_kernel<K, true, TC_FMT_RGB, RBT>)
-               : (cls ? tc_frame_kernel<K, false, TC_FMT_CLASSES, RBT> : tc_frame_kernel<K, false, TC_FMT_RGB, RBT>);
+using Kvars = Among<int, 5, 8, 9, 13>;
+using Kcodes = Among<int, 516, 5, 8, 9>;
+using Thicks = Bools;
+using Fmts = Among<int, TC_FMT_CLASSES, TC_FMT_RGB>;
+template <int CODE> struct StepKRb { static constexpr int K = CODE == 516 ? 5 : CODE, RB = CODE == 516 ? 16 : RB_OF_K(CODE); };
+template <int CODE> using FrameKRb = StepKRb<CODE>;
 #endif
-}
 
-template <int K, int RBT = RB_OF_K(K)>
-static frame_kern_t pick_recover(bool thick, bool cls) {
-#ifdef TC_DEV_FAST
-  return tc_frame_recover_kernel<TC_DEV_FK, true, TC_DEV_FMTV, TC_DEV_FRB>;
-#else
-  return thick ? (cls ? tc_frame_recover_kernel<K, true, TC_FMT_CLASSES, RBT> : tc_frame_recover_kernel<K, true, TC_FMT_RGB, RBT>)
-               : (cls ? tc_frame_recover_kernel<K, false, TC_FMT_CLASSES, RBT> : tc_frame_recover_kernel<K, false, TC_FMT_RGB, RBT>);
-#endif
+typedef void (*step_kern_t)(StepArgs);
+typedef void (*frame_kern_t)(FrameArgs);
+typedef void (*raster_kern_t)(RArgs);
+// all stages in one launch
+static step_kern_t step_kernel_of(int kcode, bool thick, int fmt, unsigned feat) {
+  return lift([](auto kc, auto t, auto f, auto ft) -> step_kern_t { return tc_step_kernel<StepKRb<kc>::K, t, f, StepKRb<kc>::RB, ft>; },
+              Kcodes{kcode}, Thicks{thick}, Fmts{fmt}, Feats{feat});
 }
-// by tc_env::kframe: the simulate variant's K, or 516 = K 5 with batches of 16
-static frame_kern_t frame_kernel_of(int kframe, bool thick, bool cls) {
-  return kframe == 516 ? pick_frame<5, 16>(thick, cls) : kframe == 5 ? pick_frame<5>(thick, cls) : kframe == 8 ? pick_frame<8>(thick, cls) : pick_frame<9>(thick, cls);
+// simulate stage alone, by register-cache variant, with or without the camera stage compiled in (without: fewer
+// registers, half the code)
+static step_kern_t env_kernel_of(int kv, bool cam, unsigned feat) {
+  return lift([](auto k, auto c, auto ft) -> step_kern_t { return tc_env_kernel<k, c, ft>; }, Kvars{kv}, Bools{cam}, Feats{feat});
 }
-static frame_kern_t recover_kernel_of(int kframe, bool thick, bool cls) {
-  return kframe == 516 ? pick_recover<5, 16>(thick, cls) : kframe == 5 ? pick_recover<5>(thick, cls) : kframe == 8 ? pick_recover<8>(thick, cls) : pick_recover<9>(thick, cls);
+static step_kern_t envg_kernel_of(unsigned feat) {
+  return lift([](auto ft) -> step_kern_t { return tc_envg_kernel<ft>; }, Feats{feat});
+}
+// recover: tc_frame_recover_kernel, the pass behind a streamed call's frame launch
+static frame_kern_t frame_kernel_of(int kcode, bool thick, int fmt, bool recover) {
+  return lift(
+      [](auto kc, auto t, auto f, auto rec) -> frame_kern_t {
+        if constexpr (rec) return tc_frame_recover_kernel<FrameKRb<kc>::K, t, f, FrameKRb<kc>::RB>;
+        else return tc_frame_kernel<FrameKRb<kc>::K, t, f, FrameKRb<kc>::RB>;
+      },
+      Kcodes{kcode}, Thicks{thick}, Fmts{fmt}, Bools{recover});
+}
+static raster_kern_t raster_kernel_of(bool thick, int fmt) {
+  return lift([](auto t, auto f) -> raster_kern_t { return tc_raster_kernel<t, f>; }, Thicks{thick}, Fmts{fmt});
 }
 
 // =============================================================================================
@@ -4123,41 +4102,31 @@ extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const 
   {
     int lds = L.total > e->r_lds ? L.total : e->r_lds;
     if (e->frame_lds > lds) lds = e->frame_lds;
-    if (lds > 48 * 1024) {
-      for (int t = 0; t < 2; t++)
-        for (int c = 0; c < 4; c++) {  // (c & 2: the per-env-car instantiation)
-          for (int ep = 0; ep < 2; ep++) {  // (and the ones with the episode accounting)
-            (void)hipFuncSetAttribute((const void*)pick_fused<5>(t, c & 1, c & 2, ep), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)hipFuncSetAttribute((const void*)pick_fused<5, 16>(t, c & 1, c & 2, ep), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)hipFuncSetAttribute((const void*)pick_fused<8>(t, c & 1, c & 2, ep), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)hipFuncSetAttribute((const void*)pick_fused<9>(t, c & 1, c & 2, ep), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (lds > 48 * 1024)  // every tc_step_kernel and tc_frame_kernel variant
+      for (int kcode : {516, 5, 8, 9})
+        for (int t = 0; t < 2; t++)
+          for (int fmt : {TC_FMT_CLASSES, TC_FMT_RGB}) {
+            for (unsigned feat = 0; feat <= TC_FEAT_ALL; feat++)
+              (void)hipFuncSetAttribute((const void*)step_kernel_of(kcode, t, fmt, feat), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            (void)hipFuncSetAttribute((const void*)frame_kernel_of(kcode, t, fmt, false), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
           }
-          (void)hipFuncSetAttribute((const void*)pick_frame<5>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-          (void)hipFuncSetAttribute((const void*)pick_frame<5, 16>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-          (void)hipFuncSetAttribute((const void*)pick_frame<8>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-          (void)hipFuncSetAttribute((const void*)pick_frame<9>(t, c), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        }
-    }
   }
   {  // tc_envg_kernel's LDS copies of the map (edge records + fat lanepath nodes, see launch()) can exceed the 48 KB default
     const size_t envg_lds = ((size_t)m.total_edges * 48 + 15) / 16 * 16 + (size_t)m.lpN * sizeof(LpNode);
     if (envg_lds > 40 * 1024)
-      for (const void* g : {(const void*)tc_envg_kernel, (const void*)tc_envg_kernel_car, (const void*)tc_envg_kernel_ep,
-                            (const void*)tc_envg_kernel_ep_car})
-        (void)hipFuncSetAttribute(g, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(envg_lds < 150 * 1024 ? envg_lds : 150 * 1024));
+      for (unsigned feat = 0; feat <= TC_FEAT_ALL; feat++)
+        (void)hipFuncSetAttribute((const void*)envg_kernel_of(feat), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(envg_lds < 150 * 1024 ? envg_lds : 150 * 1024));
   }
-#ifndef TC_DEV_FAST
-  if (e->r_lds > 48 * 1024) {
-    (void)hipFuncSetAttribute((const void*)tc_raster_kernel<true, TC_FMT_CLASSES>, hipFuncAttributeMaxDynamicSharedMemorySize, e->r_lds);
-    (void)hipFuncSetAttribute((const void*)tc_raster_kernel<true, TC_FMT_RGB>, hipFuncAttributeMaxDynamicSharedMemorySize, e->r_lds);
-    (void)hipFuncSetAttribute((const void*)tc_raster_kernel<false, TC_FMT_CLASSES>, hipFuncAttributeMaxDynamicSharedMemorySize, e->r_lds);
-    (void)hipFuncSetAttribute((const void*)tc_raster_kernel<false, TC_FMT_RGB>, hipFuncAttributeMaxDynamicSharedMemorySize, e->r_lds);
-  }
+  if (e->r_lds > 48 * 1024)
+    for (int t = 0; t < 2; t++)
+      for (int fmt : {TC_FMT_CLASSES, TC_FMT_RGB})
+        (void)hipFuncSetAttribute((const void*)raster_kernel_of(t, fmt), hipFuncAttributeMaxDynamicSharedMemorySize, e->r_lds);
   if (L.total > 48 * 1024) {
     hipError_t he = hipSuccess;
     static const int kvs[4] = {5, 8, 9, 13};
-    for (int i = 0; i < 32 && he == hipSuccess; i++)  // every tc_env_kernel / _car / _ep / _ep_car variant
-      he = hipFuncSetAttribute((const void*)pick_env(kvs[i & 3], (i & 4) == 0, (i & 8) != 0, (i & 16) != 0),
+    for (int i = 0; i < 32 && he == hipSuccess; i++)  // every tc_env_kernel variant
+      he = hipFuncSetAttribute((const void*)env_kernel_of(kvs[i & 3], (i & 4) == 0, (unsigned)i >> 3),
                                hipFuncAttributeMaxDynamicSharedMemorySize, L.total);
     if (he != hipSuccess) {
       set_err(std::string("hipFuncSetAttribute: ") + hipGetErrorString(he));
@@ -4165,7 +4134,6 @@ extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const 
       return TC_E_HIP;
     }
   }
-#endif
   e->obs_bytes = (int64_t)dc.H * dc.W * (dc.format == TC_FMT_CLASSES ? m.C : 3);
   e->k.seg_cap = m.total_edges > 0 ? m.total_edges : 1;
   {
@@ -4731,14 +4699,7 @@ static int launch_raster(tc_env* e, const int* seg_g, const int* seg_n, int seg_
 #endif
   RArgs r = make_rargs(e, seg_g, seg_n, seg_cap, mask, flags, env0, obs, with_noise);
   if (count < 0) count = e->k.N;
-#ifdef TC_DEV_FAST
-  auto kern = tc_raster_kernel<true, TC_DEV_FMTV>;
-#else
-  const bool thick = r.cam.thickness > 1, cls = r.cam.format == TC_FMT_CLASSES;
-  auto kern = thick ? (cls ? tc_raster_kernel<true, TC_FMT_CLASSES> : tc_raster_kernel<true, TC_FMT_RGB>)
-                    : (cls ? tc_raster_kernel<false, TC_FMT_CLASSES> : tc_raster_kernel<false, TC_FMT_RGB>);
-#endif
-  hipLaunchKernelGGL(kern, dim3(count), dim3(TC_NT), e->r_lds, (hipStream_t)stream, r);
+  hipLaunchKernelGGL(raster_kernel_of(r.cam.thickness > 1, r.cam.format), dim3(count), dim3(TC_NT), e->r_lds, (hipStream_t)stream, r);
   HIP_TRY(hipGetLastError());
   return TC_OK;
 }
@@ -4752,23 +4713,44 @@ static int noise_advance(tc_env* e, int mode, bool rendered, int nsteps, void* s
   return TC_OK;
 }
 
-// steps per simulate / frame dispatch of a K-step call that renders (see launch()): TC_CHUNK (16), or a quarter of the
-// call when that is less, so that a short call (the 20 steps of a smoke benchmark) still has several chunks in flight;
-// never more than a ring slot holds.  Calls that are not pipelined run in chunks as large as the ring allows.
-static int chunk_steps(const tc_env* e, int nsteps, bool frames, bool all) {
-  const bool can_pipe = frames && e->env_grouped && e->pipe && all && nsteps > 1;
-  int c = nsteps;
-  if (can_pipe) {
-    const int q = (nsteps + 3) / 4;
-    c = e->chunk < q ? e->chunk : (q < 2 ? 2 : q);
+// Which way a call of nsteps steps goes through launch() on this handle: decided here for launch(), which branches on
+// it, and for tc_env_launch_info, which reports it.  obs: there is a tensor to draw into (the bound one or the rollout's);
+// all: every step's frame is wanted (a rollout with observations), else only the last one survives.
+struct CallPlan {
+  bool do_raster;  // frames are drawn at all
+  bool fused;      // one tc_step_kernel launch: simulate + raster by the same wavefront
+  bool split;      // K steps with frames: per chunk ONE simulate launch over its steps and ONE launch over the frames wanted
+                   // (neither: one tc_env_kernel launch, and a tc_raster_kernel launch behind it when frames are drawn)
+  bool frames;     // split: camera + raster per frame (tc_frame_kernel); else camera in the simulate launch (the
+                   // register-hungry K = 13 stage, TC_FUSE=0) and a raster launch
+  bool piped;      // split: the frames of a chunk are produced on an internal stream, beside the next simulate launch
+  bool streamed;   // piped: the whole call (or st_rows steps of it) is one simulate launch and one gated frame launch
+  int steps;       // steps per simulate / frame dispatch
+};
+static CallPlan plan_call(const tc_env* e, uint32_t flags, int nsteps, bool obs, bool all) {
+  CallPlan p;
+  // (the register-hungry K = 13 simulate stage spills when fused, so it stays two launches)
+  const bool can_fuse = e->fuse && e->kvar != 13;
+  p.do_raster = !(flags & (TC_F_NO_OBSERVATION | DBG_SKIP_CAMERA)) && obs;
+  p.split = p.do_raster && nsteps > 1 && (e->multi_split || !can_fuse);
+  p.fused = p.do_raster && can_fuse && !p.split;
+  p.frames = p.split && can_fuse;
+  p.piped = p.frames && e->env_grouped && e->pipe && all;
+  p.streamed = p.piped && e->stream && e->st_rows >= 2 && e->st_words;
+  p.steps = nsteps;
+  if (p.streamed) {
+    if (p.steps > e->st_rows) p.steps = e->st_rows;
+  } else if (!p.fused) {
+    // a chunk of a pipelined call: TC_CHUNK (16) steps, or a quarter of the call when that is less, so that a short call
+    // (the 20 steps of a smoke benchmark) still has several chunks in flight; never more than a ring slot holds.  Calls
+    // that are not pipelined run in chunks as large as the ring allows.
+    if (p.piped) {
+      const int q = (nsteps + 3) / 4;
+      p.steps = e->chunk < q ? e->chunk : (q < 2 ? 2 : q);
+    }
+    if (e->ring_rows > 0 && p.steps > e->ring_rows) p.steps = e->ring_rows;
   }
-  if (e->ring_rows > 0 && c > e->ring_rows) c = e->ring_rows;
-  return c;
-}
-
-static bool fused_path(const tc_env* e, uint32_t flags) {
-  const bool do_raster = !(flags & (TC_F_NO_OBSERVATION | DBG_SKIP_CAMERA)) && e->k.b.obs;
-  return do_raster && e->fuse && e->kvar != 13;
+  return p;
 }
 
 #define TC_STREAM_MAX_ROWS 128
@@ -4859,6 +4841,92 @@ extern "C" int tc_env_reserve_steps(tc_env* e, int32_t max_call_steps) {
   return TC_OK;
 }
 
+// a rollout from [step][env] row r0 on
+static tc_rollout rollout_at(const tc_rollout& r, size_t r0, size_t obs_bytes, size_t C) {
+  auto at = [r0](auto* p, size_t per_row) { return p ? p + r0 * per_row : p; };
+  tc_rollout q;
+  q.obs = at(r.obs, obs_bytes);
+  q.reward = at(r.reward, 1);
+  q.terminated = at(r.terminated, 1);
+  q.truncated = at(r.truncated, 1);
+  q.cte = at(r.cte, 1);
+  q.heading_error = at(r.heading_error, 1);
+  q.status = at(r.status, 1);
+  q.x = at(r.x, 1);
+  q.y = at(r.y, 1);
+  q.theta = at(r.theta, 1);
+  q.velocity = at(r.velocity, 1);
+  q.laneline_distances = at(r.laneline_distances, C);
+  q.nearest_edge = at(r.nearest_edge, C);
+  q.local_path = at(r.local_path, 8);
+  q.lp_len = at(r.lp_len, 1);
+  return q;
+}
+
+// What a simulate launch is given of the CALL, for the launch whose first step is step c0 of it: the handle's arguments
+// and feature rows, mode / dtype / flags, and the control, maneuver, rollout and episode rows from [step][env] row c0 * N
+// on.  What belongs to the path is left to the caller: ma.nsteps and the members of ma behind it, the scratch a.seg_g /
+// a.seg_n point to, r, env_order.
+static StepArgs step_args_at(const tc_env* e, int mode, const void* cc, int cdtype, const int32_t* man, const int32_t* spawn,
+                             const uint8_t* mask, uint32_t flags, const tc_rollout* roll, bool ep_rows, int c0) {
+  const size_t r0 = (size_t)c0 * e->k.N;
+  StepArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.a = e->k;
+  sa.a.env0 = 0;
+  sa.cr = e->cr;
+  sa.ep = e->ep;  // (the per-step rows belong to K-step calls only)
+  sa.ep.len_rows = ep_rows && e->ep.len_rows ? e->ep.len_rows + r0 : nullptr;
+  sa.ep.ret_rows = ep_rows && e->ep.ret_rows ? e->ep.ret_rows + r0 : nullptr;
+  if (roll) sa.ma.roll = rollout_at(*roll, r0, (size_t)e->obs_bytes, (size_t)e->k.m.C);
+  sa.mode = mode;
+  sa.cdtype = cdtype;
+  sa.flags = flags;
+  sa.car_control = (const char*)cc + r0 * 2 * (cdtype == TC_F32 ? 4 : 8);
+  sa.maneuver = man + r0;
+  sa.spawn_nodes = spawn;
+  sa.mask = mask;
+  return sa;
+}
+
+// The argument block of a frame launch over scratch rows: of the streamed form (gated: see launch()) or of the ring.
+// `gate` and `order` are the launch's own.
+static FrameArgs frame_args_of(const tc_env* e, uint32_t flags, const RArgs& r, bool streamed) {
+  FrameArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.a = e->k;
+  fa.a.dbg = flags;
+  fa.a.env0 = 0;
+  fa.a.seg_g = streamed ? e->st_segm_g : e->segm_g;
+  fa.a.seg_n = streamed ? e->st_segm_n : e->segm_n;
+  fa.r = r;
+  fa.pose_rows = streamed ? e->st_pose : e->pose_rows;
+  fa.a.seg_lds_off = fa.r.seg_lds_off = e->seg_lds_off;
+  fa.a.seg_lds_cap = fa.r.seg_lds_cap = e->frame_seg_cap;
+  if (streamed) {
+    fa.abort_word = e->st_words + 1;
+    fa.resident = e->st_words;
+    fa.gate_ticks = e->gate_ticks;
+    fa.gate_test = e->gate_test;
+  }
+  return fa;
+}
+
+// The grouped simulate launch (tc_envg_kernel: 32 envs per workgroup) of the steps `sa` describes.
+static unsigned int envg_grid(int N) { return (unsigned int)((N + TC_ENVG_NT / TC_EL - 1) / (TC_ENVG_NT / TC_EL)); }
+static int launch_envg(const tc_env* e, unsigned feat, StepArgs& sa, hipStream_t stream) {
+  // LDS copies of the lane-line edge records (48 B per edge) and of the lanepath's fat node records (96 B per node):
+  // simple_layout 12.4 + 17.5 KB, knuffingen 34.6 + 40.2 KB per workgroup of 32 envs (a CU holds one or two such
+  // workgroups: 128 of them cover 4096 envs)
+  const size_t map_bytes = ((size_t)e->k.m.total_edges * 48 + 15) / 16 * 16, fat_bytes = (size_t)e->k.m.lpN * sizeof(LpNode);
+  sa.ma.map_lds = (e->envg_map_lds && map_bytes <= 40 * 1024) ? 1 : 0;
+  sa.ma.fat_lds = (e->envg_map_lds && fat_bytes <= 56 * 1024) ? 1 : 0;
+  hipLaunchKernelGGL(envg_kernel_of(feat), dim3(envg_grid(e->k.N)), dim3(TC_ENVG_NT),
+                     (sa.ma.map_lds ? map_bytes : 0) + (sa.ma.fat_lds ? fat_bytes : 0), stream, sa);
+  HIP_TRY(hipGetLastError());
+  return TC_OK;
+}
+
 static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t* man, const int32_t* spawn,
                   const uint8_t* mask, uint32_t flags, void* stream, int nsteps = 1, const tc_rollout* roll = nullptr,
                   bool ep_rows = false) {
@@ -4884,30 +4952,18 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
   const bool prof = e->prof > 0 && mode == MODE_STEP && (e->prof_calls++ % e->prof) == 0;
   const int slot = e->prof_n % TC_PROF_RING;
   const int kv = e->kvar;
-  // simulate stage alone, with or without the camera stage compiled in (without: fewer registers, half the code)
-  // per-env cars (tc_env_set_car_per_env): the *_car instantiations of the simulate stages, the same launches otherwise
-  const bool per = e->cr.rows != nullptr;
-  // episodes (tc_env_set_episodes): the *_ep instantiations, likewise; the per-step rows belong to K-step calls only
-  const bool epk = e->ep.length != nullptr && mode != MODE_RENDER;
-  EpArgs ep0 = e->ep;
-  if (!ep_rows) ep0.len_rows = nullptr, ep0.ret_rows = nullptr;
-  auto ep_at = [&](size_t r0) {  // the launch whose first step is row r0 / N of the call
-    EpArgs q = ep0;
-    if (q.len_rows) q.len_rows += r0;
-    if (q.ret_rows) q.ret_rows += r0;
-    return q;
-  };
-  auto kern = pick_env(kv, true, per, epk);
-  auto kern_nocam = pick_env(kv, false, per, epk);
-  auto envg = epk ? (per ? tc_envg_kernel_ep_car : tc_envg_kernel_ep) : (per ? tc_envg_kernel_car : tc_envg_kernel);
-  const bool do_raster = !(flags & (TC_F_NO_OBSERVATION | DBG_SKIP_CAMERA)) && (e->k.b.obs || (roll && roll->obs));
+  // per-env cars (tc_env_set_car_per_env) and episodes (tc_env_set_episodes): the instantiations of the simulate stages
+  // with those bits, the same launches otherwise
+  const unsigned feat = (e->cr.rows ? TC_FEAT_CAR : 0u) | (e->ep.length && mode != MODE_RENDER ? TC_FEAT_EP : 0u);
+  const bool all = roll && roll->obs;  // with a rollout every step's frame is wanted; else only the last survives
+  const CallPlan plan = plan_call(e, flags, nsteps, e->k.b.obs || all, all);
+  const bool do_raster = plan.do_raster;
+  const bool thick = e->k.cam.thickness > 1;
+  const int fmt = e->k.cam.format;
   const int N = e->k.N;
-  MultiArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  ma.nsteps = nsteps;
-  if (roll) ma.roll = *roll;
+  auto args_at = [&](int c0) { return step_args_at(e, mode, cc, cdtype, man, spawn, mask, flags, roll, ep_rows, c0); };
   hipStream_t main = (hipStream_t)stream;
-  if (do_raster && nsteps > 1 && (e->multi_split || !e->fuse || kv == 13)) {
+  if (plan.split) {
     // K steps, split form: per chunk ONE simulate launch over its steps and ONE launch over the frames wanted.  The pose
     // rows / draw lists of a chunk live in slot (chunk index mod TC_RING_SLOTS) of the scratch ring.
     if (e->ring_rows < 1) {
@@ -4918,8 +4974,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     if (prof) HIP_TRY(hipEventRecord(e->ev[0][slot], main));
     // one stream at a time per handle: a call on another stream than the previous K-step call waits for that call
     if (e->have_call && e->last_stream != main) HIP_TRY(hipStreamWaitEvent(main, e->call_ev, 0));
-    const bool frames = e->fuse && kv != 13;  // camera + raster per frame (tc_frame_kernel); else camera in the simulate
-                                              // launch (the register-hungry K = 13 stage, TC_FUSE=0) and a raster launch
+    const bool frames = plan.frames;
     // Pipelining inside the call.  The steps are issued in chunks: the simulate launch of chunk c+1 runs on the caller's
     // stream while the frames of chunk c are produced on an internal stream (joined back before the call's work ends
     // on the caller's stream, so the caller still sees everything complete in stream order).  The two kernels suit
@@ -4927,9 +4982,8 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     // for 4096 envs), so the second hides in the first's shadow instead of adding its 21 us per step.
     // (Measured and dropped, DESIGN.md section 4: chunk sizes ramping up 1, 2, 4, ...; a short or half first chunk; other
     // divisors than 4 for short calls.)
-    const bool all = roll && roll->obs;  // with a rollout every step's frame is wanted; else only the last survives
-    const bool piped = frames && e->env_grouped && e->pipe && all && nsteps > 1;
-    const int chunk = chunk_steps(e, nsteps, frames, all);
+    const bool piped = plan.piped;
+    const int chunk = plan.steps;
     hipStream_t fs = piped ? e->frame_stream : main;
     // Short calls (chunks of fewer than 8 steps): a frame launch of 5 x N workgroups spends a good part of its life
     // ramping up and draining (5 rows: 34.6 us per row alone, 16 rows: 30.8), and a 20-step call is four of them.  There
@@ -4938,15 +4992,10 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     // 66.2 -> 58.3 us per step, 20-step call 46.9 -> 44.0; with chunks of 10 steps it costs 7 %, so longer calls keep one
     // stream and their frame launches follow one another, as a kernel trace of the default command shows them).
     const bool two_fs = piped && e->frame_streams == 2 && chunk < 8;
-    const size_t esz = cdtype == TC_F32 ? 4 : 8;
-    const bool thick = e->k.cam.thickness > 1, cls = e->k.cam.format == TC_FMT_CLASSES;
-    (void)thick;
-    (void)cls;
     bool first_frames = true;
     bool used_fs[2] = {false, false};
     e->draw_n = 0;
     e->draw_base = e->segm_n;
-    const int C = e->k.m.C;
     // Streamed form (default when every step's frame is wanted).  The chunked pipeline below pays for its structure: the
     // first chunk's simulate launch overlaps with nothing, and every frame dispatch ends in a tail with the chip half empty
     // -- a quarter of a 20-step call.  Here the whole call (or a segment of st_rows steps) is ONE simulate launch on the
@@ -4957,67 +5006,27 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     //                 (wait: simulate launch done) [tc_frame_recover_kernel: whatever a gate-1 workgroup gave up on]
     // Every wait on the device is bounded (gate_ticks), and what a bound cuts short the recover pass completes: the
     // result never depends on how the two launches were scheduled.
-    const bool streamed = piped && e->stream && e->st_rows >= 2 && e->st_words;
+    const bool streamed = plan.streamed;
     if (streamed) {
       e->draw_base = e->st_segm_n;
-      const int seg_steps = e->st_rows;
       int si = 0;
       for (int c0 = 0, cn = 0; c0 < nsteps; c0 += cn, si++) {
-        cn = nsteps - c0 < seg_steps ? nsteps - c0 : seg_steps;
-        const size_t r0 = (size_t)c0 * N;
+        cn = nsteps - c0 < plan.steps ? nsteps - c0 : plan.steps;
         // a later segment reuses the scratch rows: the frames of the one before must be drawn (and its rows cleared)
         if (si > 0) HIP_TRY(hipStreamWaitEvent(main, e->slot_ev[0], 0));
         HIP_TRY(hipEventRecord(e->start_ev, main));
-        StepArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.a = e->k;
-        sa.cr = e->cr;
-        sa.ep = ep_at(r0);
-        sa.a.env0 = 0;
+        StepArgs sa = args_at(c0);
         sa.a.seg_g = e->st_segm_g;
         sa.a.seg_n = e->st_segm_n;
-        sa.ma = ma;
         sa.ma.nsteps = cn;
         sa.ma.seg_rows = cn > 1 ? cn : 2;
-        sa.ma.cam_here = 0;
         sa.ma.pose_rows = e->st_pose;
         sa.ma.resident = e->st_words;
-        if (roll) {
-          tc_rollout& q = sa.ma.roll;
-          q.obs = roll->obs + r0 * (size_t)e->obs_bytes;
-          q.reward = roll->reward ? roll->reward + r0 : nullptr;
-          q.terminated = roll->terminated ? roll->terminated + r0 : nullptr;
-          q.truncated = roll->truncated ? roll->truncated + r0 : nullptr;
-          q.cte = roll->cte ? roll->cte + r0 : nullptr;
-          q.heading_error = roll->heading_error ? roll->heading_error + r0 : nullptr;
-          q.status = roll->status ? roll->status + r0 : nullptr;
-          q.x = roll->x ? roll->x + r0 : nullptr;
-          q.y = roll->y ? roll->y + r0 : nullptr;
-          q.theta = roll->theta ? roll->theta + r0 : nullptr;
-          q.velocity = roll->velocity ? roll->velocity + r0 : nullptr;
-          q.laneline_distances = roll->laneline_distances ? roll->laneline_distances + r0 * C : nullptr;
-          q.nearest_edge = roll->nearest_edge ? roll->nearest_edge + r0 * C : nullptr;
-          q.local_path = roll->local_path ? roll->local_path + r0 * 8 : nullptr;
-          q.lp_len = roll->lp_len ? roll->lp_len + r0 : nullptr;
-        }
-        sa.mode = mode;
-        sa.cdtype = cdtype;
-        sa.flags = flags;
-        sa.car_control = (const char*)cc + r0 * 2 * esz;
-        sa.maneuver = man + r0;
-        sa.spawn_nodes = spawn;
-        sa.mask = mask;
-        const size_t map_bytes = ((size_t)e->k.m.total_edges * 48 + 15) / 16 * 16, fat_bytes = (size_t)e->k.m.lpN * sizeof(LpNode);
-        sa.ma.map_lds = (e->envg_map_lds && map_bytes <= 40 * 1024) ? 1 : 0;
-        sa.ma.fat_lds = (e->envg_map_lds && fat_bytes <= 56 * 1024) ? 1 : 0;
-        const unsigned int sim_wgs = (unsigned int)((N + TC_ENVG_NT / TC_EL - 1) / (TC_ENVG_NT / TC_EL));
-        hipLaunchKernelGGL(envg, dim3(sim_wgs), dim3(TC_ENVG_NT), (sa.ma.map_lds ? map_bytes : 0) + (sa.ma.fat_lds ? fat_bytes : 0),
-                           main, sa);
-        HIP_TRY(hipGetLastError());
+        int rc = launch_envg(e, feat, sa, main);
+        if (rc != TC_OK) return rc;
         if (prof && c0 + cn >= nsteps) HIP_TRY(hipEventRecord(e->ev[1][slot], main));
         HIP_TRY(hipEventRecord(e->sim_ev, main));
         // ---- the frame stream
-        hipStream_t fs = e->frame_stream;
         // heaviest frames first, by the last row of the call before (see the chunked form below).  Depends on nothing but
         // this stream's own past, so it runs while the simulate launch starts
         if (e->frame_order[0] && e->cost_row[0]) {
@@ -5026,42 +5035,25 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
           e->frame_order_valid[0] = true;
         }
         HIP_TRY(hipStreamWaitEvent(fs, e->start_ev, 0));
-        RArgs r = make_rargs(e, e->st_segm_g, e->st_segm_n, e->k.seg_cap, nullptr, flags, 0, roll->obs + r0 * (size_t)e->obs_bytes,
-                             mode == MODE_STEP);
+        RArgs r = make_rargs(e, e->st_segm_g, e->st_segm_n, e->k.seg_cap, nullptr, flags, 0, sa.ma.roll.obs, mode == MODE_STEP);
         r.seg_row0 = 0;
         r.noise_row0 = c0;
         r.obs_row_stride = (long long)N * (long long)e->obs_bytes;
-        FrameArgs fa;
-        memset(&fa, 0, sizeof(fa));
-        fa.a = e->k;
-        fa.a.dbg = flags;
-        fa.a.env0 = 0;
-        fa.a.seg_g = e->st_segm_g;
-        fa.a.seg_n = e->st_segm_n;
-        fa.r = r;
-        fa.pose_rows = e->st_pose;
-        fa.a.seg_lds_off = fa.r.seg_lds_off = e->seg_lds_off;
-        fa.a.seg_lds_cap = fa.r.seg_lds_cap = e->frame_seg_cap;
-        fa.abort_word = e->st_words + 1;
-        fa.resident = e->st_words;
-        fa.gate_ticks = e->gate_ticks;
-        fa.gate_test = e->gate_test;
+        FrameArgs fa = frame_args_of(e, flags, r, true);
         if (e->frame_order[0] && e->frame_order_valid[0]) fa.order = e->frame_order[0];
         // (ten times the patience of a frame workgroup: one idle wavefront costs nothing, and when another env's frame
         // launch has the chip -- two handles stepping on one GPU -- the simulate workgroups only get on as that launch drains)
-        hipLaunchKernelGGL(tc_gate_kernel, dim3(1), dim3(64), 0, fs, (const unsigned int*)e->st_words, sim_wgs, 10 * e->gate_ticks);
+        hipLaunchKernelGGL(tc_gate_kernel, dim3(1), dim3(64), 0, fs, (const unsigned int*)e->st_words, envg_grid(N), 10 * e->gate_ticks);
         HIP_TRY(hipGetLastError());
         if (prof && si == 0) HIP_TRY(hipEventRecord(e->ev[3][slot], fs));
-        frame_kern_t fk = frame_kernel_of(e->kframe, thick, cls);
         fa.gate = 1;
-        hipLaunchKernelGGL(fk, dim3(N, cn), dim3(TC_NT), e->frame_lds, fs, fa);
+        hipLaunchKernelGGL(frame_kernel_of(e->kframe, thick, fmt, false), dim3(N, cn), dim3(TC_NT), e->frame_lds, fs, fa);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamWaitEvent(fs, e->sim_ev, 0));
         fa.gate = 2;
         fa.recover_rows = cn;
         fa.order = nullptr;
-        frame_kern_t rk = recover_kernel_of(e->kframe, thick, cls);
-        hipLaunchKernelGGL(rk, dim3(N), dim3(TC_NT), e->frame_lds, fs, fa);
+        hipLaunchKernelGGL(frame_kernel_of(e->kframe, thick, fmt, true), dim3(N), dim3(TC_NT), e->frame_lds, fs, fa);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(e->slot_ev[0], fs));
         if (e->frame_order[0]) e->cost_row[0] = e->st_segm_n + (size_t)(cn - 1) * N;
@@ -5075,66 +5067,28 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     int ci = 0;
     for (int c0 = 0, cn = 0; !streamed && c0 < nsteps; c0 += cn, ci++) {
       cn = nsteps - c0 < chunk ? nsteps - c0 : chunk;
-      const size_t r0 = (size_t)c0 * N;                 // first [step][env] row of this chunk in the caller's arrays
       const int rslot = ci % TC_RING_SLOTS;
       const size_t rb = (size_t)rslot * e->ring_rows;   // first row of this chunk in the scratch ring
       // the frames that read this ring slot TC_RING_SLOTS chunks ago must be done before it is rewritten
       if (piped && ci >= TC_RING_SLOTS) HIP_TRY(hipStreamWaitEvent(main, e->slot_ev[rslot], 0));
-      StepArgs sa;
-      memset(&sa, 0, sizeof(sa));
-      sa.a = e->k;
-      sa.cr = e->cr;
-      sa.ep = ep_at(r0);
-      sa.a.env0 = 0;
+      StepArgs sa = args_at(c0);
       sa.a.seg_g = e->segm_g + rb * N * e->k.seg_cap * 5;
       sa.a.seg_n = e->segm_n + rb * N;
-      sa.ma = ma;
       sa.ma.nsteps = cn;
       sa.ma.seg_rows = cn > 1 ? cn : 2;  // (> 1: row k of the chunk's lists; a one-step chunk still writes row 0 of them)
       sa.ma.cam_here = frames ? 0 : 1;
       sa.ma.pose_rows = frames ? e->pose_rows + rb * N * TC_POSE_ROW : nullptr;
-      if (roll) {
-        tc_rollout& q = sa.ma.roll;
-        q.obs = roll->obs ? roll->obs + r0 * (size_t)e->obs_bytes : nullptr;
-        q.reward = roll->reward ? roll->reward + r0 : nullptr;
-        q.terminated = roll->terminated ? roll->terminated + r0 : nullptr;
-        q.truncated = roll->truncated ? roll->truncated + r0 : nullptr;
-        q.cte = roll->cte ? roll->cte + r0 : nullptr;
-        q.heading_error = roll->heading_error ? roll->heading_error + r0 : nullptr;
-        q.status = roll->status ? roll->status + r0 : nullptr;
-        q.x = roll->x ? roll->x + r0 : nullptr;
-        q.y = roll->y ? roll->y + r0 : nullptr;
-        q.theta = roll->theta ? roll->theta + r0 : nullptr;
-        q.velocity = roll->velocity ? roll->velocity + r0 : nullptr;
-        q.laneline_distances = roll->laneline_distances ? roll->laneline_distances + r0 * C : nullptr;
-        q.nearest_edge = roll->nearest_edge ? roll->nearest_edge + r0 * C : nullptr;
-        q.local_path = roll->local_path ? roll->local_path + r0 * 8 : nullptr;
-        q.lp_len = roll->lp_len ? roll->lp_len + r0 : nullptr;
-      }
-      sa.mode = mode;
-      sa.cdtype = cdtype;
-      sa.flags = flags;
-      sa.car_control = (const char*)cc + r0 * 2 * esz;
-      sa.maneuver = man + r0;
-      sa.spawn_nodes = spawn;
-      sa.mask = mask;
       // The first chunk's simulate launch overlaps with nothing, so it should be SHORT rather than cheap: it goes through
       // the one-wavefront-per-env kernel (4096 wavefronts, bound by throughput: ~15 us per step) instead of the grouped
       // one (512 wavefronts, a latency chain: 13-23 us per step).  20-step call 48.4 -> 47.2 us per step, 128-step calls
       // 38.2 -> 37.6.  Both kernels read and leave the env's state in the caller's buffers, bit for bit the same.
       if (frames && e->env_grouped && !(e->first_per_env && c0 == 0 && piped && nsteps > chunk)) {  // (a one-chunk call: grouped)
-        // LDS copies of the lane-line edge records (48 B per edge) and of the lanepath's fat node records (96 B per node):
-        // simple_layout 12.4 + 17.5 KB, knuffingen 34.6 + 40.2 KB per workgroup of 32 envs (a CU holds one or two such
-        // workgroups: 128 of them cover 4096 envs)
-        const size_t map_bytes = ((size_t)e->k.m.total_edges * 48 + 15) / 16 * 16, fat_bytes = (size_t)e->k.m.lpN * sizeof(LpNode);
-        sa.ma.map_lds = (e->envg_map_lds && map_bytes <= 40 * 1024) ? 1 : 0;
-        sa.ma.fat_lds = (e->envg_map_lds && fat_bytes <= 56 * 1024) ? 1 : 0;
-        hipLaunchKernelGGL(envg, dim3((N + TC_ENVG_NT / TC_EL - 1) / (TC_ENVG_NT / TC_EL)), dim3(TC_ENVG_NT),
-                           (sa.ma.map_lds ? map_bytes : 0) + (sa.ma.fat_lds ? fat_bytes : 0), main, sa);
+        int rc = launch_envg(e, feat, sa, main);
+        if (rc != TC_OK) return rc;
+      } else {
+        hipLaunchKernelGGL(env_kernel_of(kv, !frames, feat), dim3(N), dim3(TC_NT), e->k.lds.total, main, sa);
+        HIP_TRY(hipGetLastError());
       }
-      else
-        hipLaunchKernelGGL(frames ? kern_nocam : kern, dim3(N), dim3(TC_NT), e->k.lds.total, main, sa);
-      HIP_TRY(hipGetLastError());
       const bool last_chunk = c0 + cn >= nsteps;
       if (prof && last_chunk) HIP_TRY(hipEventRecord(e->ev[1][slot], main));
       if (!all && !last_chunk) continue;  // only the last step's frame is wanted
@@ -5146,26 +5100,14 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
       }
       if (prof && first_frames && piped) HIP_TRY(hipEventRecord(e->ev[3][slot], fs));
       first_frames = false;
-      RArgs r = make_rargs(e, e->segm_g, e->segm_n, e->k.seg_cap, nullptr, flags, 0, all ? roll->obs + r0 * (size_t)e->obs_bytes : nullptr,
-                           mode == MODE_STEP);
+      RArgs r = make_rargs(e, e->segm_g, e->segm_n, e->k.seg_cap, nullptr, flags, 0, all ? sa.ma.roll.obs : nullptr, mode == MODE_STEP);
       // scratch row of the first frame drawn / its step index in the call (position in the blob stream)
       r.seg_row0 = (int)rb + (all ? 0 : cn - 1);
       r.noise_row0 = all ? c0 : nsteps - 1;
       r.obs_row_stride = all ? (long long)N * (long long)e->obs_bytes : 0;
       const int rows = all ? cn : 1;  // (<= ring_rows <= 16: one grid)
       if (frames) {
-        FrameArgs fa;
-        memset(&fa, 0, sizeof(fa));
-        fa.a = e->k;
-        fa.a.dbg = flags;
-        fa.a.env0 = 0;
-        fa.a.seg_g = e->segm_g;
-        fa.a.seg_n = e->segm_n;
-        fa.r = r;
-        fa.pose_rows = e->pose_rows;
-        frame_kern_t fk = frame_kernel_of(e->kframe, thick, cls);
-        fa.a.seg_lds_off = fa.r.seg_lds_off = e->seg_lds_off;
-        fa.a.seg_lds_cap = fa.r.seg_lds_cap = e->frame_seg_cap;
+        FrameArgs fa = frame_args_of(e, flags, r, false);
         // Heaviest frames first.  A dispatch ends with a tail -- the chip half empty while the last workgroups finish, ~36 us
         // of a 16-step dispatch, a fifth of a 5-step one -- and the dispatcher hands workgroups out in index order, so the
         // envs are sorted by the draw-list lengths of the last frame row drawn on this stream (tc_order_kernel with one
@@ -5179,16 +5121,10 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
           e->frame_order_valid[fsi] = true;
         }
         if (e->frame_order[fsi] && e->frame_order_valid[fsi]) fa.order = e->frame_order[fsi];
-        hipLaunchKernelGGL(fk, dim3(N, rows), dim3(TC_NT), e->frame_lds, fs, fa);
+        hipLaunchKernelGGL(frame_kernel_of(e->kframe, thick, fmt, false), dim3(N, rows), dim3(TC_NT), e->frame_lds, fs, fa);
         if (e->frame_order[fsi]) e->cost_row[fsi] = e->segm_n + ((size_t)r.seg_row0 + (size_t)rows - 1) * N;
       } else {
-#ifdef TC_DEV_FAST
-        auto rk = tc_raster_kernel<true, TC_DEV_FMTV>;
-#else
-        auto rk = thick ? (cls ? tc_raster_kernel<true, TC_FMT_CLASSES> : tc_raster_kernel<true, TC_FMT_RGB>)
-                        : (cls ? tc_raster_kernel<false, TC_FMT_CLASSES> : tc_raster_kernel<false, TC_FMT_RGB>);
-#endif
-        hipLaunchKernelGGL(rk, dim3(N, rows), dim3(TC_NT), e->r_lds, fs, r);
+        hipLaunchKernelGGL(raster_kernel_of(thick, fmt), dim3(N, rows), dim3(TC_NT), e->r_lds, fs, r);
       }
       HIP_TRY(hipGetLastError());
       if (piped) HIP_TRY(hipEventRecord(e->slot_ev[rslot], fs));
@@ -5222,38 +5158,19 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     return TC_OK;
   }
   if (prof) HIP_TRY(hipEventRecord(e->ev[0][slot], main));
-  if (do_raster && e->fuse && kv != 13) {  // one launch: simulate + raster by the same wavefront
-    // (the register-hungry K = 13 simulate stage spills when fused, so it stays two launches)
-    const bool thick = e->k.cam.thickness > 1, cls = e->k.cam.format == TC_FMT_CLASSES;
+  StepArgs sa = args_at(0);
+  sa.ma.nsteps = nsteps;
+  if (plan.fused) {  // one launch: simulate + raster by the same wavefront
     // (component groups that fit the K = 5 register cache: the K = 5 kernel with 16-segment batches, as for the frame kernel --
     // its simulate stage then walks the map's lane-line nodes in windows of 320 instead of 576)
-    fused_kern_t fk = e->kframe == 516 ? pick_fused<5, 16>(thick, cls, per, epk)
-                      : kv == 5        ? pick_fused<5>(thick, cls, per, epk)
-                      : kv == 8        ? pick_fused<8>(thick, cls, per, epk)
-                                       : pick_fused<9>(thick, cls, per, epk);
-    KArgs k = e->k;
-    k.env0 = 0;
-    RArgs r = make_rargs(e, e->k.seg_g, e->k.seg_n, e->k.seg_cap, nullptr, flags, 0, nullptr, mode == MODE_STEP);
+    step_kern_t fk = step_kernel_of(e->kframe == 516 ? 516 : kv, thick, fmt, feat);
+    sa.r = make_rargs(e, e->k.seg_g, e->k.seg_n, e->k.seg_cap, nullptr, flags, 0, nullptr, mode == MODE_STEP);
     // covers both stages and the parked state; behind it, up to the size that costs the CU no workgroup, the head of the
     // frame's draw list (see tc_env_create)
     const int lds = e->step_lds;
-    k.seg_lds_off = r.seg_lds_off = e->k.lds.total;
-    k.seg_lds_cap = r.seg_lds_cap = e->seg_lds_cap ? (e->step_lds - e->k.lds.total) / 20 : 0;
-    if (k.seg_lds_cap > e->seg_lds_limit) k.seg_lds_cap = r.seg_lds_cap = e->seg_lds_limit;
-    StepArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.a = k;
-    sa.cr = e->cr;
-    sa.ep = ep_at(0);
-    sa.r = r;
-    sa.ma = ma;
-    sa.mode = mode;
-    sa.cdtype = cdtype;
-    sa.flags = flags;
-    sa.car_control = cc;
-    sa.maneuver = man;
-    sa.spawn_nodes = spawn;
-    sa.mask = mask;
+    sa.a.seg_lds_off = sa.r.seg_lds_off = e->k.lds.total;
+    sa.a.seg_lds_cap = sa.r.seg_lds_cap = e->seg_lds_cap ? (e->step_lds - e->k.lds.total) / 20 : 0;
+    if (sa.a.seg_lds_cap > e->seg_lds_limit) sa.a.seg_lds_cap = sa.r.seg_lds_cap = e->seg_lds_limit;
     if (e->env_order && nsteps == 1) {
       // every order_every-th step the envs are re-dealt to the workgroups by the draw-list lengths of the step before
       // (tc_order_kernel: a 1-workgroup launch of a few microseconds on the caller's stream)
@@ -5273,34 +5190,17 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     }
     return noise_advance(e, mode, true, nsteps, stream);
   }
-  {
-    KArgs k = e->k;
-    k.env0 = 0;
-    StepArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.a = k;
-    sa.cr = e->cr;
-    sa.ep = ep_at(0);
-    sa.ma = ma;
-    sa.ma.cam_here = do_raster ? 1 : 0;
-    sa.mode = mode;
-    sa.cdtype = cdtype;
-    sa.flags = flags;
-    sa.car_control = cc;
-    sa.maneuver = man;
-    sa.spawn_nodes = spawn;
-    sa.mask = mask;
-    // (K steps without observations run on the one-wavefront-per-env kernel: with nothing to share the chip with, its
-    // shorter serial chain wins -- cfg2: 16.5 us per step against 20.7 for the grouped kernel)
-    hipLaunchKernelGGL(do_raster ? kern : kern_nocam, dim3(N), dim3(TC_NT), k.lds.total, main, sa);
-    HIP_TRY(hipGetLastError());
-    if (prof) HIP_TRY(hipEventRecord(e->ev[1][slot], main));
-    if (do_raster) {
-      int rc = launch_raster(e, e->k.seg_g, e->k.seg_n, e->k.seg_cap, mode == MODE_RESET ? mask : nullptr, flags, main, 0, N,
-                             roll ? roll->obs : nullptr, mode == MODE_STEP);
-      if (rc != TC_OK) return rc;
-      e->draw_n = -1;
-    }
+  sa.ma.cam_here = do_raster ? 1 : 0;
+  // (K steps without observations run on the one-wavefront-per-env kernel: with nothing to share the chip with, its
+  // shorter serial chain wins -- cfg2: 16.5 us per step against 20.7 for the grouped kernel)
+  hipLaunchKernelGGL(env_kernel_of(kv, do_raster, feat), dim3(N), dim3(TC_NT), e->k.lds.total, main, sa);
+  HIP_TRY(hipGetLastError());
+  if (prof) HIP_TRY(hipEventRecord(e->ev[1][slot], main));
+  if (do_raster) {
+    int rc = launch_raster(e, e->k.seg_g, e->k.seg_n, e->k.seg_cap, mode == MODE_RESET ? mask : nullptr, flags, main, 0, N,
+                           roll ? roll->obs : nullptr, mode == MODE_STEP);
+    if (rc != TC_OK) return rc;
+    e->draw_n = -1;
   }
   if (prof) {
     HIP_TRY(hipEventRecord(e->ev[2][slot], main));
@@ -5327,8 +5227,6 @@ extern "C" int tc_step_multi(tc_env* e, const void* car_control, int32_t control
     set_err("tc_env_bind has not been called");
     return TC_E_UNBOUND;
   }
-  const bool want_obs = !(flags & (TC_F_NO_OBSERVATION | DBG_SKIP_CAMERA)) && (e->k.b.obs || (rollout && rollout->obs));
-  (void)want_obs;
   if ((e->ep.len_rows || e->ep.ret_rows) && n_steps > e->ep_rows) {
     set_err("tc_step_multi: more steps than the episode rows hold (tc_env_set_episode_rollout)");
     return TC_E_INVALID;
@@ -5381,19 +5279,15 @@ extern "C" int tc_env_draw_list_stats(tc_env* e, double* mean_segments, double* 
 extern "C" int tc_env_launch_info(const tc_env* e, uint32_t flags, int32_t n_steps, int32_t* fused, int32_t* kvar,
                                   int32_t* steps_per_dispatch, char* name, int32_t name_cap) {
   if (!e) return TC_E_INVALID;
-  const bool do_raster = !(flags & (TC_F_NO_OBSERVATION | DBG_SKIP_CAMERA)) && e->k.b.obs;
-  const bool f = fused_path(e, flags) && !(n_steps > 1 && e->multi_split);
-  if (fused) *fused = f ? 1 : 0;
-  if (kvar) *kvar = (f && e->kframe == 516) ? 5 : e->kvar;  // (the fused kernel of a map with component groups: K = 5)
-  const bool frames = n_steps > 1 && do_raster && !f && e->fuse && e->kvar != 13;
-  const bool streamed = frames && e->env_grouped && e->pipe && e->stream && e->st_rows >= 2;  // (as in launch())
-  if (steps_per_dispatch)
-    *steps_per_dispatch = f ? n_steps : streamed ? (n_steps < e->st_rows ? n_steps : e->st_rows) : chunk_steps(e, n_steps, frames, true);
+  const CallPlan p = plan_call(e, flags, n_steps, e->k.b.obs != nullptr, true);  // (every frame wanted)
+  if (fused) *fused = p.fused ? 1 : 0;
+  if (kvar) *kvar = (p.fused && e->kframe == 516) ? 5 : e->kvar;  // (the fused kernel of a map with component groups: K = 5)
+  if (steps_per_dispatch) *steps_per_dispatch = p.steps;
   if (name && name_cap > 0)
     snprintf(name, (size_t)name_cap, "%s",
-             f ? "tc_step_kernel"
-               : frames ? (e->env_grouped ? "tc_envg_kernel+tc_frame_kernel" : "tc_env_kernel+tc_frame_kernel")
-               : do_raster ? "tc_env_kernel+tc_raster_kernel"
+             p.fused ? "tc_step_kernel"
+             : p.frames ? (e->env_grouped ? "tc_envg_kernel+tc_frame_kernel" : "tc_env_kernel+tc_frame_kernel")
+             : p.do_raster ? "tc_env_kernel+tc_raster_kernel"
                            : "tc_env_kernel");
   return TC_OK;
 }

@@ -2,7 +2,7 @@
 """Cost of per-env cars on cfg3 (4096 envs, simple_layout, 64x64 'classes', autoreset): env-steps/s for
 
     shared     the shared car (the default kernels)
-    rows       per-env rows set to the config's values (the *_car kernels doing the same arithmetic: the pure cost)
+    rows       per-env rows set to the config's values (the per-env-car kernels doing the same arithmetic: the pure cost)
     random     per-episode randomisation of all eight columns (every re-spawn draws a new car)
 
 each in 128-step streamed calls (step_multi with observation rows) and in the closed step() loop (tc_step), each with

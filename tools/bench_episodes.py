@@ -2,7 +2,7 @@
 """Cost of the episode accounting on cfg3 (4096 envs, simple_layout, 64x64 'classes', autoreset): env-steps/s for
 
     off        no episode buffers installed (the default kernels)
-    track      track_episodes(): length / return / statistics kept by the *_ep kernels, no limit
+    track      track_episodes(): length / return / statistics kept by the kernels with the episode bit, no limit
     limit      set_time_limit(256) with staggered starts (env i begins at length i * 256 / N): a steady trickle of
                time-limit truncations and re-spawns instead of all envs at once
 
