@@ -353,3 +353,54 @@ def test_single_steps_with_cost_aware_env_order(order, n, monkeypatch):
     stats = env.draw_list_stats()
     assert stats["frames"] == n and stats["max_segments"] > 0
     env.close()
+
+
+def oracle_calls(env, Ks, seed, dispatch=None):
+    """resets `env`, then one K-step call per entry of Ks (scratch reserved for just that K before it), every rollout row
+    and the bound buffers against the oracle; dispatch: the steps per dispatch expected of each call"""
+    n = env.num_envs
+    env.reset(seed=seed)
+    o = make_oracle(env, threads=8)
+    o.reset(env._keep[0].cpu().numpy())
+    o.spawn_queue = env._aux["spawn_queue"].cpu().numpy()
+    for call, K in enumerate(Ks):
+        env.reserve_steps(K)
+        roll = env.alloc_rollout(K, keys="all")
+        cc, man = mixed_actions(n, K, seed=seed + 30 + call)
+        env.step_multi(cc, man, rollout=roll)
+        torch.cuda.synchronize()
+        check_rows_against_oracle(env, o, cc, man, roll, orc.F_AUTORESET, f"call {call} of {K} steps")
+        if dispatch:
+            assert env.launch_info(K)["steps_per_dispatch"] == dispatch[call], (call, env.launch_info(K))
+    assert_same(env, o, env.n_classes, check_obs=False, label="bound buffers after the last call")
+
+
+@pytest.mark.parametrize("switch,dispatch", [({}, (4, 40)), ({"TC_STREAM": "0"}, (2, 10))], ids=["streamed", "ring"])
+def test_scratch_grows_between_calls(switch, dispatch, monkeypatch):
+    """one handle, scratch reserved for 4 steps and used, then for 40 and used: the second reservation frees and
+    re-allocates the rows of the streamed scratch (defaults: the 40 steps are one dispatch only if it now has 40 rows) /
+    of the ring (TC_STREAM=0: chunks of 10 steps only if a slot has grown beyond its 4 rows)"""
+    for k, v in switch.items():
+        monkeypatch.setenv(k, v)
+    env = make_env("simple_layout", "r64", "classes", 64, autoreset=True, spawn_queue_len=32)
+    oracle_calls(env, (4, 40), seed=6, dispatch=dispatch)
+    env.close()
+
+
+def test_refused_creation_leaves_the_next_one_intact():
+    """tc_env_create with a camera of height 0 is refused on the host (TC_E_INVALID, no handle, no kernel) after the
+    handle's streams and events exist; a normal creation right behind it works and steps like the oracle"""
+    import ctypes as C
+    from tinycarlo_amd import _native as nat
+    probe = make_env("simple_layout", "r64", "classes", 8)
+    cp = nat.make_car_params(probe.car_params)
+    bad = nat.make_camera_params(probe.camera, nat.FMT_CLASSES)
+    bad.height = 0
+    h = C.c_void_p()
+    assert nat.lib().tc_env_create(probe._nmap.handle, C.byref(cp), C.byref(bad), 8, C.byref(h)) == -1  # TC_E_INVALID
+    assert not h.value and b"camera" in nat.lib().tc_last_error()
+    env = make_env("simple_layout", "r64", "classes", 64, autoreset=True, spawn_queue_len=32)
+    torch.cuda.synchronize()
+    oracle_calls(env, (4,), seed=2)
+    env.close()
+    probe.close()

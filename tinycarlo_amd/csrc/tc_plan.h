@@ -1,0 +1,183 @@
+// Host-only planners of tc_env_create: how the camera stage's work is cut into groups and where its buffers sit in
+// LDS.  Pure arithmetic on host arrays -- no HIP header, no device call -- so the host compiler builds it alone
+// (tests/test_plan_cpu.py does).  The limits that belong to the kernels (group count, register-cache sizes) come in as
+// arguments.
+#pragma once
+#include <vector>
+
+static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
+
+// Camera layer groups.  Up to 512 nodes / edges the whole map is one group held in the K = 5 / 8 register cache.
+// Beyond that the layers are packed greedily, in order, into groups no larger than the largest single layer:
+// the LDS node buffer shrinks from the whole map to that layer (knuffingen: 827 -> 517 nodes, 26.6 -> 17.4 KB per
+// env, 6 -> 8 workgroups per CU) and a K = 9 cache (576 slots) covers a group.  Maps whose largest layer exceeds
+// `max_cap` (576) nodes or edges, or that would need more than `max_groups` groups or fewer than two, stay one group
+// on the K = 13 windowed path: ok is false and nothing else is set.
+struct LayerGroups {
+  bool ok = false;
+  std::vector<int> layer;  // group g = layers layer[g] .. layer[g + 1] - 1
+  int cap_n = 0, cap_e = 0;  // nodes / edges of the largest group
+};
+static inline LayerGroups plan_layer_groups(const int* node_off, const int* edge_off, int C, int max_cap, int max_groups) {
+  LayerGroups p;
+  int cap = 0;
+  for (int l = 0; l < C; l++) {
+    int nl = node_off[l + 1] - node_off[l], el = edge_off[l + 1] - edge_off[l];
+    cap = nl > cap ? nl : cap;
+    cap = el > cap ? el : cap;
+  }
+  if (cap > max_cap) return p;
+  std::vector<int> lay(1, 0);
+  for (int l = 0; l < C;) {
+    if ((int)lay.size() - 1 == max_groups) return p;
+    int first = l;
+    while (l < C && node_off[l + 1] - node_off[first] <= cap && edge_off[l + 1] - edge_off[first] <= cap) l++;
+    lay.push_back(l);  // l > first: a single layer always fits `cap`
+  }
+  const int ng = (int)lay.size() - 1;
+  if (ng < 2) return p;
+  for (int g = 0; g < ng; g++) {
+    int nl = node_off[lay[g + 1]] - node_off[lay[g]], el = edge_off[lay[g + 1]] - edge_off[lay[g]];
+    p.cap_n = nl > p.cap_n ? nl : p.cap_n;
+    p.cap_e = el > p.cap_e ? el : p.cap_e;
+  }
+  p.layer = lay;
+  p.ok = true;
+  return p;
+}
+
+// Component groups.  The layer scheme leaves the LDS node buffer at the size of the largest LAYER (knuffingen: 517 of
+// 827 nodes, 12.4 KB of a workgroup's 17.4 KB), and that buffer is what decides how many frame workgroups a CU holds
+// (9).  A layer is not the unit of independence, though: camera.py's fix-up passes move a node along its own edges
+// only, so every connected component of the lane-line graph (a dash of a dashed line is one) can be processed on its
+// own.  The camera stage therefore works from a copy of the map in which the components of each layer stand side by
+// side -- nodes renumbered, every layer's edges still contiguous and in their original relative order (the replay of a
+// fix-up chain follows edge order, and a chain never leaves its component) -- packed greedily into groups of at most
+// T nodes / edges (TC_CAM_GROUP, default 320: the buffer shrinks to 7.7 KB).  Nodes without an edge are never drawn and
+// are left out.  ok is false when a component is larger than T, the groups are more than `max_groups`, or a group's
+// edges are not one index range: the caller keeps the layer scheme.
+struct ComponentGroups {
+  bool ok = false;
+  std::vector<int> new_id;    // [n_nodes]: a node's id in the camera copy, -1 for a node without an edge
+  std::vector<int> n0, e0;    // group g = nodes n0[g] .. n0[g + 1] - 1 (new ids) and edges e0[g] .. e0[g + 1] - 1
+  std::vector<int> l0, l1;    // ... whose layers are l0[g] .. l1[g] - 1
+  int cap_n = 0, cap_e = 0;   // nodes / edges of the largest group
+};
+// edges: n_edges = edge_off[C] pairs of global node ids, layer by layer
+static inline ComponentGroups plan_component_groups(const int* edge_off, int C, const int* edges, int n_nodes, int T,
+                                                    int max_groups) {
+  ComponentGroups p;
+  const int TN = n_nodes, TE = edge_off[C];
+  std::vector<int> parent(TN);
+  for (int i = 0; i < TN; i++) parent[i] = i;
+  auto find = [&](int x) {
+    while (parent[x] != x) x = parent[x] = parent[parent[x]];
+    return x;
+  };
+  for (int ed = 0; ed < TE; ed++) {
+    const int a0 = find(edges[2 * ed]), b0 = find(edges[2 * ed + 1]);
+    if (a0 != b0) parent[b0 > a0 ? b0 : a0] = b0 > a0 ? a0 : b0;
+  }
+  // components in order of their first edge (edges are layer by layer, so components are too)
+  std::vector<int> comp_of_root(TN, -1), comp_first_edge, comp_nn, comp_ne;
+  std::vector<int> edge_comp(TE);
+  for (int ed = 0; ed < TE; ed++) {
+    const int r = find(edges[2 * ed]);
+    if (comp_of_root[r] < 0) {
+      comp_of_root[r] = (int)comp_first_edge.size();
+      comp_first_edge.push_back(ed);
+      comp_nn.push_back(0);
+      comp_ne.push_back(0);
+    }
+    edge_comp[ed] = comp_of_root[r];
+    comp_ne[edge_comp[ed]]++;
+  }
+  std::vector<int> node_comp(TN, -1);
+  for (int i = 0; i < TN; i++) {
+    const int c = comp_of_root[find(i)];
+    node_comp[i] = c;  // -1: a node without an edge
+    if (c >= 0) comp_nn[c]++;
+  }
+  const int NC = (int)comp_first_edge.size();
+  if (NC == 0) return p;
+  for (int c = 0; c < NC; c++)
+    if (comp_nn[c] > T || comp_ne[c] > T) return p;
+  std::vector<int> grp_first_comp(1, 0);
+  for (int c = 0, gn = 0, ge = 0; c < NC; c++) {
+    if (gn + comp_nn[c] > T || ge + comp_ne[c] > T) {
+      grp_first_comp.push_back(c);
+      gn = ge = 0;
+    }
+    gn += comp_nn[c];
+    ge += comp_ne[c];
+  }
+  grp_first_comp.push_back(NC);
+  const int NG = (int)grp_first_comp.size() - 1;
+  if (NG > max_groups) return p;
+  // New node ids: components in order, nodes of a component in their old order.  The edges are NOT moved (inside a
+  // layer the edges of two components may interleave -- two dashes drawn alternately -- and the replay of a fix-up
+  // chain needs every layer's edges in their old relative order): an edge keeps its index and only its node ids
+  // change.  A group's edges are then the index range from its first component's first edge to its last component's
+  // last edge, which must hold no edge of another group's components and start where the group before ends.
+  p.new_id.assign(TN, -1);
+  std::vector<int> comp_n0(NC + 1, 0);
+  for (int c = 0; c < NC; c++) comp_n0[c + 1] = comp_n0[c] + comp_nn[c];
+  std::vector<int> fill(comp_n0.begin(), comp_n0.end() - 1);
+  for (int i = 0; i < TN; i++)
+    if (node_comp[i] >= 0) p.new_id[i] = fill[node_comp[i]]++;
+  std::vector<int> comp_last_edge(NC, -1);
+  for (int ed = 0; ed < TE; ed++) comp_last_edge[edge_comp[ed]] = ed;
+  p.e0.assign(NG + 1, TE);
+  p.n0.assign(NG + 1, comp_n0[NC]);
+  int next_e = 0;  // where a group's edges must start: right behind the group before
+  for (int g = 0; g < NG; g++) {
+    const int c0 = grp_first_comp[g], c1 = grp_first_comp[g + 1];
+    int lo = TE, hi = -1, ne = 0;
+    for (int c = c0; c < c1; c++) {
+      lo = comp_first_edge[c] < lo ? comp_first_edge[c] : lo;
+      hi = comp_last_edge[c] > hi ? comp_last_edge[c] : hi;
+      ne += comp_ne[c];
+    }
+    if (lo != next_e) return p;
+    for (int ed = lo; ed <= hi; ed++)
+      if (edge_comp[ed] < c0 || edge_comp[ed] >= c1) return p;
+    next_e = lo + ne;
+    p.e0[g] = lo;
+    p.n0[g] = comp_n0[c0];
+  }
+  p.l0.assign(NG, 0);
+  p.l1.assign(NG, 0);
+  for (int g = 0; g < NG; g++) {
+    const int nl = p.n0[g + 1] - p.n0[g], el = p.e0[g + 1] - p.e0[g];
+    p.cap_n = nl > p.cap_n ? nl : p.cap_n;
+    p.cap_e = el > p.cap_e ? el : p.cap_e;
+    int la = 0, lb = 0;
+    while (la + 1 < C && p.e0[g] >= edge_off[la + 1]) la++;
+    while (lb + 1 < C && p.e0[g + 1] - 1 >= edge_off[lb + 1]) lb++;
+    p.l0[g] = la;
+    p.l1[g] = lb + 1;
+  }
+  p.ok = true;
+  return p;
+}
+
+// LDS of the camera stage, per workgroup: the node buffer, the node flags, the fix-up edge list / projection candidate
+// list and the counters, for camera groups of at most cap_n nodes and cap_e edges on a map of total_nodes nodes.
+// Sets off_p, off_flg, off_list, off_cnt and total of L (the kernels' LdsLayout).
+template <class Layout>
+static inline void plan_cam_lds(Layout& L, int cap_n, int cap_e, int total_nodes) {
+  const int cap_nodes = cap_n > 0 ? cap_n : 1;
+  int off = 0;
+  L.off_p = off;  // node buffer: 3 doubles per node of the largest camera group; phase B aliases it with one
+                  // double per lane-line node of the whole map
+  int pbytes = 3 * cap_nodes * 8;
+  if (total_nodes * 8 > pbytes) pbytes = total_nodes * 8;
+  off += align_up(pbytes, 16);
+  L.off_flg = off;
+  off += align_up(cap_nodes, 16);
+  L.off_list = off;  // fix-up edge list / projection candidate list
+  off += align_up((2 * cap_e > cap_n ? 2 * cap_e : cap_n) * 4 + 16, 16);
+  L.off_cnt = off;
+  off += 64;
+  L.total = off;
+}

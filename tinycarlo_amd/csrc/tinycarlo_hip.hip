@@ -3372,6 +3372,14 @@ static raster_kern_t raster_kernel_of(bool thick, int fmt) {
 // =============================================================================================
 // Host side: C ABI
 // =============================================================================================
+#include <assert.h>
+
+#include <algorithm>
+#include <memory>
+#include <utility>
+
+#include "tc_plan.h"
+
 static thread_local std::string g_err;
 static void set_err(const std::string& s) { g_err = s; }
 extern "C" const char* tc_last_error(void) { return g_err.c_str(); }
@@ -3386,109 +3394,232 @@ extern "C" int tc_abi_version(void) { return TC_ABI_VERSION; }
     }                                                                                    \
   } while (0)
 
-struct tc_map {
-  DevMap d;
-  std::vector<void*> allocs;
-  int device;
-  std::vector<double2> h_nodes;   // host copies of d.nodes / d.edges_g (tc_env_create groups the camera's copy by them)
-  std::vector<int2> h_edges_g;
-};
-
-struct tc_env {
-  const tc_map* map;
-  KArgs k;
-  CarRows cr;            // per-env cars (tc_env_set_car_per_env / tc_env_set_car_randomization); rows NULL = shared car
-  CarDrawTab* car_tab;   // device copy of the randomisation ranges (library owned, updated in place), or NULL
-  EpArgs ep;             // episodes (tc_env_set_episodes / tc_env_set_episode_rollout); length NULL = feature off
-  int* ep_tab;           // device word holding max_episode_steps (library owned, updated in place), or NULL
-  int ep_rows;           // rows of ep.len_rows / ep.ret_rows
-  bool bound;
-  int64_t obs_bytes;
-  int r_off_tab, r_off_bits, r_lds;
-  int fuse;  // 1: simulate + raster in one launch (tc_step_kernel); 0: two launches
-  // tc_step_multi with observations, split form (default; TC_MULTI_SPLIT=0 selects the fused K-step kernel): ONE
+// ---------------------------------------------------------------------------------------------
+// Every switch the library reads from the environment, parsed once per tc_env_create / tc_map_create by read_tuning()
+// -- the only place that looks at the environment.  INTEGRATION.md calls the shipped ones result-neutral.
+struct Tuning {
+  int fuse, env_grouped, envg_map_lds, first_per_env, stream, groups, seg_lds, frame_order, cand_grid;  // on / off
+  // tc_step_multi with observations, split form (default; 0 selects the fused K-step kernel): ONE
   // simulate launch loops over the K steps and leaves K draw lists per env, ONE raster launch of K x N workgroups
   // draws them.  Why: a frame costs between ~10 k clocks (nothing in view) and ~80 k (60 segments) to rasterise and an
   // env keeps its kind of view for many steps, so in the fused K-step kernel the launch lasts as long as its heaviest
   // env (measured on cfg3: 70.9 us per step against a mean of 41 us per wavefront-step).  Frames are independent of
   // each other, and K x N workgroups are many more than the chip holds at once, so the dispatcher balances them.
   int multi_split;
-  int chunk;        // K-step calls with a rollout: steps per chunk (TC_CHUNK, default 16)
-  int pipe;         // 1: the frame launches of a chunk run on an internal stream beside the next chunk's simulate launch
-                    // (TC_CHUNK=0 switches that off: chunks of the default size follow each other on the caller's stream)
-  hipStream_t frame_stream, frame_stream2;
-  hipEvent_t sim_ev, frames_ev, frames_ev2;
-  hipEvent_t slot_ev[TC_RING_SLOTS];  // frames of the chunk that last used ring slot s are done
-  hipEvent_t call_ev;                 // end of the last K-step call on its stream
-  hipStream_t last_stream;            // stream of that call
-  bool have_call;
+  int chunk;          // K-step calls with a rollout: steps per chunk
+  int pipe;           // 1: the frame launches of a chunk run on an internal stream beside the next chunk's simulate launch
+  int frame_streams;  // short K-step calls: frame launches of consecutive chunks alternate between two streams
+  long long gate_ticks;  // bound of a frame workgroup's wait in a streamed call (100 MHz ticks)
+  int gate_test;         // m > 0 (tests): frames with (row + env) % m == 0 are left to the gate-2 pass
+  int band_bytes;     // LDS budget of one band's bit-planes
+  bool band_fixed;    // ... given by the caller: the band is not shrunk to the camera stage's LDS afterwards
+  int cam_group;      // nodes / edges per component group of the camera's copy of the map
+  int seg_lds_limit;  // at most so many segments of a frame's draw list stay in LDS
+  int order_every;    // the env order of single steps is refreshed every n-th tc_step, 0 = no such order
+  double scratch_bytes;  // budget of the scratch of streamed K-step calls
+  bool print_lds = false;             // development builds only (TC_ABLATE)
+  int lds_pad = 0, step_lds_pad = 0;  // development builds only (TC_EXPERIMENT)
+};
+
+static Tuning read_tuning() {
+  static_assert(5 * TC_NT == 320, "default of TC_CAM_GROUP below");
+  static const struct {
+    const char *name, *dflt, *what;
+  } table[] = {
+      {"TC_FUSE", "1", "0: a single step is a simulate launch and a raster launch instead of one tc_step_kernel"},
+      {"TC_MULTI_SPLIT", "1", "0: K steps with frames loop inside the fused tc_step_kernel"},
+      {"TC_ENV_GROUPED", "1", "0: K-step calls simulate with one wavefront per env (tc_env_kernel), not tc_envg_kernel"},
+      {"TC_ENVG_MAP_LDS", "1", "0: tc_envg_kernel reads the edge and lanepath records from global memory, never LDS"},
+      {"TC_CHUNK", "16", "steps per chunk of a chunked K-step call; <= 0: 16, and the chunks are not pipelined"},
+      {"TC_FIRST_CHUNK_PER_ENV", "1", "0: the first chunk of a pipelined call is simulated by tc_envg_kernel too"},
+      {"TC_FRAME_STREAMS", "2", "1: the frame launches of short chunks stay on one internal stream"},
+      {"TC_STREAM", "1", "0: K-step calls run chunked instead of streamed"},
+      {"TC_STREAM_WAIT_US", "5000", "patience of a frame workgroup of a streamed call, microseconds"},
+      {"TC_STREAM_TEST_SKIP", "0", "m > 0 (tests): every m-th gated frame workgroup gives up at once"},
+      {"TC_STREAM_SCRATCH_MB", "16384", "budget of a streamed call's scratch; longer calls run as segments"},
+      {"TC_BAND_BYTES", "16384", "LDS bytes of one raster band's bit-planes (>= 1024); set: no later shrink"},
+      {"TC_GROUPS", "1", "0: no camera groups, big maps take the K = 13 windowed path"},
+      {"TC_CAM_GROUP", "320", "nodes / edges per component group; outside [64, 576]: groups of whole layers"},
+      {"TC_SEG_LDS", "1", "0: draw lists go through global memory only"},
+      {"TC_SEG_LDS_CAP", "-1", "n >= 0: at most n segments of a draw list stay in LDS"},
+      {"TC_FRAME_ORDER", "1", "0: frame workgroups in env order instead of heaviest first"},
+      {"TC_STEP_ORDER", "8", "single steps re-deal the envs to workgroups every n-th tc_step; <= 0: never"},
+      {"TC_CAND_GRID", "1", "0: nearest-edge queries scan every edge instead of the candidate grid"},
+#ifdef TC_ABLATE
+      {"TC_PRINT_LDS", "", "set: tc_env_create prints its LDS layout"},
+#endif
+#ifdef TC_EXPERIMENT
+      {"TC_LDS_PAD", "0", "unused LDS bytes per frame workgroup (occupancy experiments)"},
+      {"TC_STEP_LDS_PAD", "0", "unused LDS bytes per tc_step_kernel workgroup"},
+#endif
+  };
+  // the switch's text, or its default; *set: whether the environment has it
+  auto sw = [&](const char* name, bool* set = nullptr) -> const char* {
+    for (const auto& row : table)
+      if (!strcmp(row.name, name)) {
+        const char* v = getenv(row.name);
+        if (set) *set = v != nullptr;
+        return v ? v : row.dflt;
+      }
+    assert(!"read_tuning: a switch that is not in the table");
+    return "";
+  };
+  auto on = [&](const char* name) { return atoi(sw(name)) != 0 ? 1 : 0; };
+  auto positive = [&](const char* name) { return atoi(sw(name)) > 0 ? atoi(sw(name)) : 0; };
+  Tuning t;
+  t.fuse = on("TC_FUSE");
+  t.multi_split = on("TC_MULTI_SPLIT");
+  t.env_grouped = on("TC_ENV_GROUPED");
+  t.envg_map_lds = on("TC_ENVG_MAP_LDS");
+  t.first_per_env = on("TC_FIRST_CHUNK_PER_ENV");
+  t.stream = on("TC_STREAM");
+  t.groups = on("TC_GROUPS");
+  t.seg_lds = on("TC_SEG_LDS");
+  t.frame_order = on("TC_FRAME_ORDER");
+  t.cand_grid = on("TC_CAND_GRID");
+  t.pipe = positive("TC_CHUNK") > 0;
+  t.chunk = t.pipe ? positive("TC_CHUNK") : 16;
+  t.frame_streams = atoi(sw("TC_FRAME_STREAMS")) == 1 ? 1 : 2;
+  t.gate_ticks = (long long)(atof(sw("TC_STREAM_WAIT_US")) * 100.0);
+  t.gate_test = positive("TC_STREAM_TEST_SKIP");
+  t.scratch_bytes = atof(sw("TC_STREAM_SCRATCH_MB")) * 1048576.0;
+  t.band_bytes = atoi(sw("TC_BAND_BYTES", &t.band_fixed));
+  if (t.band_bytes < 1024) t.band_bytes = 16384;
+  t.cam_group = atoi(sw("TC_CAM_GROUP"));
+  t.seg_lds_limit = atoi(sw("TC_SEG_LDS_CAP")) >= 0 ? atoi(sw("TC_SEG_LDS_CAP")) : 1 << 30;
+  t.order_every = positive("TC_STEP_ORDER");
+#ifdef TC_ABLATE
+  (void)sw("TC_PRINT_LDS", &t.print_lds);
+#endif
+#ifdef TC_EXPERIMENT
+  t.lds_pad = atoi(sw("TC_LDS_PAD"));
+  t.step_lds_pad = atoi(sw("TC_STEP_LDS_PAD"));
+#endif
+  return t;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Move-only owners of a HIP resource: it is released when its owner goes or is assigned another.
+template <class H, hipError_t (*Release)(H)>
+struct Owned {
+  H h = nullptr;
+  Owned() = default;
+  Owned(Owned&& o) noexcept : h(o.h) { o.h = nullptr; }
+  Owned& operator=(Owned&& o) noexcept {  // (what this held goes with `o`)
+    std::swap(h, o.h);
+    return *this;
+  }
+  ~Owned() { reset(); }
+  void reset() {
+    if (h) (void)Release(h);
+    h = nullptr;
+  }
+  operator H() const { return h; }
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+template <class T>
+struct DevPtr {  // device memory of `count` T
+  Owned<void*, hipFree> mem;
+  operator T*() const { return (T*)mem.h; }
+  hipError_t alloc(size_t count) {
+    mem.reset();
+    return hipMalloc(&mem.h, count * sizeof(T));
+  }
+};
+
+// Scratch of K-step calls, `rows` steps of it: what the simulate launch leaves per (step, env) for the frame launch
+struct ScratchRows {
+  DevPtr<int> seg_g;    // [..rows][N][seg_cap][5] draw lists
+  DevPtr<int> seg_n;    // [..rows][N] their lengths
+  DevPtr<double> pose;  // [..rows][N][TC_POSE_ROW]
+  int rows = 0;
+};
+
+struct tc_map {
+  DevMap d{};
+  std::vector<DevPtr<char>> allocs;
+  int device = 0;
+  std::vector<double2> h_nodes;   // host copies of d.nodes / d.edges_g (tc_env_create groups the camera's copy by them)
+  std::vector<int2> h_edges_g;
+};
+
+struct tc_env {
+  explicit tc_env(const Tuning& t) : tune(t) {}
+  const Tuning tune;
+  const tc_map* map = nullptr;
+  KArgs k{};
+  // owners of what k points to: k.seg_g / k.seg_n, k.terms, k.spawn_tab, k.cam_nodes / k.cam_edges_g (the camera's copy of
+  // the map, grouped by connected components, or NULL)
+  DevPtr<int> seg_g, seg_n;
+  DevPtr<tc_term> terms;
+  DevPtr<int> spawn_tab;
+  DevPtr<double2> cam_nodes;
+  DevPtr<int2> cam_edges;
+  CarRows cr{};          // per-env cars (tc_env_set_car_per_env / tc_env_set_car_randomization); rows NULL = shared car
+  DevPtr<CarDrawTab> car_tab;  // device copy of the randomisation ranges (updated in place), or NULL
+  EpArgs ep{};           // episodes (tc_env_set_episodes / tc_env_set_episode_rollout); length NULL = feature off
+  DevPtr<int> ep_tab;    // device word holding max_episode_steps (updated in place), or NULL
+  int ep_rows = 0;       // rows of ep.len_rows / ep.ret_rows
+  bool bound = false;
+  int64_t obs_bytes = 0;
+  int r_off_tab = 0, r_off_bits = 0, r_lds = 0;
+  Stream frame_stream, frame_stream2;
+  Event sim_ev, frames_ev, frames_ev2;
+  Event slot_ev[TC_RING_SLOTS];  // frames of the chunk that last used ring slot s are done
+  Event call_ev;                 // end of the last K-step call on its stream
+  hipStream_t last_stream = nullptr;  // stream of that call
+  bool have_call = false;
   // where the draw-list lengths of the most recent frames are (tc_env_draw_list_stats): up to TC_RING_SLOTS (first ring
   // row, rows) pairs of the last K-step call, or the per-env list of the last single step (draw_n < 0)
-  int draw_rows[TC_RING_SLOTS][2];
-  int draw_n;
-  const int* draw_base;  // the [rows][N] array the pairs index: the ring's, or the streamed call's
-  // Streamed K-step calls (TC_STREAM=0: chunked as above): ONE simulate launch for all steps of the call and ONE frame
-  // launch beside it whose workgroups wait for their pose row -- see launch().  Scratch for st_rows steps
-  // (tc_env_reserve_steps); longer calls run as segments of st_rows steps.
-  int stream;            // 1 = on
-  int st_rows;
-  int* st_segm_g;        // [st_rows][N][seg_cap][5]
-  int* st_segm_n;        // [st_rows][N]
-  double* st_pose;       // [st_rows][N][TC_POSE_ROW], every entry TC_POSE_EMPTY between calls
-  unsigned int* st_words;  // [0] simulate workgroups resident, [1] "a frame workgroup gave up waiting"
-  long long gate_ticks;  // bound of a frame workgroup's wait (100 MHz ticks; TC_STREAM_WAIT_US)
-  int gate_test;         // TC_STREAM_TEST_SKIP=m (tests): frames with (row + env) % m == 0 are left to the gate-2 pass
-  hipEvent_t start_ev;
-  int step_lds;  // tc_step_kernel: LDS bytes per workgroup (lds.total grown like frame_lds)
-  // cost-aware env order of single-step launches (tc_order_kernel): refreshed every order_every-th tc_step
-  // heaviest-first order of the frame workgroups of a K-step call (TC_FRAME_ORDER=0: env order), one buffer per frame stream
-  int* frame_order[2];       // [N] each, device
-  const int* cost_row[2];    // draw-list lengths of the last frame row launched on that stream (library scratch), or NULL
-  bool frame_order_valid[2]; // the buffer holds a permutation (a sort has run on it)
-  int* env_order;   // [N] device, a permutation (identity until the first refresh); NULL = off (TC_STEP_ORDER=0, N % G != 0)
-  int order_g;      // G = SIMDs of the device
-  int order_every, order_calls;
-  int seg_lds_limit;  // TC_SEG_LDS_CAP
-  int frame_lds, seg_lds_off, seg_lds_cap;  // tc_frame_kernel: LDS bytes per workgroup, draw-list region (see KArgs)
-  void *cam_nodes_dev, *cam_edges_dev;  // the camera's copy of the map, grouped by connected components (or NULL)
-  int kframe;  // tc_frame_kernel variant: kvar, or 516 (K = 5, batches of 16) when every component group fits 320 nodes / edges
-  int frame_seg_cap;  // tc_frame_kernel's own capacity: seg_lds_cap, but never below 8 (its raster stage reads the list from LDS only)
-  int frame_streams;  // short K-step calls: frame launches of consecutive chunks alternate between two streams (TC_FRAME_STREAMS)
-  int prof_piped[TC_PROF_RING];
-  int envg_map_lds; // tc_envg_kernel keeps the edge records in LDS when they fit (TC_ENVG_MAP_LDS=0: always from global)
-  int first_per_env;  // the first chunk of a pipelined call goes through tc_env_kernel (TC_FIRST_CHUNK_PER_ENV=0: grouped too)
-  int env_grouped;  // K-step calls: simulate with tc_envg_kernel (TC_EL lanes per env); TC_ENV_GROUPED=0 keeps one wavefront per env
-  // scratch ring of K-step calls (tc_env_reserve_steps): TC_RING_SLOTS chunks of ring_rows steps
-  int *segm_g, *segm_n;  // [TC_RING_SLOTS * ring_rows][N][seg_cap][5], [..][N]
-  double* pose_rows;     // [TC_RING_SLOTS * ring_rows][N][TC_POSE_ROW]
-  int ring_rows;
-  int kvar;  // register-cache slots of the simulate stage: 5, 8 (whole map in one window), 9 (camera layer groups), 13
+  int draw_rows[TC_RING_SLOTS][2] = {};
+  int draw_n = 0;
+  const int* draw_base = nullptr;  // the [rows][N] array the pairs index: the ring's, or the streamed call's
+  // Streamed K-step calls (tune.stream = 0: chunked): ONE simulate launch for all steps of the call and ONE frame launch
+  // beside it whose workgroups wait for their pose row -- see launch().  Scratch for streamed.rows steps
+  // (tc_env_reserve_steps), every pose entry TC_POSE_EMPTY between calls; longer calls run as segments of that many steps.
+  ScratchRows streamed;
+  DevPtr<unsigned int> st_words;  // [0] simulate workgroups resident, [1] "a frame workgroup gave up waiting"
+  Event start_ev;
+  // scratch ring of chunked K-step calls (tc_env_reserve_steps): TC_RING_SLOTS chunks of ring.rows steps
+  ScratchRows ring;
+  int step_lds = 0;  // tc_step_kernel: LDS bytes per workgroup (lds.total grown like frame_lds)
+  // heaviest-first order of the frame workgroups of a K-step call (tune.frame_order = 0: env order), one buffer per frame stream
+  DevPtr<int> frame_order[2];               // [N] each
+  const int* cost_row[2] = {};              // draw-list lengths of the last frame row launched on that stream (library scratch), or NULL
+  bool frame_order_valid[2] = {};           // the buffer holds a permutation (a sort has run on it)
+  // cost-aware env order of single-step launches (tc_order_kernel): refreshed every tune.order_every-th tc_step
+  DevPtr<int> env_order;  // [N], a permutation (identity until the first refresh); NULL = off (order_every 0, N % G != 0)
+  int order_g = 0;        // G = SIMDs of the device
+  int order_calls = 0;
+  int frame_lds = 0, seg_lds_off = 0, seg_lds_cap = 0;  // tc_frame_kernel: LDS bytes per workgroup, draw-list region (see KArgs)
+  int kvar = 0;    // register-cache slots of the simulate stage: 5, 8 (whole map in one window), 9 (camera layer groups), 13
+  int kframe = 0;  // tc_frame_kernel variant: kvar, or 516 (K = 5, batches of 16) when every component group fits 320 nodes / edges
+  int frame_seg_cap = 0;  // tc_frame_kernel's own capacity: seg_lds_cap, but never below 8 (its raster stage reads the list from LDS only)
   // optional per-kernel timing: a ring of (start, mid, end) HIP events recorded on the caller's stream
-  int prof;    // 0 = off, n = record every n-th tc_step
-  int prof_n;  // launches recorded so far
-  int prof_calls;
+  int prof = 0;    // 0 = off, n = record every n-th tc_step
+  int prof_n = 0;  // launches recorded so far
+  int prof_calls = 0;
+  int prof_piped[TC_PROF_RING] = {};
+  hipEvent_t ev[4][TC_PROF_RING] = {};  // start, simulate done, all done, first frame launch (pipelined calls)
   // NoiseObservationWrapper: blobs per plane (0 = off), radius bound, the per-radius span table, launch counter
-  int noise_blobs, noise_max_radius;
-  unsigned char* noise_hw;
-  unsigned long long noise_seed;
-  unsigned int* noise_step;  // device counter
-  hipEvent_t ev[4][TC_PROF_RING];  // start, simulate done, all done, first frame launch (pipelined calls)
+  int noise_blobs = 0, noise_max_radius = 0;
+  DevPtr<unsigned char> noise_hw;
+  unsigned long long noise_seed = 0;
+  DevPtr<unsigned int> noise_step;  // device counter
 };
 
 template <typename T>
 static int upload(tc_map* m, const std::vector<T>& h, const T** out) {
-  void* p = nullptr;
-  size_t bytes = (h.size() ? h.size() : 1) * sizeof(T);
-  HIP_TRY(hipMalloc(&p, bytes));
-  m->allocs.push_back(p);
-  if (h.size()) HIP_TRY(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = (const T*)p;
+  DevPtr<char> p;
+  HIP_TRY(p.alloc((h.size() ? h.size() : 1) * sizeof(T)));
+  *out = (const T*)(char*)p;
+  m->allocs.push_back(std::move(p));
+  if (h.size()) HIP_TRY(hipMemcpy((void*)*out, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
   return TC_OK;
 }
 
 extern "C" int tc_map_destroy(tc_map* m) {
-  if (!m) return TC_OK;
-  for (void* p : m->allocs) (void)hipFree(p);
   delete m;
   return TC_OK;
 }
@@ -3509,15 +3640,12 @@ extern "C" int tc_map_create(const tc_map_desc* desc, tc_map** out) {
     set_err("tc_map_create: need 1..16 lane-line layers and a non-empty lanepath");
     return TC_E_INVALID;
   }
-  tc_map* m = new tc_map();
+  std::unique_ptr<tc_map> owner(new tc_map());
+  tc_map* m = owner.get();
   DevMap& d = m->d;
-  memset(&d, 0, sizeof(d));
   d.C = C;
   for (int l = 0; l < C; l++) {
-    if (desc->node_count[l] < 0 || desc->edge_count[l] < 0) {
-      delete m;
-      return TC_E_INVALID;
-    }
+    if (desc->node_count[l] < 0 || desc->edge_count[l] < 0) return TC_E_INVALID;
     d.node_off[l + 1] = d.node_off[l] + desc->node_count[l];
     d.edge_off[l + 1] = d.edge_off[l] + desc->edge_count[l];
     if (desc->node_count[l] > d.max_nodes) d.max_nodes = desc->node_count[l];
@@ -3534,7 +3662,6 @@ extern "C" int tc_map_create(const tc_map_desc* desc, tc_map** out) {
         int v = desc->edges[2 * e + k];
         if (v < 0 || v >= desc->node_count[l]) {
           set_err("tc_map_create: lane-line edge references a node outside its layer");
-          delete m;
           return TC_E_INVALID;
         }
       }
@@ -3544,7 +3671,6 @@ extern "C" int tc_map_create(const tc_map_desc* desc, tc_map** out) {
       int v = desc->lanepath_edges[2 * e + k];
       if (v < 0 || v >= lpN) {
         set_err("tc_map_create: lanepath edge references a missing node");
-        delete m;
         return TC_E_INVALID;
       }
     }
@@ -3613,7 +3739,6 @@ extern "C" int tc_map_create(const tc_map_desc* desc, tc_map** out) {
     if (noff[i + 1] > noff[i]) d.first_spawnable = i;
   if (d.first_spawnable < 0) {
     set_err("tc_map_create: lanepath has no edge, nothing can spawn");
-    delete m;
     return TC_E_INVALID;
   }
   // ---- candidate grid (see DevMap): cells of >= 4 cm, at most ~64 k of them, over the lane lines + 4 m
@@ -3629,7 +3754,7 @@ extern "C" int tc_map_create(const tc_map_desc* desc, tc_map** out) {
       if (i == 0 || y < by0) by0 = y;
       if (i == 0 || y > by1) by1 = y;
     }
-    if (const char* g = getenv("TC_CAND_GRID")) finite = finite && atoi(g) != 0;
+    finite = finite && read_tuning().cand_grid;
     std::vector<double> f(d.max_edges > 0 ? d.max_edges : 1);
     // appends the lists of an nx x ny grid of `cell`-sized cells with origin (x0, y0); returns the id of its first cell
     auto add_level = [&](double x0, double y0, double cell, int nx, int ny) {
@@ -3686,15 +3811,21 @@ extern "C" int tc_map_create(const tc_map_desc* desc, tc_map** out) {
 #undef UP
   m->h_nodes = nodes;
   m->h_edges_g = edges_g;
-  if (rc != TC_OK) {
-    tc_map_destroy(m);
-    return rc;
-  }
-  *out = m;
+  if (rc != TC_OK) return rc;
+  *out = owner.release();
   return TC_OK;
 }
 
-static int align_up(int v, int a) { return (v + a - 1) / a * a; }
+// the constants tc_env_set_car may change (T and the presence flags are fixed at tc_env_create)
+static void fill_car_constants(DevCar& c, const tc_car_params* car) {
+  c.wheelbase = car->wheelbase;
+  c.track_width = car->track_width;
+  c.max_velocity = car->max_velocity;
+  c.max_steering_angle = car->max_steering_angle;
+  c.steering_speed = car->steering_speed;
+  c.max_acceleration = car->max_acceleration;
+  c.max_deceleration = car->max_deceleration;
+}
 
 static int fill_camera(tc_env* e, const tc_camera_params* cam) {
   if (cam->height < 1 || cam->width < 1 || cam->height > 16384 || cam->width > 16384 || cam->line_thickness < 1 ||
@@ -3715,157 +3846,51 @@ static int fill_camera(tc_env* e, const tc_camera_params* cam) {
   return TC_OK;
 }
 
-extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const tc_camera_params* cam,
-                             int32_t num_envs, tc_env** out) {
-  if (!map || !car || !cam || !out || num_envs < 1) return TC_E_INVALID;
-  *out = nullptr;
-  tc_env* e = new tc_env();
-  memset(&e->k, 0, sizeof(e->k));
-  e->map = map;
-  e->bound = false;
-  e->prof = 0;
-  e->prof_n = 0;
-  e->prof_calls = 0;
-  memset(e->ev, 0, sizeof(e->ev));
-  e->fuse = 1;
-  if (const char* fu = getenv("TC_FUSE")) e->fuse = atoi(fu) != 0;
-  e->multi_split = 1;
-  if (const char* ms = getenv("TC_MULTI_SPLIT")) e->multi_split = atoi(ms) != 0;
-  e->env_grouped = 1;
-  if (const char* eg = getenv("TC_ENV_GROUPED")) e->env_grouped = atoi(eg) != 0;
-  e->envg_map_lds = 1;
-  if (const char* ml = getenv("TC_ENVG_MAP_LDS")) e->envg_map_lds = atoi(ml) != 0;
-  e->chunk = 16;
-  e->pipe = 1;
-  if (const char* ch = getenv("TC_CHUNK")) {
-    if (atoi(ch) > 0)
-      e->chunk = atoi(ch);
-    else
-      e->pipe = 0;
-  }
-  e->frame_stream = e->frame_stream2 = nullptr;
-  e->sim_ev = e->frames_ev = e->frames_ev2 = e->call_ev = nullptr;
-  memset(e->slot_ev, 0, sizeof(e->slot_ev));
-  e->last_stream = nullptr;
-  e->have_call = false;
-  e->first_per_env = 1;
-  if (const char* fp = getenv("TC_FIRST_CHUNK_PER_ENV")) e->first_per_env = atoi(fp) != 0;
-  e->frame_streams = 2;
-  if (const char* fsn = getenv("TC_FRAME_STREAMS")) e->frame_streams = atoi(fsn) == 1 ? 1 : 2;
-  memset(e->prof_piped, 0, sizeof(e->prof_piped));
-  e->stream = 1;
-  if (const char* st = getenv("TC_STREAM")) e->stream = atoi(st) != 0;
-  e->st_rows = 0;
-  e->st_segm_g = e->st_segm_n = nullptr;
-  e->st_pose = nullptr;
-  e->st_words = nullptr;
-  e->draw_base = nullptr;
-  e->start_ev = nullptr;
-  e->gate_ticks = 5000 * 100LL;  // 5 ms
-  if (const char* gw = getenv("TC_STREAM_WAIT_US")) e->gate_ticks = (long long)(atof(gw) * 100.0);
-  e->gate_test = 0;
-  if (const char* gt = getenv("TC_STREAM_TEST_SKIP")) e->gate_test = atoi(gt) > 0 ? atoi(gt) : 0;
-  if (hipStreamCreateWithFlags(&e->frame_stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&e->frame_stream2, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&e->frames_ev2, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->sim_ev, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->start_ev, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->frames_ev, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->call_ev, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->slot_ev[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->slot_ev[1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->slot_ev[2], hipEventDisableTiming) != hipSuccess) {
+// ---- tc_env_create, step by step (in the order they are called)
+
+static int create_streams_and_events(tc_env* e) {
+  bool ok = hipStreamCreateWithFlags(&e->frame_stream.h, hipStreamNonBlocking) == hipSuccess &&
+            hipStreamCreateWithFlags(&e->frame_stream2.h, hipStreamNonBlocking) == hipSuccess;
+  for (Event* ev : {&e->frames_ev2, &e->sim_ev, &e->start_ev, &e->frames_ev, &e->call_ev, &e->slot_ev[0], &e->slot_ev[1], &e->slot_ev[2]})
+    ok = ok && hipEventCreateWithFlags(&ev->h, hipEventDisableTiming) == hipSuccess;
+  static_assert(TC_RING_SLOTS == 3, "slot events are listed one by one above");
+  if (!ok) {
     set_err("tc_env_create: cannot create the internal frame streams / events");
-    tc_env_destroy(e);
     return TC_E_HIP;
   }
-  static_assert(TC_RING_SLOTS == 3, "slot events are created one by one above");
-  e->segm_g = e->segm_n = nullptr;
-  e->pose_rows = nullptr;
-  e->ring_rows = 0;
-  e->k.m = map->d;
-  e->k.N = num_envs;
-  DevCar& c = e->k.car;
-  c.T = car->T;
-  c.wheelbase = car->wheelbase;
-  c.track_width = car->track_width;
-  c.max_velocity = car->max_velocity;
-  c.max_steering_angle = car->max_steering_angle;
-  c.steering_speed = car->steering_speed;
-  c.max_acceleration = car->max_acceleration;
-  c.max_deceleration = car->max_deceleration;
-  c.has_steering_speed = car->has_steering_speed;
-  c.has_max_acceleration = car->has_max_acceleration;
-  int rc = fill_camera(e, cam);
-  if (rc != TC_OK) {
-    delete e;
-    return rc;
-  }
+  return TC_OK;
+}
+
+// bit-plane band: keep one band's planes within a budget so several envs share a CU's 160 KiB LDS
+static void set_band_rows(tc_env* e, int band_rows) {
   DevCam& dc = e->k.cam;
-  const DevMap& m = map->d;
-  // bit-plane band: keep one band's planes within a budget so several envs share a CU's 160 KiB LDS
-  int budget = 16384;
-  if (const char* s = getenv("TC_BAND_BYTES")) {
-    int v = atoi(s);
-    if (v >= 1024) budget = v;
-  }
-  int row_bytes = m.C * dc.wpr * 4;
-  int band_rows = budget / row_bytes;
   if (band_rows < 1) band_rows = 1;
   if (band_rows > dc.H) band_rows = dc.H;
   dc.band_rows = band_rows;
   dc.n_bands = (dc.H + band_rows - 1) / band_rows;
-  // Camera layer groups.  Up to 512 nodes / edges the whole map is one group held in the K = 5 / 8 register cache.
-  // Beyond that the layers are packed greedily, in order, into groups no larger than the largest single layer:
-  // the LDS node buffer shrinks from the whole map to that layer (knuffingen: 827 -> 517 nodes, 26.6 -> 17.4 KB per
-  // env, 6 -> 8 workgroups per CU) and a K = 9 cache (576 slots) covers a group.  Maps whose largest layer exceeds
-  // 576 nodes or edges, or that would need more than TC_MAX_GROUPS groups, stay one group on the K = 13 windowed path
-  // (env var TC_GROUPS=0 forces that).
+}
+
+// Camera groups of whole layers (tc_plan.h), or the whole map as one group: sets kvar and the group bounds; returns
+// the nodes / edges of the largest group through cap_n / cap_e.
+static void plan_layers(tc_env* e, int* cap_n, int* cap_e) {
+  const DevMap& m = e->k.m;
   const int big = m.total_nodes > m.total_edges ? m.total_nodes : m.total_edges;
-  int cap_n = m.total_nodes, cap_e = m.total_edges;
+  *cap_n = m.total_nodes;
+  *cap_e = m.total_edges;
   e->k.n_grp = 1;
   e->k.grp_layer[0] = 0;
   e->k.grp_layer[1] = m.C;
   e->kvar = big <= 5 * TC_NT ? 5 : big <= 8 * TC_NT ? 8 : 13;
-  bool want_groups = big > 8 * TC_NT;
-  if (const char* sg = getenv("TC_GROUPS")) want_groups = want_groups && atoi(sg) != 0;
-  if (want_groups) {
-    int cap = 0;
-    for (int l = 0; l < m.C; l++) {
-      int nl = m.node_off[l + 1] - m.node_off[l], el = m.edge_off[l + 1] - m.edge_off[l];
-      cap = nl > cap ? nl : cap;
-      cap = el > cap ? el : cap;
-    }
-    if (cap <= 9 * TC_NT) {
-      int lay[TC_MAX_GROUPS + 1], ng = 0, l = 0;
-      bool ok = true;
-      lay[0] = 0;
-      while (l < m.C) {
-        if (ng == TC_MAX_GROUPS) {
-          ok = false;
-          break;
-        }
-        int first = l;
-        while (l < m.C && m.node_off[l + 1] - m.node_off[first] <= cap && m.edge_off[l + 1] - m.edge_off[first] <= cap) l++;
-        lay[++ng] = l;  // l > first: a single layer always fits `cap`
-      }
-      if (ok && ng >= 2) {
-        e->k.n_grp = ng;
-        cap_n = cap_e = 0;
-        for (int g = 0; g <= ng; g++) e->k.grp_layer[g] = lay[g];
-        for (int g = 0; g < ng; g++) {
-          int nl = m.node_off[lay[g + 1]] - m.node_off[lay[g]], el = m.edge_off[lay[g + 1]] - m.edge_off[lay[g]];
-          cap_n = nl > cap_n ? nl : cap_n;
-          cap_e = el > cap_e ? el : cap_e;
-        }
-        e->kvar = 9;
-      }
+  if (big > 8 * TC_NT && e->tune.groups) {
+    const LayerGroups p = plan_layer_groups(m.node_off, m.edge_off, m.C, 9 * TC_NT, TC_MAX_GROUPS);
+    if (p.ok) {
+      e->k.n_grp = (int)p.layer.size() - 1;
+      std::copy(p.layer.begin(), p.layer.end(), e->k.grp_layer);
+      *cap_n = p.cap_n;
+      *cap_e = p.cap_e;
+      e->kvar = 9;
     }
   }
-  // group bounds of the layer scheme (or of the single group)
-  e->k.cam_nodes = nullptr;
-  e->k.cam_edges_g = nullptr;
-  e->cam_nodes_dev = e->cam_edges_dev = nullptr;
   for (int g = 0; g <= e->k.n_grp; g++) {
     e->k.grp_n0[g] = m.node_off[e->k.grp_layer[g]];
     e->k.grp_e0[g] = m.edge_off[e->k.grp_layer[g]];
@@ -3874,321 +3899,240 @@ extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const 
     e->k.grp_l0[g] = e->k.grp_layer[g];
     e->k.grp_l1[g] = e->k.grp_layer[g + 1];
   }
-  // Component groups.  The layer scheme leaves the LDS node buffer at the size of the largest LAYER (knuffingen: 517 of
-  // 827 nodes, 12.4 KB of a workgroup's 17.4 KB), and that buffer is what decides how many frame workgroups a CU holds
-  // (9).  A layer is not the unit of independence, though: camera.py's fix-up passes move a node along its own edges
-  // only, so every connected component of the lane-line graph (a dash of a dashed line is one) can be processed on its
-  // own.  The camera stage therefore works from a copy of the map in which the components of each layer stand side by
-  // side -- nodes renumbered, every layer's edges still contiguous and in their original relative order (the replay of a
-  // fix-up chain follows edge order, and a chain never leaves its component) -- packed greedily into groups of at most
-  // TC_CAM_GROUP nodes / edges (default 320: the buffer shrinks to 7.7 KB).  Nodes without an edge are never drawn and
-  // are left out.  Falls back to the layer scheme when a component is larger than that or the groups are too many.
-  if (e->k.n_grp >= 2 && e->kvar == 9 && (int)map->h_nodes.size() == m.total_nodes && (int)map->h_edges_g.size() == m.total_edges) {
-    int T = 5 * TC_NT;
-    if (const char* cg = getenv("TC_CAM_GROUP")) T = atoi(cg);
-    if (T >= TC_NT && T <= 9 * TC_NT) {
-      const int TN = m.total_nodes, TE = m.total_edges;
-      std::vector<int> parent(TN);
-      for (int i = 0; i < TN; i++) parent[i] = i;
-      auto find = [&](int x) {
-        while (parent[x] != x) x = parent[x] = parent[parent[x]];
-        return x;
-      };
-      for (int ed = 0; ed < TE; ed++) {
-        const int a0 = find(map->h_edges_g[ed].x), b0 = find(map->h_edges_g[ed].y);
-        if (a0 != b0) parent[b0 > a0 ? b0 : a0] = b0 > a0 ? a0 : b0;
-      }
-      // components in order of their first edge (edges are layer by layer, so components are too)
-      std::vector<int> comp_of_root(TN, -1), comp_first_edge, comp_nn, comp_ne;
-      std::vector<int> edge_comp(TE);
-      for (int ed = 0; ed < TE; ed++) {
-        const int r = find(map->h_edges_g[ed].x);
-        if (comp_of_root[r] < 0) {
-          comp_of_root[r] = (int)comp_first_edge.size();
-          comp_first_edge.push_back(ed);
-          comp_nn.push_back(0);
-          comp_ne.push_back(0);
-        }
-        edge_comp[ed] = comp_of_root[r];
-        comp_ne[edge_comp[ed]]++;
-      }
-      std::vector<int> node_comp(TN, -1);
-      for (int i = 0; i < TN; i++) {
-        const int c = comp_of_root[find(i)];
-        node_comp[i] = c;  // -1: a node without an edge
-        if (c >= 0) comp_nn[c]++;
-      }
-      const int NC = (int)comp_first_edge.size();
-      bool ok = NC > 0;
-      for (int c = 0; c < NC && ok; c++) ok = comp_nn[c] <= T && comp_ne[c] <= T;
-      // a component's edges must all belong to one layer (they do: edges join nodes of their own layer) and components
-      // must appear layer by layer, so that an edge's position in the new order is its position in the old one's layer
-      std::vector<int> grp_first_comp;
-      if (ok) {
-        int gn = 0, ge = 0;
-        grp_first_comp.push_back(0);
-        for (int c = 0; c < NC; c++) {
-          if (gn + comp_nn[c] > T || ge + comp_ne[c] > T) {
-            grp_first_comp.push_back(c);
-            gn = ge = 0;
-          }
-          gn += comp_nn[c];
-          ge += comp_ne[c];
-        }
-        grp_first_comp.push_back(NC);
-        ok = (int)grp_first_comp.size() - 1 <= TC_MAX_GROUPS;
-      }
-      if (ok) {
-        // new node ids: components in order, nodes of a component in their old order; new edge order: by component,
-        // old order inside -- which is the old order within each layer as long as a layer's components are visited in
-        // the order of their first edges AND no component's edges interleave with another's inside a layer.  They may
-        // (two dashes drawn alternately), so the edges are NOT moved: an edge keeps its index and only its node ids
-        // change; a group's edges are then the index range from its first component's first edge to its last
-        // component's last edge, which must not contain edges of other groups' components -- checked below.
-        std::vector<int> new_id(TN, -1);
-        std::vector<int> comp_n0(NC + 1, 0);
-        for (int c = 0; c < NC; c++) comp_n0[c + 1] = comp_n0[c] + comp_nn[c];
-        std::vector<int> fill(comp_n0.begin(), comp_n0.end() - 1);
-        for (int i = 0; i < TN; i++)
-          if (node_comp[i] >= 0) new_id[i] = fill[node_comp[i]]++;
-        std::vector<int> comp_last_edge(NC, -1);
-        for (int ed = 0; ed < TE; ed++) comp_last_edge[edge_comp[ed]] = ed;
-        const int NG = (int)grp_first_comp.size() - 1;
-        std::vector<int> ge0(NG + 1), gn0(NG + 1);
-        for (int g = 0; g < NG && ok; g++) {
-          const int c0 = grp_first_comp[g], c1 = grp_first_comp[g + 1];
-          int lo = TE, hi = -1;
-          for (int c = c0; c < c1; c++) {
-            lo = comp_first_edge[c] < lo ? comp_first_edge[c] : lo;
-            hi = comp_last_edge[c] > hi ? comp_last_edge[c] : hi;
-          }
-          ge0[g] = lo;
-          gn0[g] = comp_n0[c0];
-          for (int ed = lo; ed <= hi && ok; ed++) ok = edge_comp[ed] >= c0 && edge_comp[ed] < c1;
-          if (g > 0) ok = ok && lo == ge0[g - 1] + [&] { int n = 0; for (int c = grp_first_comp[g - 1]; c < c0; c++) n += comp_ne[c]; return n; }();
-        }
-        ge0[NG] = TE;
-        gn0[NG] = comp_n0[NC];
-        ok = ok && ge0[0] == 0;
-        if (ok) {
-          std::vector<double2> cn((size_t)comp_n0[NC]);
-          std::vector<int2> ce((size_t)TE);
-          for (int i = 0; i < TN; i++)
-            if (new_id[i] >= 0) cn[new_id[i]] = map->h_nodes[i];
-          for (int ed = 0; ed < TE; ed++) ce[ed] = make_int2(new_id[map->h_edges_g[ed].x], new_id[map->h_edges_g[ed].y]);
-          void *dn = nullptr, *de = nullptr;
-          if (hipMalloc(&dn, cn.size() * sizeof(double2)) == hipSuccess && hipMalloc(&de, ce.size() * sizeof(int2)) == hipSuccess &&
-              hipMemcpy(dn, cn.data(), cn.size() * sizeof(double2), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(de, ce.data(), ce.size() * sizeof(int2), hipMemcpyHostToDevice) == hipSuccess) {
-            e->cam_nodes_dev = dn;
-            e->cam_edges_dev = de;
-            e->k.cam_nodes = (const double2*)dn;
-            e->k.cam_edges_g = (const int2*)de;
-            e->k.n_grp = NG;
-            cap_n = cap_e = 0;
-            for (int g = 0; g <= NG; g++) {
-              e->k.grp_n0[g] = gn0[g];
-              e->k.grp_e0[g] = ge0[g];
-            }
-            for (int g = 0; g < NG; g++) {
-              const int nl = gn0[g + 1] - gn0[g], el = ge0[g + 1] - ge0[g];
-              cap_n = nl > cap_n ? nl : cap_n;
-              cap_e = el > cap_e ? el : cap_e;
-              int la = 0, lb = 0;
-              while (la + 1 < m.C && ge0[g] >= m.edge_off[la + 1]) la++;
-              while (lb + 1 < m.C && ge0[g + 1] - 1 >= m.edge_off[lb + 1]) lb++;
-              e->k.grp_l0[g] = la;
-              e->k.grp_l1[g] = lb + 1;
-            }
-          } else {
-            if (dn) (void)hipFree(dn);
-            if (de) (void)hipFree(de);
-          }
-        }
-      }
-    }
-  }
+}
+
+// The camera's copy of the map with the nodes renumbered by `p`, on the device; false (nothing kept) when that fails.
+static bool upload_camera_copy(tc_env* e, const ComponentGroups& p) {
+  const tc_map* map = e->map;
+  std::vector<double2> cn((size_t)p.n0.back());
+  std::vector<int2> ce(map->h_edges_g.size());
+  for (size_t i = 0; i < map->h_nodes.size(); i++)
+    if (p.new_id[i] >= 0) cn[p.new_id[i]] = map->h_nodes[i];
+  for (size_t ed = 0; ed < ce.size(); ed++) ce[ed] = make_int2(p.new_id[map->h_edges_g[ed].x], p.new_id[map->h_edges_g[ed].y]);
+  DevPtr<double2> dn;
+  DevPtr<int2> de;
+  if (dn.alloc(cn.size()) != hipSuccess || de.alloc(ce.size()) != hipSuccess ||
+      hipMemcpy(dn, cn.data(), cn.size() * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(de, ce.data(), ce.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess)
+    return false;
+  e->cam_nodes = std::move(dn);
+  e->cam_edges = std::move(de);
+  e->k.cam_nodes = e->cam_nodes;
+  e->k.cam_edges_g = e->cam_edges;
+  return true;
+}
+
+// Camera groups of connected components (tc_plan.h) in place of the layer groups, where the plan succeeds
+static void plan_components(tc_env* e, int* cap_n, int* cap_e) {
+  const DevMap& m = e->k.m;
+  const tc_map* map = e->map;
+  const int T = e->tune.cam_group;
+  if (e->k.n_grp < 2 || e->kvar != 9 || (int)map->h_nodes.size() != m.total_nodes || (int)map->h_edges_g.size() != m.total_edges ||
+      T < TC_NT || T > 9 * TC_NT)
+    return;
+  static_assert(sizeof(int2) == 2 * sizeof(int), "edges are read as pairs of int");
+  const ComponentGroups p = plan_component_groups(m.edge_off, m.C, (const int*)map->h_edges_g.data(), m.total_nodes, T, TC_MAX_GROUPS);
+  if (!p.ok || !upload_camera_copy(e, p)) return;
+  e->k.n_grp = (int)p.l0.size();
+  std::copy(p.n0.begin(), p.n0.end(), e->k.grp_n0);
+  std::copy(p.e0.begin(), p.e0.end(), e->k.grp_e0);
+  std::copy(p.l0.begin(), p.l0.end(), e->k.grp_l0);
+  std::copy(p.l1.begin(), p.l1.end(), e->k.grp_l1);
+  *cap_n = p.cap_n;
+  *cap_e = p.cap_e;
+}
+
+// LDS of a workgroup: the camera stage's buffers (tc_plan.h), the raster stage's tables and band, the parked env state
+static void layout_lds(tc_env* e, int cap_n, int cap_e) {
+  const DevMap& m = e->k.m;
+  DevCam& dc = e->k.cam;
+  LdsLayout& L = e->k.lds;
   e->kframe = e->kvar;
   if (e->k.cam_nodes && cap_n <= 5 * TC_NT && cap_e <= 5 * TC_NT) e->kframe = 516;
   e->k.cap_nodes = cap_n > 0 ? cap_n : 1;
-  LdsLayout& L = e->k.lds;
-  int off = 0;
-  L.off_p = off;  // node buffer: 3 doubles per node of the largest camera group; phase B aliases it with one
-                  // double per lane-line node of the whole map
-  int pbytes = 3 * e->k.cap_nodes * 8;
-  if (m.total_nodes * 8 > pbytes) pbytes = m.total_nodes * 8;
-  off += align_up(pbytes, 16);
-  L.off_flg = off;
-  off += align_up(e->k.cap_nodes, 16);
-  L.off_list = off;  // fix-up edge list / projection candidate list
-  off += align_up((2 * cap_e > cap_n ? 2 * cap_e : cap_n) * 4 + 16, 16);
-  L.off_cnt = off;
-  off += 64;
-  L.total = off;
+  plan_cam_lds(L, cap_n, cap_e, m.total_nodes);
   // raster kernel: tables + bit-planes of one band
   // A frame taller than one band: the workgroup's LDS is the larger of the two stages' needs, and how many workgroups a
   // CU holds decides the rate of the big frames (cfg5: 6 per CU at 23.2 KB, 9 at 17.4 KB: 3.10 -> 3.82 M env-steps/s).
   // So the band shrinks until the raster stage needs no more than the camera stage does anyway -- not further: more
   // bands only repeat the per-band set-up (measured: 8 KB and 6 KB bands are slower again).
   // (tables of the batch size the fused / frame kernels of this variant are compiled with; tc_raster_kernel: RB_MAX)
+  const int row_bytes = m.C * dc.wpr * 4;
   const int r_off_bits_k = e->kvar == 13 ? R_OFF_BITS_OF(RB_MAX) : (e->kvar >= 8 ? R_OFF_BITS_OF(RB_OF_K(8)) : R_OFF_BITS_OF(RB_OF_K(5)));
-  if (dc.n_bands > 1 && !getenv("TC_BAND_BYTES")) {
+  if (dc.n_bands > 1 && !e->tune.band_fixed) {
     const int fit = (L.total - r_off_bits_k) / row_bytes;
-    if (fit >= 8 && fit < dc.band_rows) {
-      dc.band_rows = band_rows = fit;
-      dc.n_bands = (dc.H + band_rows - 1) / band_rows;
-    }
+    if (fit >= 8 && fit < dc.band_rows) set_band_rows(e, fit);
   }
   e->r_off_tab = R_OFF_TAB;
   e->r_off_bits = R_OFF_BITS_OF(RB_MAX);
-  e->r_lds = e->r_off_bits + align_up(m.C * band_rows * dc.wpr * 4, 16);
+  e->r_lds = e->r_off_bits + align_up(dc.band_rows * row_bytes, 16);
   // the env's parked state (tc_step_multi) sits behind whichever stage needs more, so that neither aliases it
-  const int r_lds_k = r_off_bits_k + align_up(m.C * band_rows * dc.wpr * 4, 16);
+  const int r_lds_k = r_off_bits_k + align_up(dc.band_rows * row_bytes, 16);
   L.off_live = align_up(L.total > r_lds_k ? L.total : r_lds_k, 16);
   L.total = L.off_live + TC_LIVE_BYTES;
-  {
-    // tc_frame_kernel keeps no env state in LDS, so the bytes behind both stages' buffers -- the LiveLds slot and whatever
-    // the workgroup can grow without costing the CU a workgroup (160 KB / workgroups per CU, in 1280-byte steps) --
-    // hold the head of the frame's draw list: the raster stage reads what the camera stage of the same wavefront just
-    // wrote without a round trip through global memory (cfg3: 44 of a frame's ~20-30 segments).
-    const int cu_lds = 160 * 1024;
-    const int w = cu_lds / L.total > 0 ? cu_lds / L.total : 1;
-    int grown = cu_lds / w / 1280 * 1280;
-    if (grown > L.total + 4096) grown = L.total + 4096;  // (200 segments are plenty)
-    if (grown < L.total) grown = L.total;
+}
+
+// tc_frame_kernel keeps no env state in LDS, so the bytes behind both stages' buffers -- the LiveLds slot and whatever
+// the workgroup can grow without costing the CU a workgroup (160 KB / workgroups per CU, in 1280-byte steps) --
+// hold the head of the frame's draw list: the raster stage reads what the camera stage of the same wavefront just
+// wrote without a round trip through global memory (cfg3: 44 of a frame's ~20-30 segments).
+static void grow_lds_for_draw_lists(tc_env* e) {
+  const LdsLayout& L = e->k.lds;
+  const int cu_lds = 160 * 1024;
+  const int w = cu_lds / L.total > 0 ? cu_lds / L.total : 1;
+  int grown = cu_lds / w / 1280 * 1280;
+  if (grown > L.total + 4096) grown = L.total + 4096;  // (200 segments are plenty)
+  if (grown < L.total) grown = L.total;
 #ifdef TC_TIMING_LDS
-    if (grown - 256 >= L.total) grown -= 256;  // the stamp buffer (static LDS) comes out of the draw-list head: same workgroups per CU
+  if (grown - 256 >= L.total) grown -= 256;  // the stamp buffer (static LDS) comes out of the draw-list head: same workgroups per CU
 #endif
-    e->frame_lds = e->step_lds = grown;
-    e->seg_lds_off = L.off_live;
-    e->seg_lds_cap = (grown - L.off_live) / 20;
-    e->seg_lds_limit = 1 << 30;
-    if (const char* sl = getenv("TC_SEG_LDS")) {
-      if (atoi(sl) == 0) {
-        e->seg_lds_cap = 0;
-        e->frame_lds = e->step_lds = L.total;
-      }
-    }
-    // TC_SEG_LDS_CAP=n: at most n segments of a frame's draw list stay in LDS (tests: a small n makes every frame take
-    // the mixed LDS + global list that otherwise only frames with more than ~44 segments reach)
-    if (const char* sc = getenv("TC_SEG_LDS_CAP")) {
-      const int v = atoi(sc);
-      if (v >= 0) e->seg_lds_limit = v;
-      if (e->seg_lds_cap > e->seg_lds_limit) e->seg_lds_cap = e->seg_lds_limit;
-    }
-    // tc_frame_kernel reads draw lists from LDS only (longer ones batch by batch through it): it keeps a region of at least
-    // 8 entries whatever the switches above say (they still rule tc_step_kernel, which has the generic form)
-    e->frame_seg_cap = e->seg_lds_cap;
-    if (e->frame_seg_cap < 8) {
-      e->frame_seg_cap = 8;
-      if (e->frame_lds < e->seg_lds_off + 8 * 20) e->frame_lds = e->seg_lds_off + 8 * 20;
-    }
+  e->frame_lds = e->step_lds = grown;
+  e->seg_lds_off = L.off_live;
+  e->seg_lds_cap = (grown - L.off_live) / 20;
+  if (!e->tune.seg_lds) {
+    e->seg_lds_cap = 0;
+    e->frame_lds = e->step_lds = L.total;
+  }
+  // tune.seg_lds_limit (tests): a small n makes every frame take the mixed LDS + global list that otherwise only frames
+  // with more than ~44 segments reach
+  if (e->seg_lds_cap > e->tune.seg_lds_limit) e->seg_lds_cap = e->tune.seg_lds_limit;
+  // tc_frame_kernel reads draw lists from LDS only (longer ones batch by batch through it): it keeps a region of at least
+  // 8 entries whatever the switches above say (they still rule tc_step_kernel, which has the generic form)
+  e->frame_seg_cap = e->seg_lds_cap;
+  if (e->frame_seg_cap < 8) {
+    e->frame_seg_cap = 8;
+    if (e->frame_lds < e->seg_lds_off + 8 * 20) e->frame_lds = e->seg_lds_off + 8 * 20;
+  }
 #ifdef TC_ABLATE
-    if (getenv("TC_PRINT_LDS"))
-      fprintf(stderr, "tc_env_create: lds.total %d off_live %d frame_lds %d seg_lds_cap %d r_lds %d band_rows %d n_bands %d\n", (int)L.total,
-              (int)L.off_live, e->frame_lds, e->seg_lds_cap, e->r_lds, e->k.cam.band_rows, e->k.cam.n_bands);
+  if (e->tune.print_lds)
+    fprintf(stderr, "tc_env_create: lds.total %d off_live %d frame_lds %d seg_lds_cap %d r_lds %d band_rows %d n_bands %d\n", (int)L.total,
+            (int)L.off_live, e->frame_lds, e->seg_lds_cap, e->r_lds, e->k.cam.band_rows, e->k.cam.n_bands);
 #endif
 #ifdef TC_EXPERIMENT
-    // occupancy experiments (make dev-exp, never shipped): unused LDS bytes per frame workgroup -> fewer workgroups per CU
-    if (const char* pd = getenv("TC_LDS_PAD")) e->frame_lds += atoi(pd);
-    if (const char* pd = getenv("TC_STEP_LDS_PAD")) e->step_lds += atoi(pd);
+  // occupancy experiments (make dev-exp, never shipped): unused LDS bytes per frame workgroup -> fewer workgroups per CU
+  e->frame_lds += e->tune.lds_pad;
+  e->step_lds += e->tune.step_lds_pad;
 #endif
-  }
-  if (L.total > 160 * 1024 || e->r_lds > 160 * 1024) {
-    set_err("tc_env_create: map too large for one workgroup's LDS");
-    delete e;
-    return TC_E_LDS;
-  }
-  {
-    int lds = L.total > e->r_lds ? L.total : e->r_lds;
-    if (e->frame_lds > lds) lds = e->frame_lds;
-    if (lds > 48 * 1024)  // every tc_step_kernel and tc_frame_kernel variant
-      for (int kcode : {516, 5, 8, 9})
-        for (int t = 0; t < 2; t++)
-          for (int fmt : {TC_FMT_CLASSES, TC_FMT_RGB}) {
-            for (unsigned feat = 0; feat <= TC_FEAT_ALL; feat++)
-              (void)hipFuncSetAttribute((const void*)step_kernel_of(kcode, t, fmt, feat), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)hipFuncSetAttribute((const void*)frame_kernel_of(kcode, t, fmt, false), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-          }
-  }
-  {  // tc_envg_kernel's LDS copies of the map (edge records + fat lanepath nodes, see launch()) can exceed the 48 KB default
-    const size_t envg_lds = ((size_t)m.total_edges * 48 + 15) / 16 * 16 + (size_t)m.lpN * sizeof(LpNode);
-    if (envg_lds > 40 * 1024)
-      for (unsigned feat = 0; feat <= TC_FEAT_ALL; feat++)
-        (void)hipFuncSetAttribute((const void*)envg_kernel_of(feat), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(envg_lds < 150 * 1024 ? envg_lds : 150 * 1024));
-  }
+}
+
+static int raise_lds_limits(const tc_env* e) {
+  const DevMap& m = e->k.m;
+  const int total = e->k.lds.total;
+  int rc = TC_OK;
+  // lets `kernel` be launched with `bytes` of dynamic LDS (beyond the runtime's default limit); after a refusal no more are tried
+  auto raise = [&rc](const void* kernel, int bytes, const char* family) {
+    const hipError_t he = rc == TC_OK ? hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) : hipSuccess;
+    if (he == hipSuccess) return;
+    (void)hipGetLastError();
+    set_err(std::string("tc_env_create: cannot raise the dynamic LDS limit of ") + family + " to " + std::to_string(bytes) +
+            " bytes: " + hipGetErrorString(he));
+    rc = TC_E_HIP;
+  };
+  int lds = total > e->r_lds ? total : e->r_lds;
+  if (e->frame_lds > lds) lds = e->frame_lds;
+  if (lds > 48 * 1024)  // every tc_step_kernel and tc_frame_kernel variant
+    for (int kcode : {516, 5, 8, 9})
+      for (int t = 0; t < 2; t++)
+        for (int fmt : {TC_FMT_CLASSES, TC_FMT_RGB}) {
+          for (unsigned feat = 0; feat <= TC_FEAT_ALL; feat++) raise((const void*)step_kernel_of(kcode, t, fmt, feat), lds, "tc_step_kernel");
+          raise((const void*)frame_kernel_of(kcode, t, fmt, false), lds, "tc_frame_kernel");
+        }
+  // tc_envg_kernel's LDS copies of the map (edge records + fat lanepath nodes, see launch()) can exceed the 48 KB default
+  const size_t envg_lds = ((size_t)m.total_edges * 48 + 15) / 16 * 16 + (size_t)m.lpN * sizeof(LpNode);
+  if (envg_lds > 40 * 1024)
+    for (unsigned feat = 0; feat <= TC_FEAT_ALL; feat++)
+      raise((const void*)envg_kernel_of(feat), (int)(envg_lds < 150 * 1024 ? envg_lds : 150 * 1024), "tc_envg_kernel");
   if (e->r_lds > 48 * 1024)
     for (int t = 0; t < 2; t++)
-      for (int fmt : {TC_FMT_CLASSES, TC_FMT_RGB})
-        (void)hipFuncSetAttribute((const void*)raster_kernel_of(t, fmt), hipFuncAttributeMaxDynamicSharedMemorySize, e->r_lds);
-  if (L.total > 48 * 1024) {
-    hipError_t he = hipSuccess;
+      for (int fmt : {TC_FMT_CLASSES, TC_FMT_RGB}) raise((const void*)raster_kernel_of(t, fmt), e->r_lds, "tc_raster_kernel");
+  if (total > 48 * 1024) {
     static const int kvs[4] = {5, 8, 9, 13};
-    for (int i = 0; i < 32 && he == hipSuccess; i++)  // every tc_env_kernel variant
-      he = hipFuncSetAttribute((const void*)env_kernel_of(kvs[i & 3], (i & 4) == 0, (unsigned)i >> 3),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, L.total);
-    if (he != hipSuccess) {
-      set_err(std::string("hipFuncSetAttribute: ") + hipGetErrorString(he));
-      delete e;
-      return TC_E_HIP;
+    for (int i = 0; i < 32; i++)  // every tc_env_kernel variant
+      raise((const void*)env_kernel_of(kvs[i & 3], (i & 4) == 0, (unsigned)i >> 3), total, "tc_env_kernel");
+  }
+  return rc;
+}
+
+// the draw list of the current frame, per env (single steps)
+static int alloc_draw_lists(tc_env* e) {
+  const size_t N = (size_t)e->k.N;
+  e->k.seg_cap = e->k.m.total_edges > 0 ? e->k.m.total_edges : 1;
+  hipError_t he = e->seg_g.alloc(N * e->k.seg_cap * 5);
+  if (he == hipSuccess) he = e->seg_n.alloc(N);
+  if (he == hipSuccess) he = hipMemset(e->seg_n, 0, N * sizeof(int));
+  if (he != hipSuccess) {
+    set_err(std::string("hipMalloc(draw list): ") + hipGetErrorString(he));
+    return TC_E_NOMEM;
+  }
+  e->k.seg_g = e->seg_g;
+  e->k.seg_n = e->seg_n;
+  return TC_OK;
+}
+
+// The orders workgroups are dealt in; each is optional (an allocation that fails leaves it off).
+static void alloc_orders(tc_env* e) {
+  const int N = e->k.N;
+  // heaviest-first order of the frame workgroups of a K-step call, one buffer per frame stream
+  if (e->tune.frame_order && N <= 60000) {
+    DevPtr<int> f0, f1;
+    if (f0.alloc((size_t)N) == hipSuccess && f1.alloc((size_t)N) == hipSuccess) {
+      e->frame_order[0] = std::move(f0);
+      e->frame_order[1] = std::move(f1);
+    } else {
+      (void)hipGetLastError();
     }
   }
+  // cost-aware env order of single-step launches (tc_order_kernel): when the N workgroups are whole rows of G = SIMDs
+  // of the device and all resident at once (N / G <= 4 wavefronts per SIMD)
+  hipDeviceProp_t prop;
+  int dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) e->order_g = prop.multiProcessorCount * 4;
+  if (e->tune.order_every > 0 && e->order_g > 0 && N % e->order_g == 0 && N / e->order_g <= 4 && N / e->order_g >= 2) {
+    std::vector<int> ident((size_t)N);
+    for (int i = 0; i < N; i++) ident[(size_t)i] = i;
+    DevPtr<int> o;
+    if (o.alloc((size_t)N) == hipSuccess && hipMemcpy(o, ident.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice) == hipSuccess)
+      e->env_order = std::move(o);
+    else
+      (void)hipGetLastError();
+  }
+}
+
+extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const tc_camera_params* cam,
+                             int32_t num_envs, tc_env** out) {
+  if (!map || !car || !cam || !out || num_envs < 1) return TC_E_INVALID;
+  *out = nullptr;
+  std::unique_ptr<tc_env> e(new tc_env(read_tuning()));
+  e->map = map;
+  int rc = create_streams_and_events(e.get());
+  if (rc != TC_OK) return rc;
+  e->k.m = map->d;
+  e->k.N = num_envs;
+  e->k.car.T = car->T;
+  e->k.car.has_steering_speed = car->has_steering_speed;
+  e->k.car.has_max_acceleration = car->has_max_acceleration;
+  fill_car_constants(e->k.car, car);
+  rc = fill_camera(e.get(), cam);
+  if (rc != TC_OK) return rc;
+  const DevCam& dc = e->k.cam;
+  const DevMap& m = map->d;
+  set_band_rows(e.get(), e->tune.band_bytes / (m.C * dc.wpr * 4));
+  int cap_n = 0, cap_e = 0;  // nodes / edges of the largest camera group
+  plan_layers(e.get(), &cap_n, &cap_e);
+  plan_components(e.get(), &cap_n, &cap_e);
+  layout_lds(e.get(), cap_n, cap_e);
+  grow_lds_for_draw_lists(e.get());
+  if (e->k.lds.total > 160 * 1024 || e->r_lds > 160 * 1024) {
+    set_err("tc_env_create: map too large for one workgroup's LDS");
+    return TC_E_LDS;
+  }
+  rc = raise_lds_limits(e.get());
+  if (rc != TC_OK) return rc;
   e->obs_bytes = (int64_t)dc.H * dc.W * (dc.format == TC_FMT_CLASSES ? m.C : 3);
-  e->k.seg_cap = m.total_edges > 0 ? m.total_edges : 1;
-  {
-    void *p = nullptr, *q = nullptr;
-    hipError_t he = hipMalloc(&p, (size_t)num_envs * e->k.seg_cap * 5 * sizeof(int));
-    if (he == hipSuccess) he = hipMalloc(&q, (size_t)num_envs * sizeof(int));
-    if (he == hipSuccess) he = hipMemset(q, 0, (size_t)num_envs * sizeof(int));
-    if (he != hipSuccess) {
-      set_err(std::string("hipMalloc(draw list): ") + hipGetErrorString(he));
-      if (p) (void)hipFree(p);
-      delete e;
-      return TC_E_NOMEM;
-    }
-    e->k.seg_g = (int*)p;
-    e->k.seg_n = (int*)q;
-  }
-  {
-    // cost-aware env order of single-step launches (tc_order_kernel): when the N workgroups are whole rows of G = SIMDs
-    // of the device and all resident at once (N / G <= 4 wavefronts per SIMD).  TC_STEP_ORDER=n refreshes the order every
-    // n-th tc_step (default 8), 0 switches it off.
-    e->env_order = nullptr;
-    e->frame_order[0] = e->frame_order[1] = nullptr;
-    e->cost_row[0] = e->cost_row[1] = nullptr;
-    e->frame_order_valid[0] = e->frame_order_valid[1] = false;
-    if (!(getenv("TC_FRAME_ORDER") && atoi(getenv("TC_FRAME_ORDER")) == 0) && num_envs <= 60000) {
-      void *f0 = nullptr, *f1 = nullptr;
-      if (hipMalloc(&f0, (size_t)num_envs * sizeof(int)) == hipSuccess && hipMalloc(&f1, (size_t)num_envs * sizeof(int)) == hipSuccess) {
-        e->frame_order[0] = (int*)f0;
-        e->frame_order[1] = (int*)f1;
-      } else {
-        if (f0) (void)hipFree(f0);
-        (void)hipGetLastError();
-      }
-    }
-    e->order_calls = 0;
-    e->order_every = 8;
-    if (const char* so = getenv("TC_STEP_ORDER")) e->order_every = atoi(so) > 0 ? atoi(so) : 0;
-    hipDeviceProp_t prop;
-    int dev = 0;
-    e->order_g = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) e->order_g = prop.multiProcessorCount * 4;
-    if (e->order_every > 0 && e->order_g > 0 && num_envs % e->order_g == 0 && num_envs / e->order_g <= 4 && num_envs / e->order_g >= 2) {
-      std::vector<int> ident((size_t)num_envs);
-      for (int i = 0; i < num_envs; i++) ident[(size_t)i] = i;
-      void* o = nullptr;
-      if (hipMalloc(&o, (size_t)num_envs * sizeof(int)) == hipSuccess &&
-          hipMemcpy(o, ident.data(), (size_t)num_envs * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) {
-        e->env_order = (int*)o;
-      } else {
-        if (o) (void)hipFree(o);
-        (void)hipGetLastError();
-      }
-    }
-  }
-  *out = e;
+  rc = alloc_draw_lists(e.get());
+  if (rc != TC_OK) return rc;
+  alloc_orders(e.get());
+  *out = e.release();
   return TC_OK;
 }
 
@@ -4224,40 +4168,10 @@ extern "C" int tc_env_profile_read(tc_env* e, double* sim_us, double* raster_us,
 }
 
 extern "C" int tc_env_destroy(tc_env* e) {
-  if (e && e->ev[0][0])
+  if (!e) return TC_OK;
+  if (e->ev[0][0])
     for (int k = 0; k < 4; k++)
       for (int i = 0; i < TC_PROF_RING; i++) (void)hipEventDestroy(e->ev[k][i]);
-  if (e) {
-    for (int sl = 0; sl < TC_RING_SLOTS; sl++)
-      if (e->slot_ev[sl]) (void)hipEventDestroy(e->slot_ev[sl]);
-    if (e->call_ev) (void)hipEventDestroy(e->call_ev);
-    if (e->frame_stream) (void)hipStreamDestroy(e->frame_stream);
-    if (e->frame_stream2) (void)hipStreamDestroy(e->frame_stream2);
-    if (e->frames_ev2) (void)hipEventDestroy(e->frames_ev2);
-    if (e->sim_ev) (void)hipEventDestroy(e->sim_ev);
-    if (e->start_ev) (void)hipEventDestroy(e->start_ev);
-    if (e->st_segm_g) (void)hipFree(e->st_segm_g);
-    if (e->st_segm_n) (void)hipFree(e->st_segm_n);
-    if (e->st_pose) (void)hipFree(e->st_pose);
-    if (e->st_words) (void)hipFree(e->st_words);
-    if (e->cam_nodes_dev) (void)hipFree(e->cam_nodes_dev);
-    if (e->cam_edges_dev) (void)hipFree(e->cam_edges_dev);
-    if (e->frames_ev) (void)hipEventDestroy(e->frames_ev);
-  }
-  if (e && e->segm_g) (void)hipFree(e->segm_g);
-  if (e && e->segm_n) (void)hipFree(e->segm_n);
-  if (e && e->pose_rows) (void)hipFree(e->pose_rows);
-  if (e && e->k.seg_g) (void)hipFree(e->k.seg_g);
-  if (e && e->k.seg_n) (void)hipFree(e->k.seg_n);
-  if (e && e->env_order) (void)hipFree(e->env_order);
-  if (e && e->frame_order[0]) (void)hipFree(e->frame_order[0]);
-  if (e && e->frame_order[1]) (void)hipFree(e->frame_order[1]);
-  if (e && e->k.terms) (void)hipFree((void*)e->k.terms);
-  if (e && e->k.spawn_tab) (void)hipFree((void*)e->k.spawn_tab);
-  if (e && e->noise_hw) (void)hipFree(e->noise_hw);
-  if (e && e->car_tab) (void)hipFree(e->car_tab);
-  if (e && e->ep_tab) (void)hipFree(e->ep_tab);
-  if (e && e->noise_step) (void)hipFree(e->noise_step);
   delete e;
   return TC_OK;
 }
@@ -4297,14 +4211,7 @@ extern "C" int tc_env_set_car(tc_env* e, const tc_car_params* car) {
     set_err("tc_env_set_car: T and the presence flags are fixed at tc_env_create, and every constant must be finite");
     return TC_E_INVALID;
   }
-  DevCar& c = e->k.car;
-  c.wheelbase = car->wheelbase;
-  c.track_width = car->track_width;
-  c.max_velocity = car->max_velocity;
-  c.max_steering_angle = car->max_steering_angle;
-  c.steering_speed = car->steering_speed;
-  c.max_acceleration = car->max_acceleration;
-  c.max_deceleration = car->max_deceleration;
+  fill_car_constants(e->k.car, car);
   return TC_OK;
 }
 
@@ -4350,11 +4257,7 @@ extern "C" int tc_env_set_car_randomization(tc_env* e, const double* lo, const d
   t.seed = seed;
   t.mask = column_mask;
   t.env_offset = env_offset;
-  if (!e->car_tab) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, sizeof(CarDrawTab)));
-    e->car_tab = (CarDrawTab*)p;
-  }
+  if (!e->car_tab) HIP_TRY(e->car_tab.alloc(1));
   // (in place: a graph captured earlier keeps reading this table; the copy waits for launches that may still read it)
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(e->car_tab, &t, sizeof(t), hipMemcpyHostToDevice));
@@ -4376,11 +4279,7 @@ extern "C" int tc_env_set_episodes(tc_env* e, const tc_episode_buffers* bufs, in
     e->ep_rows = 0;
     return TC_OK;
   }
-  if (!e->ep_tab) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, sizeof(int)));
-    e->ep_tab = (int*)p;
-  }
+  if (!e->ep_tab) HIP_TRY(e->ep_tab.alloc(1));
   // (in place: a graph captured earlier keeps reading this word; the copy waits for launches that may still read it)
   const int lim = max_episode_steps > 0 ? max_episode_steps : 0;
   HIP_TRY(hipDeviceSynchronize());
@@ -4493,23 +4392,13 @@ extern "C" int tc_env_set_noise(tc_env* e, int32_t n_blobs, int32_t max_radius, 
       minus -= mask2 & 2;
     }
   }
-  HIP_TRY(hipDeviceSynchronize());
-  if (e->noise_hw) {
-    HIP_TRY(hipFree(e->noise_hw));
-    e->noise_hw = nullptr;
-  }
-  void* p = nullptr;
-  HIP_TRY(hipMalloc(&p, hw.size()));
-  HIP_TRY(hipMemcpy(p, hw.data(), hw.size(), hipMemcpyHostToDevice));
-  e->noise_hw = (unsigned char*)p;
+  HIP_TRY(hipDeviceSynchronize());  // launches in flight still read the old table
+  HIP_TRY(e->noise_hw.alloc(hw.size()));  // (lets the old one go first)
+  HIP_TRY(hipMemcpy(e->noise_hw, hw.data(), hw.size(), hipMemcpyHostToDevice));
   e->noise_blobs = n_blobs;
   e->noise_max_radius = max_radius;
   e->noise_seed = seed;
-  if (!e->noise_step) {
-    void* q = nullptr;
-    HIP_TRY(hipMalloc(&q, sizeof(unsigned int)));
-    e->noise_step = (unsigned int*)q;
-  }
+  if (!e->noise_step) HIP_TRY(e->noise_step.alloc(1));
   HIP_TRY(hipMemset(e->noise_step, 0, sizeof(unsigned int)));
   const int lds = noise_lds_bytes(e);
   if (lds > 160 * 1024) {
@@ -4574,16 +4463,13 @@ extern "C" int tc_env_set_spawn_table(tc_env* e, const int32_t* nodes, int32_t n
       return TC_E_INVALID;
     }
   HIP_TRY(hipDeviceSynchronize());  // launches in flight still read the old table
-  if (e->k.spawn_tab) {
-    HIP_TRY(hipFree((void*)e->k.spawn_tab));
-    e->k.spawn_tab = nullptr;
-  }
+  e->spawn_tab.mem.reset();
+  e->k.spawn_tab = nullptr;
   e->k.spawn_n = 0;
   if (n > 0) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, sizeof(int32_t) * (size_t)n));
-    HIP_TRY(hipMemcpy(p, nodes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-    e->k.spawn_tab = (const int*)p;
+    HIP_TRY(e->spawn_tab.alloc((size_t)n));
+    HIP_TRY(hipMemcpy(e->spawn_tab, nodes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+    e->k.spawn_tab = e->spawn_tab;
     e->k.spawn_n = n;
   }
   e->k.spawn_seed = seed;
@@ -4613,12 +4499,11 @@ extern "C" int tc_env_set_terms(tc_env* e, const tc_term* terms, int32_t n_terms
     }
   }
   HIP_TRY(hipDeviceSynchronize());  // launches in flight still read the old table
-  if (!e->k.terms) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, sizeof(tc_term) * TC_MAX_TERMS));
-    e->k.terms = (const tc_term*)p;
+  if (!e->terms) {
+    HIP_TRY(e->terms.alloc(TC_MAX_TERMS));
+    e->k.terms = e->terms;
   }
-  if (n_terms > 0) HIP_TRY(hipMemcpy((void*)e->k.terms, terms, sizeof(tc_term) * n_terms, hipMemcpyHostToDevice));
+  if (n_terms > 0) HIP_TRY(hipMemcpy(e->terms, terms, sizeof(tc_term) * n_terms, hipMemcpyHostToDevice));
   e->k.n_terms = n_terms;
   e->k.term_counters = counters;
   return TC_OK;
@@ -4730,115 +4615,93 @@ struct CallPlan {
 static CallPlan plan_call(const tc_env* e, uint32_t flags, int nsteps, bool obs, bool all) {
   CallPlan p;
   // (the register-hungry K = 13 simulate stage spills when fused, so it stays two launches)
-  const bool can_fuse = e->fuse && e->kvar != 13;
+  const bool can_fuse = e->tune.fuse && e->kvar != 13;
   p.do_raster = !(flags & (TC_F_NO_OBSERVATION | DBG_SKIP_CAMERA)) && obs;
-  p.split = p.do_raster && nsteps > 1 && (e->multi_split || !can_fuse);
+  p.split = p.do_raster && nsteps > 1 && (e->tune.multi_split || !can_fuse);
   p.fused = p.do_raster && can_fuse && !p.split;
   p.frames = p.split && can_fuse;
-  p.piped = p.frames && e->env_grouped && e->pipe && all;
-  p.streamed = p.piped && e->stream && e->st_rows >= 2 && e->st_words;
+  p.piped = p.frames && e->tune.env_grouped && e->tune.pipe && all;
+  p.streamed = p.piped && e->tune.stream && e->streamed.rows >= 2 && e->st_words;
   p.steps = nsteps;
   if (p.streamed) {
-    if (p.steps > e->st_rows) p.steps = e->st_rows;
+    if (p.steps > e->streamed.rows) p.steps = e->streamed.rows;
   } else if (!p.fused) {
     // a chunk of a pipelined call: TC_CHUNK (16) steps, or a quarter of the call when that is less, so that a short call
     // (the 20 steps of a smoke benchmark) still has several chunks in flight; never more than a ring slot holds.  Calls
     // that are not pipelined run in chunks as large as the ring allows.
     if (p.piped) {
       const int q = (nsteps + 3) / 4;
-      p.steps = e->chunk < q ? e->chunk : (q < 2 ? 2 : q);
+      p.steps = e->tune.chunk < q ? e->tune.chunk : (q < 2 ? 2 : q);
     }
-    if (e->ring_rows > 0 && p.steps > e->ring_rows) p.steps = e->ring_rows;
+    if (e->ring.rows > 0 && p.steps > e->ring.rows) p.steps = e->ring.rows;
   }
   return p;
 }
 
 #define TC_STREAM_MAX_ROWS 128
+// Makes `s` hold `slots` x `rows` rows of N envs.  Nothing to do when it has that many rows; else the old arrays go
+// (once the launches that may still use them are done) and new ones come, their contents left to the caller: *grown.
+static int reserve_rows(tc_env* e, ScratchRows& s, int slots, int rows, const char* what, bool* grown) {
+  *grown = false;
+  if (s.rows >= rows) return TC_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  s = ScratchRows();
+  e->cost_row[0] = e->cost_row[1] = nullptr;
+  const size_t R = (size_t)slots * rows * e->k.N;
+  hipError_t he = s.seg_g.alloc(R * e->k.seg_cap * 5);
+  if (he == hipSuccess) he = s.seg_n.alloc(R);
+  if (he == hipSuccess) he = s.pose.alloc(R * TC_POSE_ROW);
+  if (he != hipSuccess) {
+    s = ScratchRows();
+    set_err(std::string("hipMalloc(") + what + "): " + hipGetErrorString(he));
+    return TC_E_NOMEM;
+  }
+  s.rows = rows;
+  *grown = true;
+  return TC_OK;
+}
+
 // scratch of streamed calls: rows for min(max_call_steps, TC_STREAM_MAX_ROWS) steps
 static int reserve_stream(tc_env* e, int max_call_steps) {
   int rows = max_call_steps < TC_STREAM_MAX_ROWS ? max_call_steps : TC_STREAM_MAX_ROWS;
   // the scratch of a row is N x (pose row + draw-list length + room for a whole draw list: 20 B x lane-line edges of the
   // map -- knuffingen: 15 KB per frame); with many envs on a big map the rows are cut so that it stays within a budget
-  // (TC_STREAM_SCRATCH_MB, default 16 GiB), and a longer call runs as more, shorter segments
-  {
-    const double per_row = (double)e->k.N * ((double)e->k.seg_cap * 5 * sizeof(int) + sizeof(int) + TC_POSE_ROW * sizeof(double));
-    double budget = 16384.0 * 1048576.0;
-    if (const char* sb = getenv("TC_STREAM_SCRATCH_MB")) budget = atof(sb) * 1048576.0;
-    const double fit = budget / per_row;
-    if (fit < (double)rows) rows = (int)fit;
-  }
+  // (tune.scratch_bytes, default 16 GiB), and a longer call runs as more, shorter segments
+  const double per_row = (double)e->k.N * ((double)e->k.seg_cap * 5 * sizeof(int) + sizeof(int) + TC_POSE_ROW * sizeof(double));
+  const double fit = e->tune.scratch_bytes / per_row;
+  if (fit < (double)rows) rows = (int)fit;
   if (rows < 2) rows = 2;
-  if (e->st_rows >= rows) return TC_OK;
-  HIP_TRY(hipDeviceSynchronize());  // earlier launches may still use the old arrays
-  if (e->st_segm_g) (void)hipFree(e->st_segm_g);
-  if (e->st_segm_n) (void)hipFree(e->st_segm_n);
-  if (e->st_pose) (void)hipFree(e->st_pose);
-  e->st_segm_g = e->st_segm_n = nullptr;
-  e->st_pose = nullptr;
-  e->st_rows = 0;
-  e->cost_row[0] = e->cost_row[1] = nullptr;
-  e->draw_n = 0;
+  bool grown;
+  int rc = reserve_rows(e, e->streamed, 1, rows, "scratch of streamed K-step calls", &grown);
+  if (rc != TC_OK || grown) e->draw_n = 0;  // (the rows the draw-list statistics pointed into are gone)
+  if (rc != TC_OK || !grown) return rc;
   const size_t R = (size_t)rows * e->k.N;
-  void *p = nullptr, *q = nullptr, *pr = nullptr;
-  hipError_t he = hipMalloc(&p, R * e->k.seg_cap * 5 * sizeof(int));
-  if (he == hipSuccess) he = hipMalloc(&q, R * sizeof(int));
-  if (he == hipSuccess) he = hipMalloc(&pr, R * TC_POSE_ROW * sizeof(double));
-  if (he == hipSuccess && !e->st_words) {
-    void* w = nullptr;
-    he = hipMalloc(&w, 256);
-    if (he == hipSuccess) he = hipMemset(w, 0, 256);
-    e->st_words = (unsigned int*)w;
+  hipError_t he = hipSuccess;
+  if (!e->st_words) {
+    he = e->st_words.alloc(64);
+    if (he == hipSuccess) he = hipMemset(e->st_words, 0, 256);
   }
-  if (he == hipSuccess) he = hipMemset(pr, 0xFF, R * TC_POSE_ROW * sizeof(double));  // every entry TC_POSE_EMPTY
-  if (he == hipSuccess) he = hipMemset(q, 0, R * sizeof(int));
+  if (he == hipSuccess) he = hipMemset(e->streamed.pose, 0xFF, R * TC_POSE_ROW * sizeof(double));  // every entry TC_POSE_EMPTY
+  if (he == hipSuccess) he = hipMemset(e->streamed.seg_n, 0, R * sizeof(int));
   if (he == hipSuccess) he = hipDeviceSynchronize();
   if (he != hipSuccess) {
-    if (p) (void)hipFree(p);
-    if (q) (void)hipFree(q);
-    if (pr) (void)hipFree(pr);
+    e->streamed = ScratchRows();
     set_err(std::string("hipMalloc(scratch of streamed K-step calls): ") + hipGetErrorString(he));
     return TC_E_NOMEM;
   }
-  e->st_segm_g = (int*)p;
-  e->st_segm_n = (int*)q;
-  e->st_pose = (double*)pr;
-  e->st_rows = rows;
   return TC_OK;
 }
 
 extern "C" int tc_env_reserve_steps(tc_env* e, int32_t max_call_steps) {
   if (!e || max_call_steps < 1) return TC_E_INVALID;
-  if (e->stream && e->env_grouped && e->pipe) {
+  if (e->tune.stream && e->tune.env_grouped && e->tune.pipe) {
     int rc = reserve_stream(e, max_call_steps);
     if (rc != TC_OK) return rc;
   }
-  int rows = max_call_steps < e->chunk ? max_call_steps : e->chunk;
+  int rows = max_call_steps < e->tune.chunk ? max_call_steps : e->tune.chunk;
   if (rows < 2) rows = 2;  // (a pipelined call never uses chunks of fewer than 2 steps)
-  if (e->ring_rows >= rows) return TC_OK;
-  HIP_TRY(hipDeviceSynchronize());  // earlier launches may still read the old ring
-  if (e->segm_g) (void)hipFree(e->segm_g);
-  if (e->segm_n) (void)hipFree(e->segm_n);
-  if (e->pose_rows) (void)hipFree(e->pose_rows);
-  e->segm_g = e->segm_n = nullptr;
-  e->pose_rows = nullptr;
-  e->ring_rows = 0;
-  e->cost_row[0] = e->cost_row[1] = nullptr;
-  const size_t R = (size_t)TC_RING_SLOTS * rows * e->k.N;
-  void *p = nullptr, *q = nullptr, *pr = nullptr;
-  hipError_t he = hipMalloc(&p, R * e->k.seg_cap * 5 * sizeof(int));
-  if (he == hipSuccess) he = hipMalloc(&q, R * sizeof(int));
-  if (he == hipSuccess) he = hipMalloc(&pr, R * TC_POSE_ROW * sizeof(double));
-  if (he != hipSuccess) {
-    if (p) (void)hipFree(p);
-    if (q) (void)hipFree(q);
-    set_err(std::string("hipMalloc(scratch ring of K-step calls): ") + hipGetErrorString(he));
-    return TC_E_NOMEM;
-  }
-  e->segm_g = (int*)p;
-  e->segm_n = (int*)q;
-  e->pose_rows = (double*)pr;
-  e->ring_rows = rows;
-  return TC_OK;
+  bool grown;
+  return reserve_rows(e, e->ring, TC_RING_SLOTS, rows, "scratch ring of K-step calls", &grown);
 }
 
 // a rollout from [step][env] row r0 on
@@ -4897,17 +4760,18 @@ static FrameArgs frame_args_of(const tc_env* e, uint32_t flags, const RArgs& r, 
   fa.a = e->k;
   fa.a.dbg = flags;
   fa.a.env0 = 0;
-  fa.a.seg_g = streamed ? e->st_segm_g : e->segm_g;
-  fa.a.seg_n = streamed ? e->st_segm_n : e->segm_n;
+  const ScratchRows& s = streamed ? e->streamed : e->ring;
+  fa.a.seg_g = s.seg_g;
+  fa.a.seg_n = s.seg_n;
   fa.r = r;
-  fa.pose_rows = streamed ? e->st_pose : e->pose_rows;
+  fa.pose_rows = s.pose;
   fa.a.seg_lds_off = fa.r.seg_lds_off = e->seg_lds_off;
   fa.a.seg_lds_cap = fa.r.seg_lds_cap = e->frame_seg_cap;
   if (streamed) {
     fa.abort_word = e->st_words + 1;
     fa.resident = e->st_words;
-    fa.gate_ticks = e->gate_ticks;
-    fa.gate_test = e->gate_test;
+    fa.gate_ticks = e->tune.gate_ticks;
+    fa.gate_test = e->tune.gate_test;
   }
   return fa;
 }
@@ -4919,8 +4783,8 @@ static int launch_envg(const tc_env* e, unsigned feat, StepArgs& sa, hipStream_t
   // simple_layout 12.4 + 17.5 KB, knuffingen 34.6 + 40.2 KB per workgroup of 32 envs (a CU holds one or two such
   // workgroups: 128 of them cover 4096 envs)
   const size_t map_bytes = ((size_t)e->k.m.total_edges * 48 + 15) / 16 * 16, fat_bytes = (size_t)e->k.m.lpN * sizeof(LpNode);
-  sa.ma.map_lds = (e->envg_map_lds && map_bytes <= 40 * 1024) ? 1 : 0;
-  sa.ma.fat_lds = (e->envg_map_lds && fat_bytes <= 56 * 1024) ? 1 : 0;
+  sa.ma.map_lds = (e->tune.envg_map_lds && map_bytes <= 40 * 1024) ? 1 : 0;
+  sa.ma.fat_lds = (e->tune.envg_map_lds && fat_bytes <= 56 * 1024) ? 1 : 0;
   hipLaunchKernelGGL(envg_kernel_of(feat), dim3(envg_grid(e->k.N)), dim3(TC_ENVG_NT),
                      (sa.ma.map_lds ? map_bytes : 0) + (sa.ma.fat_lds ? fat_bytes : 0), stream, sa);
   HIP_TRY(hipGetLastError());
@@ -4966,7 +4830,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
   if (plan.split) {
     // K steps, split form: per chunk ONE simulate launch over its steps and ONE launch over the frames wanted.  The pose
     // rows / draw lists of a chunk live in slot (chunk index mod TC_RING_SLOTS) of the scratch ring.
-    if (e->ring_rows < 1) {
+    if (e->ring.rows < 1) {
       set_err("tc_step_multi with observations needs the scratch ring: call tc_env_reserve_steps(env, n) once before "
               "(tc_step_multi itself never allocates)");
       return TC_E_INVALID;
@@ -4991,11 +4855,11 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     // simulate launch -- so that chunk c+1's workgroups fill the slots chunk c's tail leaves empty (cfg3: 8-step call
     // 66.2 -> 58.3 us per step, 20-step call 46.9 -> 44.0; with chunks of 10 steps it costs 7 %, so longer calls keep one
     // stream and their frame launches follow one another, as a kernel trace of the default command shows them).
-    const bool two_fs = piped && e->frame_streams == 2 && chunk < 8;
+    const bool two_fs = piped && e->tune.frame_streams == 2 && chunk < 8;
     bool first_frames = true;
     bool used_fs[2] = {false, false};
     e->draw_n = 0;
-    e->draw_base = e->segm_n;
+    e->draw_base = e->ring.seg_n;
     // Streamed form (default when every step's frame is wanted).  The chunked pipeline below pays for its structure: the
     // first chunk's simulate launch overlaps with nothing, and every frame dispatch ends in a tail with the chip half empty
     // -- a quarter of a 20-step call.  Here the whole call (or a segment of st_rows steps) is ONE simulate launch on the
@@ -5008,7 +4872,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     // result never depends on how the two launches were scheduled.
     const bool streamed = plan.streamed;
     if (streamed) {
-      e->draw_base = e->st_segm_n;
+      e->draw_base = e->streamed.seg_n;
       int si = 0;
       for (int c0 = 0, cn = 0; c0 < nsteps; c0 += cn, si++) {
         cn = nsteps - c0 < plan.steps ? nsteps - c0 : plan.steps;
@@ -5016,11 +4880,11 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
         if (si > 0) HIP_TRY(hipStreamWaitEvent(main, e->slot_ev[0], 0));
         HIP_TRY(hipEventRecord(e->start_ev, main));
         StepArgs sa = args_at(c0);
-        sa.a.seg_g = e->st_segm_g;
-        sa.a.seg_n = e->st_segm_n;
+        sa.a.seg_g = e->streamed.seg_g;
+        sa.a.seg_n = e->streamed.seg_n;
         sa.ma.nsteps = cn;
         sa.ma.seg_rows = cn > 1 ? cn : 2;
-        sa.ma.pose_rows = e->st_pose;
+        sa.ma.pose_rows = e->streamed.pose;
         sa.ma.resident = e->st_words;
         int rc = launch_envg(e, feat, sa, main);
         if (rc != TC_OK) return rc;
@@ -5035,7 +4899,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
           e->frame_order_valid[0] = true;
         }
         HIP_TRY(hipStreamWaitEvent(fs, e->start_ev, 0));
-        RArgs r = make_rargs(e, e->st_segm_g, e->st_segm_n, e->k.seg_cap, nullptr, flags, 0, sa.ma.roll.obs, mode == MODE_STEP);
+        RArgs r = make_rargs(e, e->streamed.seg_g, e->streamed.seg_n, e->k.seg_cap, nullptr, flags, 0, sa.ma.roll.obs, mode == MODE_STEP);
         r.seg_row0 = 0;
         r.noise_row0 = c0;
         r.obs_row_stride = (long long)N * (long long)e->obs_bytes;
@@ -5043,7 +4907,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
         if (e->frame_order[0] && e->frame_order_valid[0]) fa.order = e->frame_order[0];
         // (ten times the patience of a frame workgroup: one idle wavefront costs nothing, and when another env's frame
         // launch has the chip -- two handles stepping on one GPU -- the simulate workgroups only get on as that launch drains)
-        hipLaunchKernelGGL(tc_gate_kernel, dim3(1), dim3(64), 0, fs, (const unsigned int*)e->st_words, envg_grid(N), 10 * e->gate_ticks);
+        hipLaunchKernelGGL(tc_gate_kernel, dim3(1), dim3(64), 0, fs, (const unsigned int*)e->st_words, envg_grid(N), 10 * e->tune.gate_ticks);
         HIP_TRY(hipGetLastError());
         if (prof && si == 0) HIP_TRY(hipEventRecord(e->ev[3][slot], fs));
         fa.gate = 1;
@@ -5056,7 +4920,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
         hipLaunchKernelGGL(frame_kernel_of(e->kframe, thick, fmt, true), dim3(N), dim3(TC_NT), e->frame_lds, fs, fa);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(e->slot_ev[0], fs));
-        if (e->frame_order[0]) e->cost_row[0] = e->st_segm_n + (size_t)(cn - 1) * N;
+        if (e->frame_order[0]) e->cost_row[0] = e->streamed.seg_n + (size_t)(cn - 1) * N;
         used_fs[0] = true;
         const int keep = cn < 3 * 16 ? cn : 3 * 16;  // the statistics cover the same span as a chunked call's ring
         e->draw_rows[0][0] = cn - keep;
@@ -5068,21 +4932,21 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     for (int c0 = 0, cn = 0; !streamed && c0 < nsteps; c0 += cn, ci++) {
       cn = nsteps - c0 < chunk ? nsteps - c0 : chunk;
       const int rslot = ci % TC_RING_SLOTS;
-      const size_t rb = (size_t)rslot * e->ring_rows;   // first row of this chunk in the scratch ring
+      const size_t rb = (size_t)rslot * e->ring.rows;   // first row of this chunk in the scratch ring
       // the frames that read this ring slot TC_RING_SLOTS chunks ago must be done before it is rewritten
       if (piped && ci >= TC_RING_SLOTS) HIP_TRY(hipStreamWaitEvent(main, e->slot_ev[rslot], 0));
       StepArgs sa = args_at(c0);
-      sa.a.seg_g = e->segm_g + rb * N * e->k.seg_cap * 5;
-      sa.a.seg_n = e->segm_n + rb * N;
+      sa.a.seg_g = e->ring.seg_g + rb * N * e->k.seg_cap * 5;
+      sa.a.seg_n = e->ring.seg_n + rb * N;
       sa.ma.nsteps = cn;
       sa.ma.seg_rows = cn > 1 ? cn : 2;  // (> 1: row k of the chunk's lists; a one-step chunk still writes row 0 of them)
       sa.ma.cam_here = frames ? 0 : 1;
-      sa.ma.pose_rows = frames ? e->pose_rows + rb * N * TC_POSE_ROW : nullptr;
+      sa.ma.pose_rows = frames ? e->ring.pose + rb * N * TC_POSE_ROW : nullptr;
       // The first chunk's simulate launch overlaps with nothing, so it should be SHORT rather than cheap: it goes through
       // the one-wavefront-per-env kernel (4096 wavefronts, bound by throughput: ~15 us per step) instead of the grouped
       // one (512 wavefronts, a latency chain: 13-23 us per step).  20-step call 48.4 -> 47.2 us per step, 128-step calls
       // 38.2 -> 37.6.  Both kernels read and leave the env's state in the caller's buffers, bit for bit the same.
-      if (frames && e->env_grouped && !(e->first_per_env && c0 == 0 && piped && nsteps > chunk)) {  // (a one-chunk call: grouped)
+      if (frames && e->tune.env_grouped && !(e->tune.first_per_env && c0 == 0 && piped && nsteps > chunk)) {  // (a one-chunk call: grouped)
         int rc = launch_envg(e, feat, sa, main);
         if (rc != TC_OK) return rc;
       } else {
@@ -5100,7 +4964,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
       }
       if (prof && first_frames && piped) HIP_TRY(hipEventRecord(e->ev[3][slot], fs));
       first_frames = false;
-      RArgs r = make_rargs(e, e->segm_g, e->segm_n, e->k.seg_cap, nullptr, flags, 0, all ? sa.ma.roll.obs : nullptr, mode == MODE_STEP);
+      RArgs r = make_rargs(e, e->ring.seg_g, e->ring.seg_n, e->k.seg_cap, nullptr, flags, 0, all ? sa.ma.roll.obs : nullptr, mode == MODE_STEP);
       // scratch row of the first frame drawn / its step index in the call (position in the blob stream)
       r.seg_row0 = (int)rb + (all ? 0 : cn - 1);
       r.noise_row0 = all ? c0 : nsteps - 1;
@@ -5122,7 +4986,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
         }
         if (e->frame_order[fsi] && e->frame_order_valid[fsi]) fa.order = e->frame_order[fsi];
         hipLaunchKernelGGL(frame_kernel_of(e->kframe, thick, fmt, false), dim3(N, rows), dim3(TC_NT), e->frame_lds, fs, fa);
-        if (e->frame_order[fsi]) e->cost_row[fsi] = e->segm_n + ((size_t)r.seg_row0 + (size_t)rows - 1) * N;
+        if (e->frame_order[fsi]) e->cost_row[fsi] = e->ring.seg_n + ((size_t)r.seg_row0 + (size_t)rows - 1) * N;
       } else {
         hipLaunchKernelGGL(raster_kernel_of(thick, fmt), dim3(N, rows), dim3(TC_NT), e->r_lds, fs, r);
       }
@@ -5170,11 +5034,11 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     const int lds = e->step_lds;
     sa.a.seg_lds_off = sa.r.seg_lds_off = e->k.lds.total;
     sa.a.seg_lds_cap = sa.r.seg_lds_cap = e->seg_lds_cap ? (e->step_lds - e->k.lds.total) / 20 : 0;
-    if (sa.a.seg_lds_cap > e->seg_lds_limit) sa.a.seg_lds_cap = sa.r.seg_lds_cap = e->seg_lds_limit;
+    if (sa.a.seg_lds_cap > e->tune.seg_lds_limit) sa.a.seg_lds_cap = sa.r.seg_lds_cap = e->tune.seg_lds_limit;
     if (e->env_order && nsteps == 1) {
       // every order_every-th step the envs are re-dealt to the workgroups by the draw-list lengths of the step before
       // (tc_order_kernel: a 1-workgroup launch of a few microseconds on the caller's stream)
-      if (mode == MODE_STEP && e->order_calls++ % e->order_every == 0 && e->order_calls > 1) {
+      if (mode == MODE_STEP && e->order_calls++ % e->tune.order_every == 0 && e->order_calls > 1) {
         hipLaunchKernelGGL(tc_order_kernel, dim3(1), dim3(TC_ORDER_NT), (size_t)(N + 15) / 16 * 16, main, (const int*)e->k.seg_n, N, e->order_g, e->env_order);
         HIP_TRY(hipGetLastError());
       }
@@ -5286,7 +5150,7 @@ extern "C" int tc_env_launch_info(const tc_env* e, uint32_t flags, int32_t n_ste
   if (name && name_cap > 0)
     snprintf(name, (size_t)name_cap, "%s",
              p.fused ? "tc_step_kernel"
-             : p.frames ? (e->env_grouped ? "tc_envg_kernel+tc_frame_kernel" : "tc_env_kernel+tc_frame_kernel")
+             : p.frames ? (e->tune.env_grouped ? "tc_envg_kernel+tc_frame_kernel" : "tc_env_kernel+tc_frame_kernel")
              : p.do_raster ? "tc_env_kernel+tc_raster_kernel"
                            : "tc_env_kernel");
   return TC_OK;
