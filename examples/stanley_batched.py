@@ -4,7 +4,7 @@
 controller reads cte / heading_error from the env's device tensors and writes the action tensor, the reference's
 wrappers (CTE sparse reward, CTE and crash termination) run inside the step kernel, finished envs re-spawn on the device.
 
-    python examples/stanley_batched.py [--envs 4096] [--steps 600] [--maneuver 3] [--randomize] [--max-episode-steps N]
+    python examples/stanley_batched.py [--envs 4096] [--steps 600] [--maneuver 3] [--randomize] [--max-episode-steps N] [--fused K]
 
 --randomize: every episode of every env drives its own car, drawn on the device at the re-spawn (wheelbase, track width,
 speed and steering limits within +-20 %), plus the steering shift of the reference's TD3 study (examples/train_td3.py:37,
@@ -14,6 +14,10 @@ env's own max_steering_angle, read from the live per-env rows (vec.env_car_param
 --max-episode-steps N: a controller that drives this well never ends an episode, so nothing would ever re-spawn (or draw
 a new car).  The time limit truncates every episode after N steps inside the step kernel (starts staggered over the
 envs); the episodes finished and their mean length / return are read from vec.episode_stats afterwards.
+
+--fused K: the same run with the controller inside the simulate kernels (vec.set_controller): `drive` calls of K steps
+each, one launch sequence per K steps instead of one per step plus the torch glue; the per-step rewards, cte and episode
+ends come back in the call's rollout rows.  The default stays the torch loop below.
 """
 import argparse
 import math
@@ -30,7 +34,7 @@ from tinycarlo_amd.wrapper import CrashTerminationWrapper, CTESparseRewardWrappe
 
 
 def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0", seed=2, randomize=False,
-        max_episode_steps=None):
+        max_episode_steps=None, fused=0):
     vec = TinyCarloVecEnv(bundled_config("config_simple_layout.yaml"), num_envs=num_envs, device=device,
                           autoreset=True, spawn="device")
     if randomize:
@@ -51,22 +55,39 @@ def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0",
     ret = torch.zeros(num_envs, dtype=torch.float64, device=device)
     cte_abs = torch.zeros((), dtype=torch.float64, device=device)
     ended = torch.zeros((), dtype=torch.int64, device=device)
+    if fused:
+        vec.set_controller(k=k, speed=speed)
+        calls = [min(fused, steps - s0) for s0 in range(0, steps, fused)]
+        prepared = {}
+        for n in set(calls):  # (a shorter last call has rows of its own)
+            roll = vec.alloc_rollout(n, keys=("obs", "reward", "terminated", "truncated", "cte"))
+            prepared[n] = (vec.prepare_drive(man.expand(n, num_envs).contiguous(), roll), roll)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        cte, he = vec.out["cte"], vec.out["heading_error"]          # of the previous step, already on the device
-        if randomize:  # this episode's car of every env (the rows change at each re-spawn)
-            max_steer = torch.deg2rad(vec.env_car_params[:, 3])
-        cc[:, 1] = (he + torch.atan2(k * cte, torch.full_like(cte, speed))) / max_steer
-        vec.step_device(cc, man)                                      # one kernel: physics, tracking, camera, wrappers
-        ret += vec.out["reward"]
-        cte_abs += vec.out["cte"].abs().mean()
-        ended += (vec.out["terminated"] | vec.out["truncated"]).sum()
+    if fused:
+        for n in calls:
+            call, roll = prepared[n]
+            call()                                                    # n closed-loop steps, frames into roll["obs"]
+            ret += roll["reward"].sum(0)
+            cte_abs += roll["cte"].abs().mean(1).sum()
+            ended += (roll["terminated"] | roll["truncated"]).sum()
+    else:
+        for _ in range(steps):
+            cte, he = vec.out["cte"], vec.out["heading_error"]      # of the previous step, already on the device
+            if randomize:  # this episode's car of every env (the rows change at each re-spawn)
+                max_steer = torch.deg2rad(vec.env_car_params[:, 3])
+            cc[:, 1] = (he + torch.atan2(k * cte, torch.full_like(cte, speed))) / max_steer
+            vec.step_device(cc, man)                                  # one kernel: physics, tracking, camera, wrappers
+            ret += vec.out["reward"]
+            cte_abs += vec.out["cte"].abs().mean()
+            ended += (vec.out["terminated"] | vec.out["truncated"]).sum()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     out = {"envs": num_envs, "steps": steps, "env_steps_per_s": num_envs * steps / dt,
            "mean_abs_cte_m": float(cte_abs) / steps, "episodes_ended": int(ended),
            "mean_reward_per_step": float(ret.mean()) / steps, "obs_shape": tuple(vec.out["obs"].shape)}
+    if fused:
+        out["steps_per_call"] = fused
     if randomize:
         out["car_episodes_drawn"] = int(vec.car_episode.sum())
     if max_episode_steps:
@@ -85,5 +106,6 @@ if __name__ == "__main__":
     ap.add_argument("--maneuver", type=int, default=3)
     ap.add_argument("--randomize", action="store_true", help="per-episode car constants and steering shift")
     ap.add_argument("--max-episode-steps", type=int, default=None, help="time limit per episode (kept by the step kernel)")
+    ap.add_argument("--fused", type=int, default=0, metavar="K", help="built-in controller: drive() calls of K steps")
     a = ap.parse_args()
-    print(run(a.envs, a.steps, a.maneuver, randomize=a.randomize, max_episode_steps=a.max_episode_steps))
+    print(run(a.envs, a.steps, a.maneuver, randomize=a.randomize, max_episode_steps=a.max_episode_steps, fused=a.fused))

@@ -32,10 +32,12 @@ F_NO_OBSERVATION, F_WRAPPED, F_AUTORESET, F_DEVICE_SPAWN = 1, 2, 4, 8
 S_UTURN_NO_EDGE, S_PICK_EMPTY, S_BAD_SPAWN, S_NOT_RESET, S_SPAWN_WRAPPED = 1, 2, 4, 8, 16
 S_TIME_LIMIT = 32  # tc_env_set_episodes: the episode reached its time limit in this step
 HAS_EPISODES = 1   # TC_HAS_EPISODES: additive within ABI 6
+HAS_CONTROLLER = 1  # TC_HAS_CONTROLLER: likewise
+CTRL_STANLEY = 1    # TC_CTRL_STANLEY
 
 EXPORTS = ["tc_abi_version", "tc_last_error", "tc_map_create", "tc_map_destroy", "tc_env_create", "tc_env_destroy",
            "tc_env_bind", "tc_env_set_camera", "tc_env_set_camera_per_env", "tc_env_set_car", "tc_env_set_car_per_env",
-           "tc_env_set_car_randomization", "tc_env_set_episodes", "tc_env_set_episode_rollout", "tc_env_set_terms", "tc_env_set_spawn_table", "tc_env_set_noise", "tc_noise", "tc_env_obs_bytes", "tc_env_lds_bytes", "tc_env_profile",
+           "tc_env_set_car_randomization", "tc_env_set_episodes", "tc_env_set_episode_rollout", "tc_env_set_controller", "tc_env_set_terms", "tc_env_set_spawn_table", "tc_env_set_noise", "tc_noise", "tc_env_obs_bytes", "tc_env_lds_bytes", "tc_env_profile",
            "tc_env_profile_read", "tc_reset", "tc_step", "tc_step_multi", "tc_env_reserve_steps", "tc_env_launch_info", "tc_env_draw_list_stats", "tc_render",
            "tc_render_segments"]
 
@@ -76,6 +78,11 @@ class Rollout(C.Structure):  # tc_rollout: per-step outputs of tc_step_multi, ea
 class EpisodeBuffers(C.Structure):  # tc_episode_buffers: device arrays of N, length and ret required
     _fields_ = [(n, C.c_void_p) for n in ("length", "ret", "count", "last_length", "last_return", "length_sum",
                                           "return_sum", "limit")]
+
+
+class ControllerC(C.Structure):  # tc_controller: gains by value, the rows device arrays [n_rows][N] (steer_last [N]) or NULL
+    _fields_ = [("kind", C.c_int32), ("n_rows", C.c_int32), ("k", C.c_double), ("speed", C.c_double),
+                ("steer_noise", C.c_void_p), ("steer_rows", C.c_void_p), ("steer_last", C.c_void_p)]
 
 
 class TermC(C.Structure):  # tc_term
@@ -133,6 +140,7 @@ def lib():
     L.tc_env_set_car_randomization.argtypes = [C.c_void_p, _dp, _dp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]
     L.tc_env_set_episodes.argtypes = [C.c_void_p, C.POINTER(EpisodeBuffers), C.c_int32]
     L.tc_env_set_episode_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    L.tc_env_set_controller.argtypes = [C.c_void_p, C.POINTER(ControllerC)]
     L.tc_env_set_terms.argtypes = [C.c_void_p, C.POINTER(TermC), C.c_int32, C.c_void_p]
     L.tc_env_set_spawn_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64]
     L.tc_env_set_noise.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64]

@@ -23,6 +23,7 @@
 #include "../../include/tinycarlo_hip.h"
 #include "tc_device.h"
 #include "tc_rng.h"
+#include "tc_ctrl.h"
 
 // Timing build only (make timing -> libtinycarlo_hip_timing.so, used by tools/phase_clock.py): every wavefront stores
 // the shader clock at its phase boundaries.  The shipped library is compiled without TC_TIMING and contains none of it.
@@ -331,8 +332,12 @@ __device__ __forceinline__ double uni_d(double v) {
 //   bit              compiles in                                                           reads
 //   TC_FEAT_CAR (1)  car constants from the env's row, re-drawn at every re-spawn          StepArgs::cr
 //   TC_FEAT_EP  (2)  episode length / return / time limit and the finished-episode sums    StepArgs::ep
+//   TC_FEAT_CTRL (4) the action computed on the device by the built-in controller           StepArgs::ct
 // A kernel without a bit contains none of that feature's code and compiles as if the feature did not exist.
-enum : unsigned { TC_FEAT_CAR = 1, TC_FEAT_EP = 2, TC_FEAT_ALL = TC_FEAT_CAR | TC_FEAT_EP };
+// The masks with TC_FEAT_CTRL are instantiations of three entry points of their own over the same bodies --
+// tc_drive_step_kernel, tc_drive_env_kernel, tc_drive_envg_kernel (masks 4-7) -- so the twelve-plus-four kernels of masks
+// 0-3 keep their names and their number, and a kernel trace tells a closed-loop call from an open-loop one by name.
+enum : unsigned { TC_FEAT_CAR = 1, TC_FEAT_EP = 2, TC_FEAT_ALL = TC_FEAT_CAR | TC_FEAT_EP, TC_FEAT_CTRL = 4 };
 
 // ---------------------------------------------------------------------------------------------
 // Per-env car constants (tc_env_set_car_per_env): row [env][TC_CAR_NP] of a caller-owned device buffer replaces the
@@ -448,6 +453,36 @@ __device__ __forceinline__ void ep_close(const EpArgs& ep, int env, size_t row, 
   }
   if (ep.len_rows) ep.len_rows[row] = len;
   if (ep.ret_rows) ep.ret_rows[row] = ret;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Built-in controller (tc_env_set_controller, tc_ctrl.h).  Only the TC_FEAT_CTRL kernels (the tc_drive_* entry points,
+// chosen at launch) touch any of this: every other kernel compiles as before.  Per env and step the action is
+//   (speed, tc_ctrl_stanley(cte, he, k, speed, max_steering_angle) + noise[k][env])
+// with cte / he as the env reported them after its previous step (the bound buffers at the first step of a launch, 0 / 0
+// after a re-spawn), max_steering_angle the env's own (its car row under TC_FEAT_CAR), and car_control is never read.
+// The command before noise goes to rows[k][env] / last[env]; a step that applies no action (re-spawn, TC_S_NOT_RESET)
+// stores 0.0 there.
+struct CtrlTab {  // library owned, updated in place by tc_env_set_controller (a captured graph sees new gains)
+  double k, speed;
+};
+struct CtrlArgs {
+  const CtrlTab* tab;
+  const double* noise;  // [K][N] from the first step of this launch on, or NULL
+  double* rows;         // likewise, out
+  double* last;         // [N] out, or NULL
+};
+typedef const __attribute__((address_space(4))) CtrlTab* CtrlTabConst;  // never written by a kernel: scalar loads
+// the steering command of one env (before noise), and the velocity command
+__device__ __forceinline__ double ctrl_command(const CtrlArgs& ct, double cte, double he, double msa, double& speed) {
+  const CtrlTabConst t = (CtrlTabConst)(unsigned long long)ct.tab;
+  speed = t->speed;
+  return tc_ctrl_stanley(cte, he, t->k, speed, msa);
+}
+// by the one lane that stores the env's outputs; row: (step, env) of the launch's per-step rows
+__device__ __forceinline__ void ctrl_store(const CtrlArgs& ct, int env, size_t row, double steer) {
+  if (ct.rows) ct.rows[row] = steer;
+  if (ct.last) ct.last[env] = steer;
 }
 
 // (scalars by value: a reference to the kernel-argument struct would force a copy of it into scratch)
@@ -1034,6 +1069,13 @@ __device__ __forceinline__ void ep_in(const KArgs& a, const EpArgs& ep, unsigned
     lv->ep_ret = ep.ret[env];
   }
 }
+// What the env reported after the step before this launch: caller's buffers -> LiveLds, likewise before live_in (the
+// TC_FEAT_CTRL kernels only: no other kernel reads the two before it has written them).
+__device__ __forceinline__ void ctrl_in(const KArgs& a, unsigned char* smem, int env, const int tid = threadIdx.x) {
+  LiveLds* lv = (LiveLds*)(smem + a.lds.off_live);
+  if (tid == 51) lv->cte = a.b.cte[env];
+  if (tid == 52) lv->he = a.b.heading_error[env];
+}
 __device__ __forceinline__ void ep_out(const KArgs& a, const EpArgs& ep, unsigned char* smem, int env, const int tid = threadIdx.x) {
   const LiveLds* lv = (const LiveLds*)(smem + a.lds.off_live);
   if (tid == 50) {
@@ -1057,13 +1099,15 @@ struct FramePose {
 
 // PER: the env's car constants come from its row of cr.rows (per-env cars, tc_env_set_car_per_env), else a.car.
 // EP: episode length / return / time limit (tc_env_set_episodes); the running pair lives in LiveLds (ep_len, ep_ret).
+// CTRL: the action comes from the built-in controller (tc_env_set_controller), computed from the cte / he the record holds
+// from the step before; car_control is not read.
 template <int K, unsigned FEAT = 0>
 __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, int env, int mode,
                                 const void* car_control, int cdtype,
                                 const int* maneuver, const int* spawn_nodes, const unsigned char* mask,
                                 unsigned int flags, const RollStep& roll, const int tid, MapCache<K>& mc, FramePose& fp,
-                                const CarRows& cr = CarRows(), const EpArgs& ep = EpArgs()) {
-  constexpr bool PER = (FEAT & TC_FEAT_CAR) != 0, EP = (FEAT & TC_FEAT_EP) != 0;
+                                const CarRows& cr = CarRows(), const EpArgs& ep = EpArgs(), const CtrlArgs& ct = CtrlArgs()) {
+  constexpr bool PER = (FEAT & TC_FEAT_CAR) != 0, EP = (FEAT & TC_FEAT_EP) != 0, CTRL = (FEAT & TC_FEAT_CTRL) != 0;
 
   TSTAMP(0);
   TSTAMP_REAL(30);
@@ -1105,6 +1149,7 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
   pinfo.valid = 0;
   bool fresh = false;  // env was (re)spawned in this launch: info is empty (car.py:47-51)
   const double* crow = PER ? cr.rows + (size_t)env * TC_CAR_NP : nullptr;
+  double ctrl_steer = 0.0;  // CTRL: this step's command before noise (0 when no action is applied)
   if (mode == MODE_RESET) {
     if (PER) car_respawn<true>(cr, env, true);
     d_reset(m, PER ? car_of<true>(a.car, crow) : a.car, s, checked_spawn(m, spawn_nodes[env], status));
@@ -1130,7 +1175,11 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
       trunc = 1;
     } else {
       double v, st;
-      if (cdtype == TC_F32) {
+      if (CTRL) {  // (every input is wave-uniform; double arithmetic has no scalar form, so the lanes all compute it)
+        ctrl_steer = ctrl_command(ct, uni_d(lv->cte), uni_d(lv->he),
+                                  PER ? car_ld<true>(crow, TC_CAR_MAX_STEERING_ANGLE) : a.car.max_steering_angle, v);
+        st = ct.noise ? ctrl_steer + uni_d(ct.noise[roll.row0 + env]) : ctrl_steer;
+      } else if (cdtype == TC_F32) {
         v = (double)((const float*)car_control)[2 * env];
         st = (double)((const float*)car_control)[2 * env + 1];
       } else {
@@ -1204,6 +1253,7 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
       if (roll.theta) roll.theta[roll.row0 + env] = s.theta;
       if (roll.velocity) roll.velocity[roll.row0 + env] = s.velocity;
       if (roll.lp_len) roll.lp_len[roll.row0 + env] = s.lp_len;
+      if (CTRL && mode == MODE_STEP) ctrl_store(ct, env, roll.row0 + env, ctrl_steer);
       if (EP) lv->ep_len = ep_len;
       if (!late) {
         lv->reward = reward;
@@ -2440,6 +2490,7 @@ struct StepArgs {
   const int* env_order;  // tc_step_kernel: workgroup w works on env env_order[w] (a permutation of 0..N-1), or NULL = env w
   CarRows cr;            // per-env cars: read by the TC_FEAT_CAR kernels only (last, so every other member keeps its offset)
   EpArgs ep;             // episodes: read by the TC_FEAT_EP kernels only (behind it, for the same reason)
+  CtrlArgs ct;           // built-in controller: read by the TC_FEAT_CTRL kernels only (likewise)
 };
 
 // The launch arguments, read through a pointer the optimiser cannot see through.  Inside the step loop of tc_step_multi
@@ -2473,7 +2524,7 @@ __device__ __forceinline__ bool wants_frame(const StepArgs& sa) {
 // tc_frame_kernel produces every (step, env) frame as a workgroup of its own.
 template <int K, bool CAM, unsigned FEAT>
 __device__ __forceinline__ void env_kernel_body() {
-  constexpr bool EP = (FEAT & TC_FEAT_EP) != 0;
+  constexpr bool EP = (FEAT & TC_FEAT_EP) != 0, CTRL = (FEAT & TC_FEAT_CTRL) != 0;
   extern __shared__ __align__(16) unsigned char smem[];
   // Touching v127 makes the kernel descriptor ask for 128 VGPRs, i.e. caps the SIMD at the 4 wavefronts the launch
   // needs (N = 4096 one-wavefront workgroups = 4 per SIMD).  The camera-less variant uses 74 registers and would fit 6,
@@ -2486,6 +2537,7 @@ __device__ __forceinline__ void env_kernel_body() {
   if (env >= s0.a.N) return;
   if (s0.mode == MODE_RESET && s0.mask && !s0.mask[env]) return;  // whole workgroup skips
   if (EP) ep_in(s0.a, s0.ep, smem, env);
+  if (CTRL) ctrl_in(s0.a, smem, env);
   live_in(s0.a, smem, env, s0.mode, s0.flags);
   const int nsteps = s0.ma.nsteps;
   long long t_prev = 0;
@@ -2515,7 +2567,7 @@ __device__ __forceinline__ void env_kernel_body() {
                           // registers per lane held across the whole step body, raster stage included)
     FramePose fp;
     sim_body<K, FEAT>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
-                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr, sa.ep);
+                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr, sa.ep, sa.ct);
     if (sa.ma.pose_rows) {
       double pose[12];
       cam_pose12(sa.a, env, fp, pose);
@@ -2547,6 +2599,12 @@ __device__ __forceinline__ void env_kernel_body() {
 }
 template <int K, bool CAM, unsigned FEAT>
 __global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) void tc_env_kernel(StepArgs sa_unused) {
+  env_kernel_body<K, CAM, FEAT>();
+}
+// the same body with the built-in controller compiled in (FEAT has TC_FEAT_CTRL: masks 4-7)
+template <int K, bool CAM, unsigned FEAT>
+__global__ __launch_bounds__(TC_NT, (K <= 5 ? TC_MIN_WAVES : K <= 9 ? 3 : 2)) void tc_drive_env_kernel(StepArgs sa_unused) {
+  static_assert((FEAT & TC_FEAT_CTRL) != 0, "the controller's entry point");
   env_kernel_body<K, CAM, FEAT>();
 }
 
@@ -2582,7 +2640,7 @@ struct GroupLds {  // per env of the wavefront: what the reward / termination te
 typedef const __attribute__((address_space(3))) double* LdsDouble;
 template <unsigned FEAT>
 __device__ __forceinline__ void envg_kernel_body() {
-  constexpr bool PER = (FEAT & TC_FEAT_CAR) != 0, EP = (FEAT & TC_FEAT_EP) != 0;
+  constexpr bool PER = (FEAT & TC_FEAT_CAR) != 0, EP = (FEAT & TC_FEAT_EP) != 0, CTRL = (FEAT & TC_FEAT_CTRL) != 0;
   __shared__ GroupLds glds[TC_ENVG_NT / TC_EL];
   extern __shared__ __align__(16) unsigned char gsm[];
   // Highest issue priority: when this kernel shares the chip with the frame kernel of the previous chunk it is the
@@ -2662,6 +2720,10 @@ __device__ __forceinline__ void envg_kernel_body() {
     if (sub == 0) g_ep_ret[grp] = s0.ep.ret[env];
   }
   double cte = 0, he = 0, reward = 0;
+  if (CTRL) {  // what the env reported after the step before this launch: the controller's input at the first step
+    cte = s0.a.b.cte[env];
+    he = s0.a.b.heading_error[env];
+  }
   int terminated = 0, trunc = 0, status = 0;
   const int nsteps = s0.ma.nsteps;
   // The action of step k+1 is fetched at the top of step k.  Vector-memory operations retire in issue order, so a load
@@ -2675,7 +2737,9 @@ __device__ __forceinline__ void envg_kernel_body() {
   auto fetch_action = [&](int kk) {
     const StepArgs& sq = step_args();
     const size_t r = (size_t)kk * sq.a.N + env;
-    if (sq.cdtype == TC_F32)
+    if (CTRL) {  // the command is computed where it is applied: only the noise value (act_d.y) travels
+      if (sq.ct.noise) act_d.y = sq.ct.noise[r];
+    } else if (sq.cdtype == TC_F32)
       act_f = ((const float2*)sq.car_control)[r];
     else
       act_d = ((const double2*)sq.car_control)[r];
@@ -2703,6 +2767,7 @@ __device__ __forceinline__ void envg_kernel_body() {
     pinfo.valid = 0;
     bool fresh = false, track = false;
     int track_man = 0;
+    double ctrl_steer = 0.0;  // CTRL: this step's command before noise (0 when no action is applied)
     if ((flags & TC_F_AUTORESET) && nr) {
       const int cur = cursor;
       int node;
@@ -2722,7 +2787,11 @@ __device__ __forceinline__ void envg_kernel_body() {
       trunc = 1;
     } else {
       double v, st;
-      if (sa.cdtype == TC_F32) {
+      const double* crow = PER ? sa.cr.rows + (size_t)env * TC_CAR_NP : nullptr;
+      if (CTRL) {  // cte / he still hold what the step before left (0 / 0 behind a re-spawn)
+        ctrl_steer = ctrl_command(sa.ct, cte, he, PER ? car_ld<false>(crow, TC_CAR_MAX_STEERING_ANGLE) : a.car.max_steering_angle, v);
+        st = sa.ct.noise ? ctrl_steer + cur_d.y : ctrl_steer;
+      } else if (sa.cdtype == TC_F32) {
         v = (double)cur_f.x;
         st = (double)cur_f.y;
       } else {
@@ -2730,7 +2799,6 @@ __device__ __forceinline__ void envg_kernel_body() {
         st = cur_d.y;
       }
       v = d_np_clip(v, -1.0, 1.0);  // env.py:118
-      const double* crow = PER ? sa.cr.rows + (size_t)env * TC_CAR_NP : nullptr;
       st = d_np_clip(PER ? st + car_ld<false>(crow, TC_CAR_STEERING_SHIFT) : st, -1.0, 1.0);  // (train_td3.py:146-148)
       const int man = cur_m;
       TSTAMP(25);
@@ -2930,6 +2998,7 @@ __device__ __forceinline__ void envg_kernel_body() {
     // ---- this step's rollout rows and pose row
     if (live && sub == 0) {
       if (EP) ep_close(sa.ep, env, row0 + env, fresh, status, ep_len, g_ep_ret[grp], reward, terminated | trunc);
+      if (CTRL) ctrl_store(sa.ct, env, row0 + env, ctrl_steer);
       if (roll.cte) roll.cte[roll.row0 + env] = cte;
       if (roll.heading_error) roll.heading_error[roll.row0 + env] = he;
       if (roll.truncated) roll.truncated[roll.row0 + env] = (unsigned char)trunc;
@@ -2985,6 +3054,12 @@ __device__ __forceinline__ void envg_kernel_body() {
 // 0 = nothing asked for, as for the variants without it.)
 template <unsigned FEAT>
 __global__ __launch_bounds__(TC_ENVG_NT, ((FEAT & TC_FEAT_EP) ? 4 : 0)) void tc_envg_kernel(StepArgs sa_unused) {
+  envg_kernel_body<FEAT>();
+}
+// the same body with the built-in controller compiled in (FEAT has TC_FEAT_CTRL: masks 4-7)
+template <unsigned FEAT>
+__global__ __launch_bounds__(TC_ENVG_NT, ((FEAT & TC_FEAT_EP) ? 4 : 0)) void tc_drive_envg_kernel(StepArgs sa_unused) {
+  static_assert((FEAT & TC_FEAT_CTRL) != 0, "the controller's entry point");
   envg_kernel_body<FEAT>();
 }
 
@@ -3158,7 +3233,7 @@ __global__ __launch_bounds__(TC_NT) void tc_frame_recover_kernel(FrameArgs fa_un
 // under TC_MULTI_SPLIT=0.
 template <int K, bool THICK, int FMT, int RBT, unsigned FEAT>
 __device__ __forceinline__ void step_kernel_body() {
-  constexpr bool EP = (FEAT & TC_FEAT_EP) != 0;
+  constexpr bool EP = (FEAT & TC_FEAT_EP) != 0, CTRL = (FEAT & TC_FEAT_CTRL) != 0;
   extern __shared__ __align__(16) unsigned char smem[];
   const StepArgs& s0 = step_args();
   if ((int)blockIdx.x >= s0.a.N) return;
@@ -3167,6 +3242,7 @@ __device__ __forceinline__ void step_kernel_body() {
                                : s0.a.env0 + (int)blockIdx.x;
   if (s0.mode == MODE_RESET && s0.mask && !s0.mask[env]) return;  // whole workgroup skips
   if (EP) ep_in(s0.a, s0.ep, smem, env);
+  if (CTRL) ctrl_in(s0.a, smem, env);
   live_in(s0.a, smem, env, s0.mode, s0.flags);
   const int nsteps = s0.ma.nsteps;
   long long t_prev = 0;
@@ -3184,7 +3260,7 @@ __device__ __forceinline__ void step_kernel_body() {
                           // registers per lane held across the whole step body, raster stage included)
     FramePose fp;
     sim_body<K, FEAT>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
-                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr, sa.ep);
+                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr, sa.ep, sa.ct);
     if (wants_frame(sa)) {
       int nseg;
       unsigned int used;
@@ -3213,6 +3289,12 @@ __device__ __forceinline__ void step_kernel_body() {
 }
 template <int K, bool THICK, int FMT, int RBT, unsigned FEAT>
 __global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_step_kernel(StepArgs sa_unused) {
+  step_kernel_body<K, THICK, FMT, RBT, FEAT>();
+}
+// the same body with the built-in controller compiled in (FEAT has TC_FEAT_CTRL: masks 4-7)
+template <int K, bool THICK, int FMT, int RBT, unsigned FEAT>
+__global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_drive_step_kernel(StepArgs sa_unused) {
+  static_assert((FEAT & TC_FEAT_CTRL) != 0, "the controller's entry point");
   step_kernel_body<K, THICK, FMT, RBT, FEAT>();
 }
 
@@ -3305,6 +3387,8 @@ static auto lift(F&& f, Among<T, V, Vs...> c, More... more) {
 // minutes for kernel work on cfg3 (make dev DEVK=9 DEVFMT=TC_FMT_RGB: the variants of cfg5; DEVK=9 alone: cfg4) -- and
 // every request maps to them (one-element lists).  Never shipped: the default build has no such macro.
 using Feats = Among<unsigned, 0u, TC_FEAT_CAR, TC_FEAT_EP, TC_FEAT_ALL>;
+// the masks of the tc_drive_* entry points (the built-in controller alone, with per-env cars, with episodes, with both)
+using DriveFeats = Among<unsigned, TC_FEAT_CTRL, TC_FEAT_CTRL | TC_FEAT_CAR, TC_FEAT_CTRL | TC_FEAT_EP, TC_FEAT_CTRL | TC_FEAT_ALL>;
 using Bools = Among<bool, true, false>;
 #ifdef TC_DEV_FAST
 #ifndef TC_DEV_KV
@@ -3345,15 +3429,21 @@ typedef void (*frame_kern_t)(FrameArgs);
 typedef void (*raster_kern_t)(RArgs);
 // all stages in one launch
 static step_kern_t step_kernel_of(int kcode, bool thick, int fmt, unsigned feat) {
+  if (feat & TC_FEAT_CTRL)
+    return lift([](auto kc, auto t, auto f, auto ft) -> step_kern_t { return tc_drive_step_kernel<StepKRb<kc>::K, t, f, StepKRb<kc>::RB, ft>; },
+                Kcodes{kcode}, Thicks{thick}, Fmts{fmt}, DriveFeats{feat});
   return lift([](auto kc, auto t, auto f, auto ft) -> step_kern_t { return tc_step_kernel<StepKRb<kc>::K, t, f, StepKRb<kc>::RB, ft>; },
               Kcodes{kcode}, Thicks{thick}, Fmts{fmt}, Feats{feat});
 }
 // simulate stage alone, by register-cache variant, with or without the camera stage compiled in (without: fewer
 // registers, half the code)
 static step_kern_t env_kernel_of(int kv, bool cam, unsigned feat) {
+  if (feat & TC_FEAT_CTRL)
+    return lift([](auto k, auto c, auto ft) -> step_kern_t { return tc_drive_env_kernel<k, c, ft>; }, Kvars{kv}, Bools{cam}, DriveFeats{feat});
   return lift([](auto k, auto c, auto ft) -> step_kern_t { return tc_env_kernel<k, c, ft>; }, Kvars{kv}, Bools{cam}, Feats{feat});
 }
 static step_kern_t envg_kernel_of(unsigned feat) {
+  if (feat & TC_FEAT_CTRL) return lift([](auto ft) -> step_kern_t { return tc_drive_envg_kernel<ft>; }, DriveFeats{feat});
   return lift([](auto ft) -> step_kern_t { return tc_envg_kernel<ft>; }, Feats{feat});
 }
 // recover: tc_frame_recover_kernel, the pass behind a streamed call's frame launch
@@ -3561,6 +3651,10 @@ struct tc_env {
   EpArgs ep{};           // episodes (tc_env_set_episodes / tc_env_set_episode_rollout); length NULL = feature off
   DevPtr<int> ep_tab;    // device word holding max_episode_steps (updated in place), or NULL
   int ep_rows = 0;       // rows of ep.len_rows / ep.ret_rows
+  CtrlArgs ct{};         // built-in controller (tc_env_set_controller); tab NULL = off
+  DevPtr<CtrlTab> ctrl_tab;  // device copy of the gains (updated in place), or NULL
+  CtrlTab ctrl_host{};   // what ctrl_tab holds
+  int ctrl_rows = 0;     // rows of ct.noise / ct.rows
   bool bound = false;
   int64_t obs_bytes = 0;
   int r_off_tab = 0, r_off_bits = 0, r_lds = 0;
@@ -4034,21 +4128,23 @@ static int raise_lds_limits(const tc_env* e) {
     for (int kcode : {516, 5, 8, 9})
       for (int t = 0; t < 2; t++)
         for (int fmt : {TC_FMT_CLASSES, TC_FMT_RGB}) {
-          for (unsigned feat = 0; feat <= TC_FEAT_ALL; feat++) raise((const void*)step_kernel_of(kcode, t, fmt, feat), lds, "tc_step_kernel");
+          for (unsigned feat = 0; feat <= (TC_FEAT_CTRL | TC_FEAT_ALL); feat++)
+            raise((const void*)step_kernel_of(kcode, t, fmt, feat), lds, (feat & TC_FEAT_CTRL) ? "tc_drive_step_kernel" : "tc_step_kernel");
           raise((const void*)frame_kernel_of(kcode, t, fmt, false), lds, "tc_frame_kernel");
         }
   // tc_envg_kernel's LDS copies of the map (edge records + fat lanepath nodes, see launch()) can exceed the 48 KB default
   const size_t envg_lds = ((size_t)m.total_edges * 48 + 15) / 16 * 16 + (size_t)m.lpN * sizeof(LpNode);
   if (envg_lds > 40 * 1024)
-    for (unsigned feat = 0; feat <= TC_FEAT_ALL; feat++)
-      raise((const void*)envg_kernel_of(feat), (int)(envg_lds < 150 * 1024 ? envg_lds : 150 * 1024), "tc_envg_kernel");
+    for (unsigned feat = 0; feat <= (TC_FEAT_CTRL | TC_FEAT_ALL); feat++)
+      raise((const void*)envg_kernel_of(feat), (int)(envg_lds < 150 * 1024 ? envg_lds : 150 * 1024),
+            (feat & TC_FEAT_CTRL) ? "tc_drive_envg_kernel" : "tc_envg_kernel");
   if (e->r_lds > 48 * 1024)
     for (int t = 0; t < 2; t++)
       for (int fmt : {TC_FMT_CLASSES, TC_FMT_RGB}) raise((const void*)raster_kernel_of(t, fmt), e->r_lds, "tc_raster_kernel");
   if (total > 48 * 1024) {
     static const int kvs[4] = {5, 8, 9, 13};
-    for (int i = 0; i < 32; i++)  // every tc_env_kernel variant
-      raise((const void*)env_kernel_of(kvs[i & 3], (i & 4) == 0, (unsigned)i >> 3), total, "tc_env_kernel");
+    for (int i = 0; i < 64; i++)  // every tc_env_kernel / tc_drive_env_kernel variant
+      raise((const void*)env_kernel_of(kvs[i & 3], (i & 4) == 0, (unsigned)i >> 3), total, (i >> 5) ? "tc_drive_env_kernel" : "tc_env_kernel");
   }
   return rc;
 }
@@ -4314,6 +4410,48 @@ extern "C" int tc_env_set_episode_rollout(tc_env* e, int32_t* length_rows, doubl
   e->ep.len_rows = length_rows;
   e->ep.ret_rows = return_rows;
   e->ep_rows = any ? n_rows : 0;
+  return TC_OK;
+}
+
+extern "C" int tc_env_set_controller(tc_env* e, const tc_controller* c) {
+  if (!e) return TC_E_INVALID;
+  if (!c) {  // feature off (the table stays for a graph captured earlier)
+    memset(&e->ct, 0, sizeof(e->ct));
+    e->ctrl_rows = 0;
+    return TC_OK;
+  }
+  if (c->kind != TC_CTRL_STANLEY) {
+    set_err("tc_env_set_controller: unknown controller kind");
+    return TC_E_INVALID;
+  }
+  if (!isfinite(c->k) || !isfinite(c->speed)) {
+    set_err("tc_env_set_controller: k and speed must be finite");
+    return TC_E_INVALID;
+  }
+  if (c->n_rows < 0) {
+    set_err("tc_env_set_controller: n_rows must not be negative");
+    return TC_E_INVALID;
+  }
+  if ((c->steer_noise || c->steer_rows) && c->n_rows < 1) {
+    set_err("tc_env_set_controller: rows given with n_rows = 0");
+    return TC_E_INVALID;
+  }
+  const bool fresh_tab = !e->ctrl_tab;
+  if (fresh_tab) HIP_TRY(e->ctrl_tab.alloc(1));
+  const CtrlTab want = {c->k, c->speed};
+  if (fresh_tab || memcmp(&want, &e->ctrl_host, sizeof(want)) != 0) {  // (bitwise: -0.0 is another speed than 0.0 to atan2)
+    // (in place: a graph captured earlier keeps reading this table; the copy waits for launches that may still read it.
+    // A call that only changes the row pointers -- kernel arguments -- has nothing to wait for.)
+    const CtrlTab t = want;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(e->ctrl_tab, &t, sizeof(t), hipMemcpyHostToDevice));
+    e->ctrl_host = t;
+  }
+  e->ct.tab = e->ctrl_tab;
+  e->ct.noise = c->steer_noise;
+  e->ct.rows = c->steer_rows;
+  e->ct.last = c->steer_last;
+  e->ctrl_rows = (c->steer_noise || c->steer_rows) ? c->n_rows : 0;
   return TC_OK;
 }
 
@@ -4741,11 +4879,14 @@ static StepArgs step_args_at(const tc_env* e, int mode, const void* cc, int cdty
   sa.ep = e->ep;  // (the per-step rows belong to K-step calls only)
   sa.ep.len_rows = ep_rows && e->ep.len_rows ? e->ep.len_rows + r0 : nullptr;
   sa.ep.ret_rows = ep_rows && e->ep.ret_rows ? e->ep.ret_rows + r0 : nullptr;
+  sa.ct = e->ct;  // (the per-step rows belong to K-step calls only, like the episode rows: tc_step reads and writes none)
+  sa.ct.noise = ep_rows && e->ct.noise ? e->ct.noise + r0 : nullptr;
+  sa.ct.rows = ep_rows && e->ct.rows ? e->ct.rows + r0 : nullptr;
   if (roll) sa.ma.roll = rollout_at(*roll, r0, (size_t)e->obs_bytes, (size_t)e->k.m.C);
   sa.mode = mode;
   sa.cdtype = cdtype;
   sa.flags = flags;
-  sa.car_control = (const char*)cc + r0 * 2 * (cdtype == TC_F32 ? 4 : 8);
+  sa.car_control = cc ? (const char*)cc + r0 * 2 * (cdtype == TC_F32 ? 4 : 8) : nullptr;  // (NULL: a controller acts)
   sa.maneuver = man + r0;
   sa.spawn_nodes = spawn;
   sa.mask = mask;
@@ -4818,7 +4959,8 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
   const int kv = e->kvar;
   // per-env cars (tc_env_set_car_per_env) and episodes (tc_env_set_episodes): the instantiations of the simulate stages
   // with those bits, the same launches otherwise
-  const unsigned feat = (e->cr.rows ? TC_FEAT_CAR : 0u) | (e->ep.length && mode != MODE_RENDER ? TC_FEAT_EP : 0u);
+  const unsigned feat = (e->cr.rows ? TC_FEAT_CAR : 0u) | (e->ep.length && mode != MODE_RENDER ? TC_FEAT_EP : 0u) |
+                        (e->ct.tab && mode == MODE_STEP ? TC_FEAT_CTRL : 0u);  // (the controller: the tc_drive_* entry points)
   const bool all = roll && roll->obs;  // with a rollout every step's frame is wanted; else only the last survives
   const CallPlan plan = plan_call(e, flags, nsteps, e->k.b.obs || all, all);
   const bool do_raster = plan.do_raster;
@@ -5080,16 +5222,22 @@ extern "C" int tc_reset(tc_env* e, const int32_t* spawn_nodes, const uint8_t* ma
 
 extern "C" int tc_step(tc_env* e, const void* car_control, int32_t control_dtype, const int32_t* maneuver,
                        uint32_t flags, void* stream) {
-  if (!car_control || !maneuver || (control_dtype != TC_F32 && control_dtype != TC_F64)) return TC_E_INVALID;
+  if (!maneuver || (control_dtype != TC_F32 && control_dtype != TC_F64)) return TC_E_INVALID;
+  if (!car_control && !(e && e->ct.tab)) return TC_E_INVALID;  // (a built-in controller replaces the action)
   return launch(e, MODE_STEP, car_control, control_dtype, maneuver, nullptr, nullptr, flags, stream);
 }
 
 extern "C" int tc_step_multi(tc_env* e, const void* car_control, int32_t control_dtype, const int32_t* maneuver,
                              int32_t n_steps, uint32_t flags, const tc_rollout* rollout, void* stream) {
-  if (!e || !car_control || !maneuver || (control_dtype != TC_F32 && control_dtype != TC_F64) || n_steps < 1) return TC_E_INVALID;
+  if (!e || !maneuver || (control_dtype != TC_F32 && control_dtype != TC_F64) || n_steps < 1) return TC_E_INVALID;
+  if (!car_control && !e->ct.tab) return TC_E_INVALID;  // (a built-in controller replaces the action)
   if (!e->bound) {
     set_err("tc_env_bind has not been called");
     return TC_E_UNBOUND;
+  }
+  if (e->ct.tab && (e->ct.noise || e->ct.rows) && n_steps > e->ctrl_rows) {
+    set_err("tc_step_multi: more steps than the controller's rows hold (tc_env_set_controller)");
+    return TC_E_INVALID;
   }
   if ((e->ep.len_rows || e->ep.ret_rows) && n_steps > e->ep_rows) {
     set_err("tc_step_multi: more steps than the episode rows hold (tc_env_set_episode_rollout)");
@@ -5147,12 +5295,14 @@ extern "C" int tc_env_launch_info(const tc_env* e, uint32_t flags, int32_t n_ste
   if (fused) *fused = p.fused ? 1 : 0;
   if (kvar) *kvar = (p.fused && e->kframe == 516) ? 5 : e->kvar;  // (the fused kernel of a map with component groups: K = 5)
   if (steps_per_dispatch) *steps_per_dispatch = p.steps;
+  const bool drive = e->ct.tab != nullptr;  // (a controller is installed: the tc_drive_* entry points)
   if (name && name_cap > 0)
     snprintf(name, (size_t)name_cap, "%s",
-             p.fused ? "tc_step_kernel"
-             : p.frames ? (e->tune.env_grouped ? "tc_envg_kernel+tc_frame_kernel" : "tc_env_kernel+tc_frame_kernel")
-             : p.do_raster ? "tc_env_kernel+tc_raster_kernel"
-                           : "tc_env_kernel");
+             p.fused ? (drive ? "tc_drive_step_kernel" : "tc_step_kernel")
+             : p.frames ? (e->tune.env_grouped ? (drive ? "tc_drive_envg_kernel+tc_frame_kernel" : "tc_envg_kernel+tc_frame_kernel")
+                                               : (drive ? "tc_drive_env_kernel+tc_frame_kernel" : "tc_env_kernel+tc_frame_kernel"))
+             : p.do_raster ? (drive ? "tc_drive_env_kernel+tc_raster_kernel" : "tc_env_kernel+tc_raster_kernel")
+                           : (drive ? "tc_drive_env_kernel" : "tc_env_kernel"));
   return TC_OK;
 }
 

@@ -230,6 +230,10 @@ class TinyCarloVecEnv(gym.Env):
         self._time_limit = 0                                   # shared max_episode_steps, 0 = none
         self._time_limit_per_env: Optional[torch.Tensor] = None  # [N] int32 device tensor, or None
         self._ep_rows: Tuple[int, int] = (0, 0)                # data pointers of the episode rows installed last
+        # built-in controller (set_controller): its gains, or None = off; what the library holds of a call's rows
+        self._ctrl: Optional[Dict[str, float]] = None
+        self._ctrl_rows: Tuple[int, int, int] = (0, 0, 0)      # data pointers of the noise / steer rows installed last, rows
+        self.steer_last: Optional[torch.Tensor] = None         # [N] f64: the controller's command of the last step
         self._setup_device()
         self._rngs: List[Optional[np.random.Generator]] = [None] * self.num_envs
         self._was_reset = False
@@ -516,6 +520,92 @@ class TinyCarloVecEnv(gym.Env):
                                                            K if (ptrs[0] or ptrs[1]) else 0), "tc_env_set_episode_rollout")
             self._ep_rows = ptrs
 
+    # ------------------------------------------------------------------ built-in controller (closed-loop K-step calls)
+    CTRL_ROLLOUT_KEYS = ("steer",)
+
+    def set_controller(self, k: Optional[float] = 4.0, speed: float = 0.4) -> None:
+        """Installs the Stanley lateral controller of the reference's examples/stanley_control.py:56-57 into the simulate
+        kernels (tc_env_set_controller): every step then computes its own action ``(speed, (heading_error + atan2(k * cte,
+        speed)) * 180 / pi / max_steering_angle)`` from the env's previous step -- each env with its own
+        ``max_steering_angle`` under per-env cars -- so a closed loop runs inside one ``drive`` call.  ``steer_last`` holds
+        the command of the last step.  New gains reach a captured HIP graph without re-capture.  ``set_controller(None)``
+        switches it off: ``step`` / ``step_multi`` apply their ``car_control`` again (while it is on they ignore it; a
+        single step takes no noise and writes no label row, only ``steer_last``)."""
+        if k is None:
+            if self._ctrl is not None:
+                with torch.cuda.device(self.device):
+                    nat.check(nat.lib().tc_env_set_controller(self._h, None), "tc_env_set_controller")
+            self._ctrl, self._ctrl_rows, self.steer_last = None, (0, 0, 0), None
+            return
+        k, speed = float(k), float(speed)
+        if not (np.isfinite(k) and np.isfinite(speed)):
+            raise ValueError(f"k and speed must be finite, got {k}, {speed}")
+        if self.steer_last is None:
+            self.steer_last = torch.zeros(self.num_envs, dtype=torch.float64, device=self.device)
+        self._ctrl = {"k": k, "speed": speed}
+        self._push_controller(0, 0, 0)  # (the rows belong to a call: the next drive / step_multi installs its own)
+
+    def _push_controller(self, noise_ptr: int, rows_ptr: int, n_rows: int) -> None:
+        c = nat.ControllerC(nat.CTRL_STANLEY, n_rows if (noise_ptr or rows_ptr) else 0, self._ctrl["k"], self._ctrl["speed"],
+                            noise_ptr or None, rows_ptr or None, self.steer_last.data_ptr())
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().tc_env_set_controller(self._h, C.byref(c)), "tc_env_set_controller")
+        self._ctrl_rows = (noise_ptr, rows_ptr, n_rows)
+
+    def _install_ctrl_rows(self, steer_noise: Optional[torch.Tensor], rollout: Optional[Dict[str, torch.Tensor]], K: int) -> None:
+        """the noise / label rows of the call about to be issued (host-side bookkeeping only: the gains do not change)"""
+        st = rollout.get("steer") if rollout else None
+        want = (steer_noise.data_ptr() if steer_noise is not None else 0, st.data_ptr() if st is not None else 0, K)
+        if not (want[0] or want[1]):
+            want = (0, 0, 0)
+        if want != self._ctrl_rows:
+            self._push_controller(*want)
+
+    def drive(self, maneuver: torch.Tensor, rollout: Optional[Dict[str, torch.Tensor]] = None,
+              steer_noise: Optional[torch.Tensor] = None) -> None:
+        """K closed-loop steps in ONE call: ``step_multi`` with every step's action computed on the device by the
+        controller of ``set_controller``.  maneuver [K, N] int32; steer_noise [K, N] float64 (optional) is added to the
+        command of step k before it is applied (the exploration noise of examples/train_stanley_il.py's data
+        collection); ``rollout["steer"]`` (``alloc_rollout(K, keys=(..., "steer"))``) receives the command BEFORE noise,
+        the imitation-learning label.  Bit-identical to K ``step_device`` calls with the action computed on the host from
+        ``out["cte"]`` / ``out["heading_error"]`` before each."""
+        self.prepare_drive(maneuver, rollout, steer_noise)()
+
+    def prepare_drive(self, maneuver: torch.Tensor, rollout: Optional[Dict[str, torch.Tensor]] = None,
+                      steer_noise: Optional[torch.Tensor] = None) -> "PreparedStepMulti":
+        """`drive` as a checked, reusable call object (see `prepare_step_multi`); its rows are installed at once, so the
+        object can be captured into a HIP graph right away."""
+        if self._ctrl is None:
+            raise RuntimeError("drive() needs set_controller() first")
+        if maneuver.dim() != 2 or int(maneuver.shape[0]) < 1 or int(maneuver.shape[1]) != self.num_envs:
+            raise ValueError(f"maneuver must be [K, {self.num_envs}], got {tuple(maneuver.shape)}")
+        K = int(maneuver.shape[0])
+        if maneuver.device != self.device or maneuver.dtype != torch.int32 or not maneuver.is_contiguous():
+            raise ValueError("drive takes a contiguous int32 device tensor as maneuver")
+        if steer_noise is not None and (tuple(steer_noise.shape) != (K, self.num_envs) or steer_noise.dtype != torch.float64 or
+                                        steer_noise.device != self.device or not steer_noise.is_contiguous()):
+            raise ValueError(f"steer_noise must be a contiguous float64 tensor of shape ({K}, {self.num_envs}) on {self.device}")
+        r = self._check_rollout(rollout, K)
+        call = PreparedStepMulti(self, None, maneuver, rollout, r, K, steer_noise)
+        self._install_ctrl_rows(steer_noise, rollout, K)
+        return call
+
+    def drive_step(self, maneuver: torch.Tensor) -> None:
+        """One closed-loop step (tc_step with the controller's action): `step_device` without a car_control."""
+        if self._ctrl is None:
+            raise RuntimeError("drive_step() needs set_controller() first")
+        if not self._was_reset:
+            raise RuntimeError("step() before reset()")
+        if (tuple(maneuver.shape) != (self.num_envs,) or maneuver.device != self.device or maneuver.dtype != torch.int32 or
+                not maneuver.is_contiguous()):
+            raise ValueError(f"drive_step takes a contiguous int32 device tensor of shape ({self.num_envs},) as maneuver")
+        self._note_fresh()
+        self._install_ctrl_rows(None, None, 0)
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().tc_step(self._h, None, nat.F64, maneuver.data_ptr(), self._flags(), self._stream()), "tc_step")
+        self._keep = (maneuver,)
+        self._step_serial += 1
+
     # ------------------------------------------------------------------ fused reward / termination wrappers
     def set_terms(self, terms: Sequence[Term]) -> None:
         """Installs the wrapper stack `terms` (innermost first) into the step kernel (tc_env_set_terms); the
@@ -693,6 +783,8 @@ class TinyCarloVecEnv(gym.Env):
         if not self._was_reset:
             raise RuntimeError("step() before reset()")
         self._note_fresh()
+        if self._ctrl is not None:  # (a controller acts: the rows of an earlier drive call are not this step's)
+            self._install_ctrl_rows(None, None, 0)
         dt = nat.F64 if car_control.dtype == torch.float64 else nat.F32
         with torch.cuda.device(self.device):
             nat.check(nat.lib().tc_step(self._h, car_control.data_ptr(), dt, maneuver.data_ptr(), self._flags(),
@@ -723,7 +815,7 @@ class TinyCarloVecEnv(gym.Env):
                 "status": ((K, N), i32), "x": ((K, N), f64), "y": ((K, N), f64), "theta": ((K, N), f64),
                 "velocity": ((K, N), f64), "laneline_distances": ((K, N, Cn), f64), "nearest_edge": ((K, N, Cn), i32),
                 "local_path": ((K, N, 8), i32), "lp_len": ((K, N), i32),
-                "episode_length": ((K, N), i32), "episode_return": ((K, N), f64)}
+                "episode_length": ((K, N), i32), "episode_return": ((K, N), f64), "steer": ((K, N), f64)}
 
     def reserve_steps(self, n_steps: int) -> None:
         """Sizes the library's scratch ring for K-step calls that render observations (tc_env_reserve_steps): done
@@ -738,14 +830,17 @@ class TinyCarloVecEnv(gym.Env):
         """Device tensors for the per-step outputs of `step_multi`: [n_steps, num_envs, ...] each."""
         K, dev = int(n_steps), self.device
         shapes = self._rollout_shapes(K)
-        if keys == "all":  # (the episode rows only while the accounting is on)
-            keys = self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS + (self.EPISODE_ROLLOUT_KEYS if self._episodes is not None else ())
+        if keys == "all":  # (the episode rows only while the accounting is on, the controller's while one is installed)
+            keys = self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS + (self.EPISODE_ROLLOUT_KEYS if self._episodes is not None else ()) + \
+                (self.CTRL_ROLLOUT_KEYS if self._ctrl is not None else ())
         for k in keys:
             if k not in shapes:
                 raise ValueError(f"unknown rollout key {k!r}; choose from "
-                                 f"{self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS + self.EPISODE_ROLLOUT_KEYS}")
+                                 f"{self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS + self.EPISODE_ROLLOUT_KEYS + self.CTRL_ROLLOUT_KEYS}")
             if k in self.EPISODE_ROLLOUT_KEYS and self._episodes is None:
                 raise ValueError(f"rollout key {k!r} needs track_episodes() / set_time_limit() first")
+            if k in self.CTRL_ROLLOUT_KEYS and self._ctrl is None:
+                raise ValueError(f"rollout key {k!r} needs set_controller() first")
         return {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=dev) for k in keys}
 
     def rollout_info(self, rollout: Dict[str, torch.Tensor], k: int) -> Dict[str, Any]:
@@ -792,6 +887,10 @@ class TinyCarloVecEnv(gym.Env):
             raise ValueError("car_control must be float32|float64 and maneuver int32")
         if not (car_control.is_contiguous() and maneuver.is_contiguous()):
             raise ValueError("step_multi takes contiguous tensors")
+        return PreparedStepMulti(self, car_control, maneuver, rollout, self._check_rollout(rollout, K), K)
+
+    def _check_rollout(self, rollout: Optional[Dict[str, torch.Tensor]], K: int) -> "nat.Rollout":
+        """the tc_rollout of a K-step call from its checked tensors; sizes the library's scratch for the call"""
         r = nat.Rollout()
         if rollout:
             want = self._shape_cache.get(K)
@@ -807,10 +906,14 @@ class TinyCarloVecEnv(gym.Env):
                     if self._episodes is None:
                         raise ValueError(f"rollout[{k!r}] needs track_episodes() / set_time_limit() first")
                     continue
+                if k in self.CTRL_ROLLOUT_KEYS:  # likewise: installed per call (tc_env_set_controller)
+                    if self._ctrl is None:
+                        raise ValueError(f"rollout[{k!r}] needs set_controller() first")
+                    continue
                 setattr(r, k, t.data_ptr())
         if K > 1 and not (self.no_observation and self.render_mode is None):
             self.reserve_steps(K)  # (no-op once the scratch covers K: the call itself never allocates)
-        return PreparedStepMulti(self, car_control, maneuver, rollout, r, K)
+        return r
 
     def launch_info(self, n_steps: int = 1) -> Dict[str, Any]:
         """What a call of n_steps steps launches with the current settings (tc_env_launch_info): for benchmark labels."""
@@ -849,7 +952,9 @@ class TinyCarloVecEnv(gym.Env):
                 "episodes": None if self._episodes is None else {
                     "max_episode_steps": int(self._time_limit),
                     "per_env": None if self._time_limit_per_env is None else self._time_limit_per_env.detach().cpu().clone(),
-                    "stats": {k: v.detach().cpu().clone() for k, v in self._episodes.items()}}}
+                    "stats": {k: v.detach().cpu().clone() for k, v in self._episodes.items()}},
+                # built-in controller: its gains
+                "controller": None if self._ctrl is None else dict(self._ctrl)}
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
         if int(sd["num_envs"]) != self.num_envs:
@@ -892,6 +997,11 @@ class TinyCarloVecEnv(gym.Env):
             self.set_time_limit(int(eps["max_episode_steps"]), per_env=eps.get("per_env"))
             for k, v in eps["stats"].items():
                 self._episodes[k].copy_(v)
+        ctl = sd.get("controller")  # (absent in older checkpoints: off)
+        if ctl is None:
+            self.set_controller(None)
+        else:
+            self.set_controller(k=ctl["k"], speed=ctl["speed"])
         self._step_serial += 1
 
     def request_reset(self, mask: torch.Tensor) -> None:
@@ -981,15 +1091,17 @@ class PreparedStepMulti:
     """A checked `step_multi` call (`TinyCarloVecEnv.prepare_step_multi`): calling it enqueues tc_step_multi with the
     tensors it was prepared with, on the stream current at that moment."""
 
-    __slots__ = ("env", "_keep", "_args", "_rollout_ref", "K")
+    __slots__ = ("env", "_keep", "_args", "_rollout_ref", "K", "_noise")
 
-    def __init__(self, env, car_control, maneuver, rollout, r, K):
+    def __init__(self, env, car_control, maneuver, rollout, r, K, steer_noise=None):
         self.env = env
         self.K = K
         self._keep = (car_control, maneuver, rollout)   # the tensors stay alive as long as the call can be issued
+        self._noise = steer_noise                       # `prepare_drive`: the controller's noise rows (car_control None)
         self._rollout_ref = r
-        dt = nat.F64 if car_control.dtype == torch.float64 else nat.F32
-        self._args = (car_control.data_ptr(), dt, maneuver.data_ptr(), K, C.byref(r) if rollout else None)
+        dt = nat.F32 if car_control is not None and car_control.dtype == torch.float32 else nat.F64
+        self._args = (car_control.data_ptr() if car_control is not None else None, dt, maneuver.data_ptr(), K,
+                      C.byref(r) if rollout else None)
 
     def __call__(self) -> None:
         env = self.env
@@ -1005,6 +1117,10 @@ class PreparedStepMulti:
         a = self._args
         if env._episodes is not None:
             env._install_episode_rows(self._keep[2], self.K)
+        if env._ctrl is not None:
+            env._install_ctrl_rows(self._noise, self._keep[2], self.K)
+        elif a[0] is None:
+            raise RuntimeError("a drive() call needs the controller it was prepared with (set_controller)")
         if torch.cuda.current_device() == env.device.index:
             rc = nat.lib().tc_step_multi(env._h, a[0], a[1], a[2], a[3], env._flags(), a[4], env._stream())
         else:
@@ -1012,7 +1128,7 @@ class PreparedStepMulti:
                 rc = nat.lib().tc_step_multi(env._h, a[0], a[1], a[2], a[3], env._flags(), a[4], env._stream())
         if rc != 0:
             nat.check(rc, "tc_step_multi")
-        env._keep = self._keep
+        env._keep = self._keep + (self._noise,)  # (the library holds their pointers until the next call installs its own)
         env._step_serial += 1
         if dbg:
             env._debug_print(f"step_multi[{self.K}]", t_dbg)
