@@ -24,6 +24,7 @@
 #include "tc_device.h"
 #include "tc_rng.h"
 #include "tc_ctrl.h"
+#include "tc_clip.h"
 
 // Timing build only (make timing -> libtinycarlo_hip_timing.so, used by tools/phase_clock.py): every wavefront stores
 // the shader clock at its phase boundaries.  The shipped library is compiled without TC_TIMING and contains none of it.
@@ -298,6 +299,7 @@ struct KArgs {
   // tc_frame_kernel: the first seg_lds_cap entries of the frame's draw list stay in LDS (byte offset seg_lds_off of the
   // workgroup's block, behind both stages' buffers) instead of going through global memory; 0 in every other launch
   int seg_lds_off, seg_lds_cap;
+  int clip_merge;  // TC_CLIP_MERGE: 1 = a pair of clip passes runs as one pass where tc_clip.h allows it, 0 = always four
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -728,36 +730,77 @@ __device__ __forceinline__ void cam_group_regs(const KArgs& a, const MapCache<K>
 #pragma unroll
   for (int k = 0; k < K; k++) ff[k] = k * TC_NT + tid < ne ? (int)flg[mc.ed[k].x] | ((int)flg[mc.ed[k].y] << 8) : 0;
   // camera.py:71-74, 75-77 (plane z = -1e-7, flag idx_front), then 81-83, 84-86 (plane z = -max_range, flag
-  // idx_in_range): one copy of the pass, looped
+  // idx_in_range): one copy of the pass, looped.  Where tc_clip.h allows it -- both lists of a pair non-empty, every
+  // target of the two lists its own node, no edge that the first pass would add to the second's list -- the pair runs
+  // as ONE pass over the concatenated list (one compaction, one LDS round trip, one batch of divisions, one flag
+  // refresh); otherwise the first list alone is used, it sits at the head of the concatenated one, and the second
+  // pass follows in its literal form from the refreshed flags.
+  const bool merge_on = a.clip_merge != 0;
 #pragma nounroll
   for (int pass = 0; pass < 4 && !DBG_ON(a.dbg, DBG_SKIP_CLIP); pass++) {
-    const int bit = pass < 2 ? 1 : 2;
-    const bool target_e0 = (pass & 1) == 0;
+    const int bit = pass < 2 ? 1 : 2, mark = pass < 2 ? TC_CLIP_MARK0 : TC_CLIP_MARK1;
     const double tz = pass < 2 ? -0.0000001 : -max_range;
-    int sel = 0;  // bit k: slot k straddles the plane in the direction of this pass
+    int s1 = 0, s2 = 0;  // bit k: slot k is in the pair's first (target e[0]) / second (target e[1]) list, flags as they stand
 #pragma unroll
     for (int k = 0; k < K; k++) {
-      const bool fa = ff[k] & bit, fb = (ff[k] >> 8) & bit;
-      sel |= (target_e0 ? (!fa && fb) : (fa && !fb)) ? 1 << k : 0;
+      const int w = tc_clip_sel(ff[k] & 0xff, ff[k] >> 8, bit);
+      s1 |= w == 1 ? 1 << k : 0;
+      s2 |= w == 2 ? 1 << k : 0;
     }
-    if (__ballot(sel != 0) != 0) {
-      int n = 0;
+    const bool any1 = __ballot(s1 != 0) != 0, any2 = __ballot(s2 != 0) != 0;
+    if (!(pass & 1) && !any1) {  // nothing for the first pass: the flags stand, s2 is the second pass's list
+      TSTAMP(17 + pass);  // (a pass that does not run still leaves its stamp: phase_clock.py reads all of 17-19 per frame)
+      pass++;
+    }
+    bool merged = !(pass & 1) && merge_on && any2;  // (wave-uniform, like every decision below)
+    if (pass & 1) {
+      if (!any2) {
+        if (pass < 3) TSTAMP(17 + pass);
+        continue;
+      }
+      s1 = 0;
+    } else if (!merged) {
+      s2 = 0;
+    }
+    int n = 0, n1 = 0;
+#pragma nounroll
+    for (int h = 0; h < 2; h++) {  // the first list's entries, then the second's
+      const int sm = h ? s2 : s1;
+      if (__ballot(sm != 0) == 0) continue;
 #pragma unroll
       for (int k = 0; k < K; k++) {
-        const bool s_k = (sel >> k) & 1;
+        const bool s_k = (sm >> k) & 1;
         const unsigned long long mk = __ballot(s_k);
         if (s_k) {
           const int j = n + wave_rank(mk);
-          const int t = target_e0 ? mc.ed[k].x : mc.ed[k].y, o = target_e0 ? mc.ed[k].y : mc.ed[k].x;
+          const int t = h ? mc.ed[k].y : mc.ed[k].x, o = h ? mc.ed[k].x : mc.ed[k].y;
           list[2 * j] = k * TC_NT + tid;
           list[2 * j + 1] = t | (o << 16);
+          // "target of the first list" for the test below (lanes sharing the node write the same byte)
+          if (merged && h == 0) flg[t] = (unsigned char)((ff[k] & 0xff) | mark);
         }
         n += __popcll(mk);
       }
-      lds_sync();
-      // the usual case: every straddling edge has a target node of its own -> one move each, order irrelevant
-      bool dup = n > TC_NT;
-      int mine = 0;
+      if (h == 0) n1 = n;
+    }
+    lds_sync();
+    if (merged) {  // condition (c) of tc_clip.h: an edge the first pass would hand to the second
+      bool joins = false;
+#pragma unroll
+      for (int k = 0; k < K; k++)
+        if (k * TC_NT + tid < ne && !(ff[k] & bit) && !((ff[k] >> 8) & bit))
+          joins |= tc_clip_joins_second(flg[mc.ed[k].x], flg[mc.ed[k].y], bit, mark) != 0;
+      if (__ballot(joins) != 0) {
+        merged = false;
+        n = n1;
+      }
+    }
+    // the usual case: every straddling edge has a target node of its own -> one move each, order irrelevant
+    bool dup;
+    int mine;
+    for (;;) {
+      dup = n > TC_NT;
+      mine = 0;
       if (n <= TC_NT) {
         // lane j < n takes list entry j; the target nodes are compared lane against lane through v_readlane (the loop
         // over the list in LDS was one dependent LDS round trip per entry, four passes per frame)
@@ -768,22 +811,30 @@ __device__ __forceinline__ void cam_group_regs(const KArgs& a, const MapCache<K>
           dup |= tid < n && j != tid && tj == my_t;
         }
       }
-      if (__ballot(dup) == 0) {
-        if (tid < n) {
-          const int t = mine & 0xffff, o = (unsigned)mine >> 16;
-          cam_move_to_plane(Px, Py, Pz, o, t, tz);
-          unsigned int f = flg[t] | (unsigned)bit;
-          if (pass < 2) f = (f & ~2u) | (Pz[t] > -max_range ? 2u : 0u);
-          flg[t] = (unsigned char)f;
-        }
-      } else {
-        cam_chain_replay(Px, Py, Pz, flg, bit, tz, list, n, max_range, pass < 2, tid);
-      }
-      lds_sync();
-#pragma unroll
-      for (int k = 0; k < K; k++) ff[k] = k * TC_NT + tid < ne ? (int)flg[mc.ed[k].x] | ((int)flg[mc.ed[k].y] << 8) : 0;
+      dup = __ballot(dup) != 0;
+      if (!merged || !dup) break;
+      merged = false;  // a target shared between the lists or inside one: the first list alone, the literal way
+      n = n1;
     }
+    if (!dup) {
+      if (tid < n) {
+        const int t = mine & 0xffff, o = (unsigned)mine >> 16;
+        cam_move_to_plane(Px, Py, Pz, o, t, tz);
+        unsigned int f = flg[t] | (unsigned)bit;
+        if (pass < 2) f = (f & ~2u) | (Pz[t] > -max_range ? 2u : 0u);
+        flg[t] = (unsigned char)f;
+      }
+    } else {
+      cam_chain_replay(Px, Py, Pz, flg, bit, tz, list, n, max_range, pass < 2, tid);
+    }
+    lds_sync();
+#pragma unroll
+    for (int k = 0; k < K; k++) ff[k] = k * TC_NT + tid < ne ? (int)flg[mc.ed[k].x] | ((int)flg[mc.ed[k].y] << 8) : 0;
     if (pass < 3) TSTAMP(17 + pass);
+    if (merged) {  // both passes of the pair are done: the second one's interval reads as empty
+      pass++;
+      if (pass < 3) TSTAMP(17 + pass);
+    }
   }
   TSTAMP(5);
   // Only nodes in front AND in range can be "visible" (camera.py:92-93), and an edge is drawn when one of its ends is
@@ -3488,7 +3539,7 @@ extern "C" int tc_abi_version(void) { return TC_ABI_VERSION; }
 // Every switch the library reads from the environment, parsed once per tc_env_create / tc_map_create by read_tuning()
 // -- the only place that looks at the environment.  INTEGRATION.md calls the shipped ones result-neutral.
 struct Tuning {
-  int fuse, env_grouped, envg_map_lds, first_per_env, stream, groups, seg_lds, frame_order, cand_grid;  // on / off
+  int fuse, env_grouped, envg_map_lds, first_per_env, stream, groups, seg_lds, frame_order, cand_grid, clip_merge;  // on / off
   // tc_step_multi with observations, split form (default; 0 selects the fused K-step kernel): ONE
   // simulate launch loops over the K steps and leaves K draw lists per env, ONE raster launch of K x N workgroups
   // draws them.  Why: a frame costs between ~10 k clocks (nothing in view) and ~80 k (60 segments) to rasterise and an
@@ -3535,6 +3586,7 @@ static Tuning read_tuning() {
       {"TC_FRAME_ORDER", "1", "0: frame workgroups in env order instead of heaviest first"},
       {"TC_STEP_ORDER", "8", "single steps re-deal the envs to workgroups every n-th tc_step; <= 0: never"},
       {"TC_CAND_GRID", "1", "0: nearest-edge queries scan every edge instead of the candidate grid"},
+      {"TC_CLIP_MERGE", "1", "0: the camera stage always runs its four clip passes one by one"},
 #ifdef TC_ABLATE
       {"TC_PRINT_LDS", "", "set: tc_env_create prints its LDS layout"},
 #endif
@@ -3567,6 +3619,7 @@ static Tuning read_tuning() {
   t.seg_lds = on("TC_SEG_LDS");
   t.frame_order = on("TC_FRAME_ORDER");
   t.cand_grid = on("TC_CAND_GRID");
+  t.clip_merge = on("TC_CLIP_MERGE");
   t.pipe = positive("TC_CHUNK") > 0;
   t.chunk = t.pipe ? positive("TC_CHUNK") : 16;
   t.frame_streams = atoi(sw("TC_FRAME_STREAMS")) == 1 ? 1 : 2;
@@ -4204,6 +4257,7 @@ extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const 
   if (rc != TC_OK) return rc;
   e->k.m = map->d;
   e->k.N = num_envs;
+  e->k.clip_merge = e->tune.clip_merge;
   e->k.car.T = car->T;
   e->k.car.has_steering_speed = car->has_steering_speed;
   e->k.car.has_max_acceleration = car->has_max_acceleration;

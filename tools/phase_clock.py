@@ -31,7 +31,8 @@ NAMES = ["entry -> tracking done (phase A)", "state / info write-back", "lane-li
 # (the first one then contains a whole batch and the last one goes negative); the first-level table is not affected.
 SUB = [("A: state from LDS, action, kinematics", 0, 23), ("A: lanepath tracking (dependent fat-node loads)", 23, 1),
        ("B: node distances + sync", 2, 14), ("B: 5 x (edge scan + wave argmin)", 14, 15), ("B: per-layer tail (loads, bounds, distance)", 15, 16),
-       ("clip pass 1 (behind -> front)", 4, 17), ("clip pass 2", 17, 18), ("range flags + clip pass 3", 18, 19), ("clip pass 4", 19, 5),
+       ("clip pass 1 (behind -> front), or merged pair 1+2", 4, 17), ("clip pass 2 (~0 when merged or empty)", 17, 18),
+       ("range flags + clip pass 3, or merged pair 3+4", 18, 19), ("clip pass 4 (~0 when merged or empty)", 19, 5),
        ("setup: table offsets, segment fetch", 9, 20), ("  .. probe 9 -> a second probe right behind it", 9, 26), ("  .. -> first instructions of the set-up (bimodal: issue contention)", 26, 27), ("  .. -> second argument (same line)", 27, 24), ("  .. to the per-segment branch", 24, 25),
        ("  .. draw-list entry from LDS", 25, 20), ("setup: ThickLine quad (sqrt, div, rounding)", 20, 21),
        ("setup: fill events", 21, 22), ("setup: table writes + sync", 22, 10)]
