@@ -615,6 +615,7 @@ __device__ inline int d_np_int32(double v) {
 // One bit per pixel and layer; `bits` points at the plane of the segment's layer for the current band.
 #define TC_XY_SHIFT 16
 #define TC_XY_ONE 65536
+#include "tc_fill.h"
 
 struct Ras {
   unsigned int* bits;
@@ -907,91 +908,20 @@ __device__ inline long long sel4(long long a0, long long a1, long long a2, long 
 }
 
 // FillConvexPoly(v[4], shift = 16, LINE_8) = 4 outline edges (Line2, above) + the scanline fill below.
-// FillConvexPoly's two edge walkers as closed-form pieces.  The scanline loop of drawing.cpp is a
-// sequence of "events" (a walker reaches the end row of its polygon edge and picks the next one, with a
-// shared budget of npts edges) between which both walkers just add dx per row.  This runs the event
-// part literally -- only at event rows -- and records every new piece (start row, x at that row, dx per
-// row, walker id); row r of walker w is then xs + (r - y_start) * dx of its latest piece.  At most 4
-// pieces (every successful update consumes at least one of the 4 edges).
-//   py/px/pdx: LDS tables [4]; returns number of pieces; wmask bit s = walker of piece s;
-//   rows [y_first, y_last] are the ones the fill draws (empty when y_last < y_first).
+// FillConvexPoly's two edge walkers as closed-form pieces: tc_fill.h has the event part, as the literal loop nest and in
+// the loop-free form that runs here (one lane per segment: a data-dependent nest costs the wavefront the union of its
+// lanes' paths).  -DTC_FILL_LITERAL builds the literal form back in -- a build switch, not a kernel argument: the frame
+// kernel has no scalar register to spare for one.
+//   py/pv: LDS tables [4] (entries past the returned count are leftovers); returns number of pieces; wmask bit s =
+//   walker of piece s; rows [y_first, y_last] are the ones the fill draws (empty when y_last < y_first).
 __device__ inline int r_fill_events(int W, int H, long long qx0, long long qx1, long long qx2, long long qx3,
                                     long long qy0, long long qy1, long long qy2, long long qy3, int* py, int* pv,
                                     int& wmask, int& y_first, int& y_last) {
-  // Integer-only part: which polygon edge each walker switches to at which row.  pv[s] = idx0 | idx << 2
-  // (xs = vx[idx0], xe = vx[idx], end row = ty[idx]); the slope of piece s is computed by r_fill_slope.
-  const int npts = 4, shift = TC_XY_SHIFT;
-  const int delta = 1 << shift >> 1;
-  wmask = 0;
-  y_first = 0;
-  y_last = -1;
-  int imin = 0;
-  long long xmin = qx0, xmax = qx0, ymin = qy0, ymax = qy0;
-#pragma unroll
-  for (int i = 1; i < npts; i++) {
-    long long x = sel4(qx0, qx1, qx2, qx3, i), y = sel4(qy0, qy1, qy2, qy3, i);
-    if (y < ymin) {
-      ymin = y;
-      imin = i;
-    }
-    if (y > ymax) ymax = y;
-    if (x > xmax) xmax = x;
-    if (x < xmin) xmin = x;
-  }
-  xmin = (xmin + delta) >> shift;
-  xmax = (xmax + delta) >> shift;
-  ymin = (ymin + delta) >> shift;
-  ymax = (ymax + delta) >> shift;
-  if (d_wrap32(xmax) < 0 || d_wrap32(ymax) < 0 || d_wrap32(xmin) >= W || d_wrap32(ymin) >= H) return 0;
-  if (ymax > H - 1) ymax = H - 1;
-  const int ty0 = d_wrap32((qy0 + delta) >> shift), ty1 = d_wrap32((qy1 + delta) >> shift);
-  const int ty2 = d_wrap32((qy2 + delta) >> shift), ty3 = d_wrap32((qy3 + delta) >> shift);
-  int y = d_wrap32(ymin);
-  int e_idx0 = imin, e_idx1 = imin, e_ye0 = y, e_ye1 = y;
-  int edges = npts, np = 0;
-  int y_end = (int)ymax + 1;
-  for (int guard = 0; guard < 8; guard++) {
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-      const int ye = i ? e_ye1 : e_ye0;
-      if (y >= ye) {
-        int idx0 = i ? e_idx1 : e_idx0;
-        const int di = i ? npts - 1 : 1;
-        int idx = idx0 + di;
-        if (idx >= npts) idx -= npts;
-        for (; edges-- > 0;) {  // (a straight-line 4-candidate version of this scan was tried: 25 % more instructions)
-          int ty = idx == 0 ? ty0 : idx == 1 ? ty1 : idx == 2 ? ty2 : ty3;
-          if (ty > y) {
-            py[np] = y;
-            pv[np] = idx0 | (idx << 2);
-            wmask |= i << np;
-            np++;
-            if (i) {
-              e_ye1 = ty;
-              e_idx1 = idx;
-            } else {
-              e_ye0 = ty;
-              e_idx0 = idx;
-            }
-            break;
-          }
-          idx0 = idx;
-          idx += di;
-          if (idx >= npts) idx -= npts;
-        }
-      }
-    }
-    if (edges < 0) {
-      y_end = y;
-      break;
-    }
-    int ynext = e_ye0 < e_ye1 ? e_ye0 : e_ye1;
-    if (ynext > (int)ymax) break;
-    y = ynext;
-  }
-  y_first = d_wrap32(ymin) > 0 ? d_wrap32(ymin) : 0;
-  y_last = y_end - 1 < (int)ymax ? y_end - 1 : (int)ymax;
-  return np;
+#ifdef TC_FILL_LITERAL
+  return tc_fill_events_literal(W, H, qx0, qx1, qx2, qx3, qy0, qy1, qy2, qy3, py, pv, wmask, y_first, y_last);
+#else
+  return tc_fill_events(W, H, qx0, qx1, qx2, qx3, qy0, qy1, qy2, qy3, py, pv, wmask, y_first, y_last);
+#endif
 }
 
 // slope of one recorded piece (drawing.cpp: edge[i].dx = ((xe - xs)*2 + (ty - y)) / (2*(ty - y)), edge[i].x = xs)
