@@ -25,6 +25,7 @@
 #include "tc_rng.h"
 #include "tc_ctrl.h"
 #include "tc_clip.h"
+#include "tc_cull.h"
 
 // Timing build only (make timing -> libtinycarlo_hip_timing.so, used by tools/phase_clock.py): every wavefront stores
 // the shader clock at its phase boundaries.  The shipped library is compiled without TC_TIMING and contains none of it.
@@ -300,6 +301,11 @@ struct KArgs {
   // workgroup's block, behind both stages' buffers) instead of going through global memory; 0 in every other launch
   int seg_lds_off, seg_lds_cap;
   int clip_merge;  // TC_CLIP_MERGE: 1 = a pair of clip passes runs as one pass where tc_clip.h allows it, 0 = always four
+  // Whole-frame cull (tc_cull.h).  frame_cull: TC_FRAME_CULL, and the map has a table, and the shared camera a cover (never
+  // with per-env cameras: the cover is the shared camera's); cull_tab: header + cells (library owned, camera independent)
+  int frame_cull;
+  const unsigned char* cull_tab;
+  TcCullCover cull;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -1517,6 +1523,62 @@ __device__ __forceinline__ void cam_pose12(const KArgs& a, int env, const FrameP
   d_matmul<3, 4, 4>(Ec, car3d, pose);  // camera.py:62
 }
 
+// The whole-frame cull of tc_cull.h at the head of the camera stage: true = this pose's draw list is empty.  Wave-uniform
+// (the pose is in scalar registers); the header fields, the cells and the special nodes come through scalar loads, and
+// every cell word is fetched before the first is looked at.
+#ifdef TC_ABLATE
+__device__ unsigned long long tc_cull_counts[2];  // frames that ran the test, frames it culled (lane 0 counts)
+#endif
+__device__ __forceinline__ bool cam_cull(const KArgs& a, const double* pose) {
+  typedef const __attribute__((address_space(4))) double* DConst;
+  typedef const __attribute__((address_space(4))) int* IConst;
+  typedef const __attribute__((address_space(4))) unsigned int* UConst;
+  static_assert(offsetof(TcCullHead, margin) == 32 && offsetof(TcCullHead, nx) == 48 && offsetof(TcCullHead, n_special) == 56 &&
+                    offsetof(TcCullHead, special) == 64 && TC_CULL_HEAD_BYTES % 4 == 0,
+                "the fields are read by offset below");
+  const DConst hd = (DConst)(unsigned long long)a.cull_tab;
+  const IConst hi = (IConst)(unsigned long long)a.cull_tab;
+  TcCullHead h;
+  h.x0 = hd[0];
+  h.y0 = hd[1];
+  h.inv = hd[2];
+  h.cell = hd[3];
+  h.margin = hd[4];
+  h.nx = hi[12];
+  h.ny = hi[13];
+  h.n_special = hi[14];
+  int cell[TC_CULL_NC];
+  unsigned int word[TC_CULL_NC];
+#pragma unroll
+  for (int i = 0; i < TC_CULL_NC; i++) {
+    double wx, wy;
+    tc_cull_world(pose, a.cull.c[i], &wx, &wy);
+    cell[i] = uni_i(tc_cull_cell(h, wx, wy, a.cull.r[i]));
+    // (a cell index is below nx * ny, and the buffer is padded to whole words: see tc_cull_plan)
+    word[i] = ((UConst)(unsigned long long)a.cull_tab)[(TC_CULL_HEAD_BYTES + (cell[i] > 0 ? cell[i] : 0)) >> 2];
+  }
+  bool empty = true;
+#pragma unroll
+  for (int i = 0; i < TC_CULL_NC; i++) {
+    const int q = (int)((word[i] >> (8 * (cell[i] & 3))) & 255u);
+    empty = empty && (cell[i] == TC_CULL_CELL_CLEAR || (cell[i] >= 0 && tc_cull_free(h, q, a.cull.r[i])));
+  }
+  if (empty) {  // guard G, only for a frame that would be culled
+    const double mr = a.cull.max_range;
+    for (int i = 0; i < h.n_special; i++) {
+      const double z = __builtin_fma(pose[9], hd[9 + 2 * i], __builtin_fma(pose[8], hd[8 + 2 * i], pose[11]));
+      empty = empty && tc_fabs(z + mr) >= TC_CULL_GUARD;
+    }
+  }
+#ifdef TC_ABLATE
+  if (threadIdx.x == 0) {
+    atomicAdd(&tc_cull_counts[0], 1ull);
+    if (empty) atomicAdd(&tc_cull_counts[1], 1ull);
+  }
+#endif
+  return empty;
+}
+
 template <int K>
 __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, int env, const double* pose_in, MapCache<K>& mc,
                                          const bool mc_loaded, const int tid, const int seg_row, int& nseg_out,
@@ -1525,6 +1587,19 @@ __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, in
   const DevMap& m = a.m;
   const int nwin_n = (m.total_nodes + TC_NT * K - 1) / (TC_NT * K), nwin_e = (m.total_edges + TC_NT * K - 1) / (TC_NT * K);
   const bool single = a.n_grp == 1 && !a.cam_nodes && a.grp_layer[0] == 0 && a.grp_layer[1] == m.C && nwin_n <= 1 && nwin_e <= 1;
+  // the 12 entries are the same in every lane: kept in scalar registers through the node loop (24 VGPRs less)
+  double pose[12];
+#pragma unroll
+  for (int i = 0; i < 12; i++) pose[i] = uni_d(pose_in[i]);
+  // Whole-frame cull: a pose whose visible ground footprint keeps clear of every lane-line segment has an empty draw
+  // list (tc_cull.h) -- the stage ends here with what it delivers for an empty list: length 0, no
+  // layer, the length stored where it is stored otherwise, nothing written to the overflow list.
+  if (a.frame_cull && cam_cull(a, pose)) {
+    nseg_out = 0;
+    used_out = 0;
+    if (store_n && tid == 0) a.seg_n[(size_t)seg_row * a.N + env] = 0;
+    return;
+  }
   if (single && !mc_loaded) {
     cache_nodes(mc, m, 0, m.total_nodes, tid);
     cache_edges(mc, m, 0, m.total_edges, 0, tid);
@@ -1536,7 +1611,7 @@ __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, in
   int* list = (int*)(smem + a.lds.off_list);
   int* cnt = (int*)(smem + a.lds.off_cnt);
   const DevCam& cam = a.cam;
-  double pose[12], Kc[9];
+  double Kc[9];
   if (a.cam_K) {  // (a branch, not a select of pointers: the shared camera's K then comes in scalar loads)
 #pragma unroll
     for (int i = 0; i < 9; i++) Kc[i] = a.cam_K[(size_t)env * 9 + i];
@@ -1545,9 +1620,6 @@ __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, in
 #pragma unroll
     for (int i = 0; i < 9; i++) Kc[i] = kk[i];  // (explicitly the kernarg segment: cannot be merged with the other branch)
   }
-  // the 12 entries are the same in every lane: kept in scalar registers through the node loop (24 VGPRs less)
-#pragma unroll
-  for (int i = 0; i < 12; i++) pose[i] = uni_d(pose_in[i]);
   // The lane-line layers of a camera group are processed together: node ids are made global (edges_g) and then
   // relative to the group, so each of the passes below is ONE loop over the group's nodes / edges instead of one
   // per layer (the layers never share nodes, so camera.py's per-layer loop and this are the same computation).
@@ -3539,7 +3611,7 @@ extern "C" int tc_abi_version(void) { return TC_ABI_VERSION; }
 // Every switch the library reads from the environment, parsed once per tc_env_create / tc_map_create by read_tuning()
 // -- the only place that looks at the environment.  INTEGRATION.md calls the shipped ones result-neutral.
 struct Tuning {
-  int fuse, env_grouped, envg_map_lds, first_per_env, stream, groups, seg_lds, frame_order, cand_grid, clip_merge;  // on / off
+  int fuse, env_grouped, envg_map_lds, first_per_env, stream, groups, seg_lds, frame_order, cand_grid, clip_merge, frame_cull;  // on / off
   // tc_step_multi with observations, split form (default; 0 selects the fused K-step kernel): ONE
   // simulate launch loops over the K steps and leaves K draw lists per env, ONE raster launch of K x N workgroups
   // draws them.  Why: a frame costs between ~10 k clocks (nothing in view) and ~80 k (60 segments) to rasterise and an
@@ -3587,6 +3659,7 @@ static Tuning read_tuning() {
       {"TC_STEP_ORDER", "8", "single steps re-deal the envs to workgroups every n-th tc_step; <= 0: never"},
       {"TC_CAND_GRID", "1", "0: nearest-edge queries scan every edge instead of the candidate grid"},
       {"TC_CLIP_MERGE", "1", "0: the camera stage always runs its four clip passes one by one"},
+      {"TC_FRAME_CULL", "1", "0: the camera stage never culls a whole frame from its pose (tc_cull.h)"},
 #ifdef TC_ABLATE
       {"TC_PRINT_LDS", "", "set: tc_env_create prints its LDS layout"},
 #endif
@@ -3620,6 +3693,7 @@ static Tuning read_tuning() {
   t.frame_order = on("TC_FRAME_ORDER");
   t.cand_grid = on("TC_CAND_GRID");
   t.clip_merge = on("TC_CLIP_MERGE");
+  t.frame_cull = on("TC_FRAME_CULL");
   t.pipe = positive("TC_CHUNK") > 0;
   t.chunk = t.pipe ? positive("TC_CHUNK") : 16;
   t.frame_streams = atoi(sw("TC_FRAME_STREAMS")) == 1 ? 1 : 2;
@@ -3699,6 +3773,8 @@ struct tc_env {
   DevPtr<int> spawn_tab;
   DevPtr<double2> cam_nodes;
   DevPtr<int2> cam_edges;
+  DevPtr<unsigned char> cull_tab;  // k.cull_tab: the whole-frame cull's table (tc_cull.h), or NULL
+  TcCullHead cull_head{};          // its header (tc_cull_cover reads it when the camera changes)
   CarRows cr{};          // per-env cars (tc_env_set_car_per_env / tc_env_set_car_randomization); rows NULL = shared car
   DevPtr<CarDrawTab> car_tab;  // device copy of the randomisation ranges (updated in place), or NULL
   EpArgs ep{};           // episodes (tc_env_set_episodes / tc_env_set_episode_rollout); length NULL = feature off
@@ -4247,6 +4323,27 @@ static void alloc_orders(tc_env* e) {
   }
 }
 
+// The whole-frame cull's table (tc_cull.h): built from the host copy of the lane-line graph, uploaded once; the cover of
+// the camera follows in cover_cull().  Cells of 2 cm, 1 m of margin (a cover circle of the bundled cameras has 0.3-0.45 m).
+static void cover_cull(tc_env* e) {
+  tc_cull_cover(e->k.cam.E, e->k.cam.K, e->k.cam.W, e->k.cam.H, e->k.cam.max_range, e->cull_head, &e->k.cull);
+  e->k.frame_cull = e->tune.frame_cull && e->k.cull_tab && e->k.cull.on && !e->k.cam_E;
+}
+static int plan_cull(tc_env* e) {
+  const tc_map* map = e->map;
+  std::vector<unsigned char> tab;
+  tc_cull_plan(map->h_nodes.empty() ? nullptr : &map->h_nodes[0].x, (int)map->h_nodes.size(),
+               map->h_edges_g.empty() ? nullptr : &map->h_edges_g[0].x, (int)map->h_edges_g.size(), 0.02, 1.0, tab);
+  memcpy(&e->cull_head, tab.data(), sizeof(e->cull_head));
+  if (e->cull_head.nx > 0) {
+    HIP_TRY(e->cull_tab.alloc(tab.size()));
+    HIP_TRY(hipMemcpy(e->cull_tab, tab.data(), tab.size(), hipMemcpyHostToDevice));
+    e->k.cull_tab = e->cull_tab;
+  }
+  cover_cull(e);
+  return TC_OK;
+}
+
 extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const tc_camera_params* cam,
                              int32_t num_envs, tc_env** out) {
   if (!map || !car || !cam || !out || num_envs < 1) return TC_E_INVALID;
@@ -4263,6 +4360,8 @@ extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const 
   e->k.car.has_max_acceleration = car->has_max_acceleration;
   fill_car_constants(e->k.car, car);
   rc = fill_camera(e.get(), cam);
+  if (rc != TC_OK) return rc;
+  rc = plan_cull(e.get());
   if (rc != TC_OK) return rc;
   const DevCam& dc = e->k.cam;
   const DevMap& m = map->d;
@@ -4513,8 +4612,20 @@ extern "C" int tc_env_set_camera_per_env(tc_env* e, const double* E, const doubl
   if (!e || ((E == nullptr) != (K == nullptr))) return TC_E_INVALID;
   e->k.cam_E = E;
   e->k.cam_K = K;
+  cover_cull(e);  // (per-env cameras: the cull is off, its cover is the shared camera's)
   return TC_OK;
 }
+
+#ifdef TC_ABLATE
+// ablation build only: frames that ran the whole-frame cull's test and frames it culled since the last reset
+extern "C" int tc_debug_cull_counts(unsigned long long* out, int reset) {
+  HIP_TRY(hipDeviceSynchronize());
+  if (out) HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(tc_cull_counts), 2 * sizeof(unsigned long long)));
+  const unsigned long long zero[2] = {0, 0};
+  if (reset) HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(tc_cull_counts), zero, sizeof(zero)));
+  return TC_OK;
+}
+#endif
 
 static int noise_lds_bytes(const tc_env* e) {  // bit-planes of a band + blob rows + one span-table row per blob
   const int nb = e->k.m.C * e->noise_blobs;
@@ -4711,6 +4822,7 @@ extern "C" int tc_env_set_camera(tc_env* e, const tc_camera_params* cam) {
   int rc = fill_camera(e, cam);
   e->k.cam.band_rows = band_rows;
   e->k.cam.n_bands = n_bands;
+  if (rc == TC_OK) cover_cull(e);  // (the cover travels by value with the launch arguments: no table to replace, no wait)
   return rc;
 }
 
