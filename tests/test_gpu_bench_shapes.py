@@ -82,21 +82,27 @@ def check_rows_against_oracle(env, o, cc, man, roll, flags, label, info_rows=Tru
     return n_reset
 
 
-def run_case(map_name, res, fmt, n, K, seed=0, actions=bench_actions, spawn_queue_len=16, calls=1, threads=16):
+def run_case(map_name, res, fmt, n, K, seed=0, actions=bench_actions, spawn_queue_len=16, calls=1, threads=16, label=None,
+             before=None):
+    """map_name: as make_env takes it (a config dict goes with res = fmt = None and a label); before(env, o): called once
+    env and oracle are reset, ahead of the K-step calls (creation checks, single steps on both)"""
     env = make_env(map_name, res, fmt, n, autoreset=True, spawn_queue_len=spawn_queue_len)
+    label = label if label is not None else map_name
     env.reset(seed=seed)
     o = make_oracle(env, threads=threads)
     o.reset(env._keep[0].cpu().numpy())
     o.spawn_queue = env._aux["spawn_queue"].cpu().numpy()
+    if before is not None:
+        before(env, o)
     roll = env.alloc_rollout(K, keys="all")
     n_reset = 0
     for c in range(calls):
         cc, man = actions(n, K, seed=seed + 17 * c + 1)
         env.step_multi(cc, man, rollout=roll)
         torch.cuda.synchronize()
-        n_reset += check_rows_against_oracle(env, o, cc, man, roll, orc.F_AUTORESET, f"{map_name} {res} {fmt} call {c}")
+        n_reset += check_rows_against_oracle(env, o, cc, man, roll, orc.F_AUTORESET, f"{label} {res} {fmt} call {c}")
     # the bound buffers hold step K-1 of the last call (the bound obs is untouched by a rollout call)
-    assert_same(env, o, env.n_classes, check_obs=False, label=f"{map_name} bound buffers")
+    assert_same(env, o, env.n_classes, check_obs=False, label=f"{label} bound buffers")
     assert np.array_equal(env._aux["spawn_cursor"].cpu().numpy(), o.spawn_cursor)
     assert np.array_equal(env._aux["needs_reset"].cpu().numpy().astype(bool), o.needs_reset.astype(bool))
     info = env.launch_info(K)

@@ -23,7 +23,18 @@ STATE_F = ("x", "y", "theta", "velocity", "steering", "radius", "front_x", "fron
 
 
 def make_env(map_name, res_key, fmt, n, **kw):
+    """map_name: a bundled / test map, or a config dict that is taken as it is (res_key and fmt then None: the config's own
+    resolution and format; its map's json_path absolute)"""
     from tinycarlo_amd.vec_env import TinyCarloVecEnv
+    if isinstance(map_name, dict):
+        cfg = copy.deepcopy(map_name)
+        if res_key is not None:
+            from common import RES
+            cfg["camera"]["resolution"] = list(RES[res_key])
+        cfg["camera"].update(kw.pop("camera", {}))
+        if fmt is not None:
+            cfg["sim"]["observation_space_format"] = fmt
+        return TinyCarloVecEnv(cfg, num_envs=n, device="cuda:0", **kw)
     cfg, cfg_path = load_cfg(map_name)
     cfg = copy.deepcopy(cfg)
     from common import RES

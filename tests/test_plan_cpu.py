@@ -1,61 +1,47 @@
 """The host planners of tc_env_create (tinycarlo_amd/csrc/tc_plan.h) on the CPU: the header is built alone by the host
-compiler and the planners run on every bundled map and the stress map.
+compiler (the shim of tests/big_maps.py) and the planners run on every bundled map, the stress map and the generated
+maps of tests/big_maps.py (CASES: 320 .. 2 970 lane-line nodes, up to 16 layers, rings with gaps, dashes, interleaved and
+duplicate edges, self-loops, isolated nodes; "<case>/<k>" below is map k of a case).
 
 A plan that reports success is held to the properties the camera stage relies on ("Host structure"); whether
 it must report failure is worked out here, independently, from the component sizes of the map.
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from common import ROOT, setup
+import big_maps
+from common import setup
 
 MAX_GROUPS = 8   # TC_MAX_GROUPS
 NT = 64          # TC_NT
 MAPS = ["simple_layout", "knuffingen", "formula_student_track", "stress_graph"]
-
-SHIM = r"""
-#include "tc_plan.h"
-#include <algorithm>
-extern "C" int components(const int* edge_off, int C, const int* edges, int n_nodes, int T, int max_groups, int* new_id,
-                          int* n0, int* e0, int* l0, int* l1, int* caps) {
-  const ComponentGroups p = plan_component_groups(edge_off, C, edges, n_nodes, T, max_groups);
-  if (!p.ok) return 0;
-  std::copy(p.new_id.begin(), p.new_id.end(), new_id);
-  std::copy(p.n0.begin(), p.n0.end(), n0);
-  std::copy(p.e0.begin(), p.e0.end(), e0);
-  std::copy(p.l0.begin(), p.l0.end(), l0);
-  std::copy(p.l1.begin(), p.l1.end(), l1);
-  caps[0] = p.cap_n;
-  caps[1] = p.cap_e;
-  return (int)p.l0.size();
-}
-extern "C" int layers(const int* node_off, const int* edge_off, int C, int max_cap, int max_groups, int* layer, int* caps) {
-  const LayerGroups p = plan_layer_groups(node_off, edge_off, C, max_cap, max_groups);
-  if (!p.ok) return 0;
-  std::copy(p.layer.begin(), p.layer.end(), layer);
-  caps[0] = p.cap_n;
-  caps[1] = p.cap_e;
-  return (int)p.layer.size() - 1;
-}
-"""
-
+BIG = [f"{name}/{k}" for name in big_maps.CASES for k in range(big_maps.N_SEEDS)]  # generated: "<case>/<map of the case>"
 
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory):
-    d = tmp_path_factory.mktemp("tc_plan")
-    src, lib = d / "shim.cpp", d / "libtc_plan.so"
-    src.write_text(SHIM)
-    subprocess.check_call(["c++", "-std=c++17", "-O1", "-Wall", "-Werror", "-shared", "-fPIC",
-                           "-I", os.path.join(ROOT, "tinycarlo_amd", "csrc"), "-o", str(lib), str(src)])
-    return C.CDLL(str(lib))
+    return big_maps.build_plan_shim(tmp_path_factory.mktemp("tc_plan"))
 
 
 def _ptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def component_labels(n_nodes, edges):
+    """component label of every node (the smallest node id its component holds), -1 = a node without an edge"""
+    label = np.arange(n_nodes)
+    while True:  # label propagation: every node takes the smallest id its edges reach
+        lo = np.minimum(label[edges[:, 0]], label[edges[:, 1]])
+        new = label.copy()
+        np.minimum.at(new, edges[:, 0], lo)
+        np.minimum.at(new, edges[:, 1], lo)
+        if np.array_equal(new, label):
+            break
+        label = new
+    has_edge = np.zeros(n_nodes, dtype=bool)
+    has_edge[edges.ravel()] = True
+    return np.where(has_edge, label, -1)
 
 
 @pytest.fixture(scope="module")
@@ -64,21 +50,12 @@ def graphs():
     out = {}
     for name in MAPS:
         f = setup(name)[1].flat()
-        node_off = np.concatenate([[0], np.cumsum(f["node_count"])]).astype(np.int32)
-        edge_off = np.concatenate([[0], np.cumsum(f["edge_count"])]).astype(np.int32)
-        edges = np.ascontiguousarray(f["edges"] + np.repeat(node_off[:-1], f["edge_count"])[:, None], dtype=np.int32)
-        label = np.arange(node_off[-1])
-        while True:  # label propagation: every node takes the smallest id its edges reach
-            lo = np.minimum(label[edges[:, 0]], label[edges[:, 1]])
-            new = label.copy()
-            np.minimum.at(new, edges[:, 0], lo)
-            np.minimum.at(new, edges[:, 1], lo)
-            if np.array_equal(new, label):
-                break
-            label = new
-        has_edge = np.zeros(node_off[-1], dtype=bool)
-        has_edge[edges.ravel()] = True
-        out[name] = (node_off, edge_off, edges, np.where(has_edge, label, -1))
+        node_off, edge_off, edges = big_maps.graph_arrays(f["node_count"], f["edge_count"], f["edges"])
+        out[name] = (node_off, edge_off, edges, component_labels(node_off[-1], edges))
+    for name in BIG:
+        case, k = name.split("/")
+        node_off, edge_off, edges = big_maps.graph_of_json(big_maps.case_map(case, int(k))[0])
+        out[name] = (node_off, edge_off, edges, component_labels(node_off[-1], edges))
     return out
 
 
@@ -104,8 +81,8 @@ def _expect_failure(edges, comp, T):
     return None
 
 
-@pytest.mark.parametrize("T", [320, 200, 64])
-@pytest.mark.parametrize("name", MAPS)
+@pytest.mark.parametrize("T", [320, 200, 64, 576])
+@pytest.mark.parametrize("name", MAPS + BIG)
 def test_component_groups(plan, graphs, name, T):
     node_off, edge_off, edges, comp = graphs[name]
     n, te, nl = int(node_off[-1]), int(edge_off[-1]), len(edge_off) - 1
@@ -164,6 +141,33 @@ def test_layer_groups_on_knuffingen(plan, graphs):
     layer = layer[:ng + 1]
     assert layer[0] == 0 and layer[-1] == nl and (np.diff(layer) > 0).all(), "whole layers, in order"
     largest = max(np.diff(node_off).max(), np.diff(edge_off).max())
+    gn, ge = np.diff(node_off[layer]), np.diff(edge_off[layer])
+    assert gn.max() <= largest and ge.max() <= largest
+    assert caps[0] == gn.max() and caps[1] == ge.max()
+
+
+@pytest.mark.parametrize("name", BIG)
+def test_layer_groups_on_generated_maps(plan, graphs, name):
+    """the same properties on the generated maps; whether the planner must refuse is worked out here from the layer sizes:
+    a layer beyond the K = 9 cache, or a greedy packing into groups no larger than the largest layer that needs more than
+    MAX_GROUPS groups or fewer than two"""
+    node_off, edge_off, _, _ = graphs[name]
+    nl = len(node_off) - 1
+    layer, caps = np.zeros(MAX_GROUPS + 1, dtype=np.int32), np.zeros(2, dtype=np.int32)
+    ng = plan.layers(_ptr(node_off), _ptr(edge_off), nl, 9 * NT, MAX_GROUPS, _ptr(layer), _ptr(caps))
+    sizes = list(zip(np.diff(node_off).tolist(), np.diff(edge_off).tolist()))
+    largest = max(max(s) for s in sizes)
+    count, gn, ge = 1, 0, 0
+    for n, e in sizes:
+        if gn + n > largest or ge + e > largest:
+            count, gn, ge = count + 1, 0, 0
+        gn, ge = gn + n, ge + e
+    if largest > 9 * NT or count > MAX_GROUPS or count < 2:
+        assert ng == 0, (name, "must be refused", largest, count)
+        return
+    assert ng == count
+    layer = layer[:ng + 1]
+    assert layer[0] == 0 and layer[-1] == nl and (np.diff(layer) > 0).all(), "whole layers, in order"
     gn, ge = np.diff(node_off[layer]), np.diff(edge_off[layer])
     assert gn.max() <= largest and ge.max() <= largest
     assert caps[0] == gn.max() and caps[1] == ge.max()

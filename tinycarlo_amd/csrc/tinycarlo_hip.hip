@@ -1651,7 +1651,9 @@ __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, in
                         my_layers, env, tid);
       continue;
     }
-    // a group larger than the register window (no bundled map): window by window, lists and counters in LDS
+    // a group larger than the register window: window by window, lists and counters in LDS.  No bundled map gets here;
+    // tests/test_gpu_big_map_fuzz.py does with k13_by_edges (two edge windows over one node window), k13_9_layers_2970
+    // (four node windows) and TC_GROUPS=0 on layers_cap_576; tests/test_gpu_parity.py with knuffingen three times over
     if (tid < 5) cnt[tid] = 0;
     if (tid == 5) cnt[5] = nseg;
     for (int w = 0; w < nwn; w++) {  // camera.py:124-131
