@@ -182,6 +182,9 @@ __device__ long long* tc_tstamp = nullptr;  // [N][32]
 #define DBG_SKIP_QUAD 0x80000u
 #define DBG_SKIP_CLIP 0x100000u
 #define DBG_SKIP_DRAWLIST 0x200000u
+// not an ablation switch: set by make_rargs in RArgs.flags when ThickLine needs only its two long outline edges
+// (tc_short_edges_skip of tc_line.h holds for the camera and TC_SHORT_EDGES is 0); never part of a caller's flags
+#define R_F_LONG_EDGES 0x40000000u
 // the kernels test them only in the ablation build (make dev-ablate): in the shipped library every test folds to false,
 // so the switches cost no scalar registers there (they were ~25 live conditions at the head of the raster stage)
 #ifdef TC_ABLATE
@@ -2092,10 +2095,19 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
         lds_sync();
         TSTAMP(10);
         MARK("outline setup");
-        for (int t = tid; t < RB * 4; t += TC_NT) {  // outline edges: clip + DDA parameters
+        // Outline edges: clip + DDA parameters.  Four per segment (FillConvexPoly's), or -- R_F_LONG_EDGES: thickness 2, see
+        // tc_line.h -- only the two long ones v3->v0 and v1->v2, whose items then sit two per segment at the front of the
+        // tables: a batch of up to 32 segments is ONE pass of this loop instead of two.  Entries past the items keep a chunk
+        // count of 0 either way.  The fill pieces ride along: one per edge lane in the four-edge form, pieces i and i + 2
+        // on the segment's lane i = 0, 1 in the two-edge form (the second evaluation is skipped by the whole wavefront when
+        // no segment has more than two pieces).
+        // (everything the two forms differ in hangs on one scalar: items per segment = 1 << sh)
+        const int sh = (a.flags & R_F_LONG_EDGES) ? 1 : 2;
+        for (int t = tid; t < RB * 4; t += TC_NT) {
           int nchunk = 0;
-          if (t < nb * 4 && ((fm[t >> 2] >> 16) & 1)) {
-            const int j = t >> 2, e = t & 3;
+          const int j = t >> sh;
+          if (t < (nb << sh) && ((fm[j] >> 16) & 1)) {
+            const int s0 = t & ((1 << sh) - 1), e = s0 << (2 - sh);  // item of the segment; its edge: 0 2, or 0 1 2 3
             const SegV sg = seg_get(base + j);
             const long long p0x = (long long)sg[1] * TC_XY_ONE, p0y = (long long)sg[2] * TC_XY_ONE;
             const long long p1x = (long long)sg[3] * TC_XY_ONE, p1y = (long long)sg[4] * TC_XY_ONE;
@@ -2108,11 +2120,20 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
             const bool a_minus = e == 2 || e == 3, b_minus = e == 1 || e == 2;
             long long ax = (a_is_p1 ? p1x : p0x) + (a_minus ? -dpx : dpx), ay = (a_is_p1 ? p1y : p0y) + (a_minus ? -dpy : dpy);
             long long bx = (b_is_p1 ? p1x : p0x) + (b_minus ? -dpx : dpx), by = (b_is_p1 ? p1y : p0y) + (b_minus ? -dpy : dpy);
-            if (e < (fm[j] & 0xff) && !DBG_ON(a.flags, DBG_SKIP_SLOPE)) {  // fill piece e of this segment: x at its start row and slope
-              long long xs, dxs;
-              r_fill_slope(qx0, qx1, qx2, qx3, qy0, qy1, qy2, qy3, fpy[t], fpv[t], xs, dxs);
-              fpx[t] = xs;
-              fpd[t] = dxs;
+            const int np = fm[j] & 0xff;
+            // fill pieces of this lane (x at the start row and slope): piece s0, and s0 + 2 in the two-edge form -- one
+            // instance of the code, a loop the wavefront leaves together
+#pragma nounroll
+            for (int h = 0; h < (8 >> sh) && !DBG_ON(a.flags, DBG_SKIP_SLOPE); h += 2) {
+              const bool want = s0 + h < np;
+              if (h != 0 && __ballot(want) == 0) break;
+              if (want) {
+                const int s = 4 * j + s0 + h;
+                long long xs, dxs;
+                r_fill_slope(qx0, qx1, qx2, qx3, qy0, qy1, qy2, qy3, fpy[s], fpv[s], xs, dxs);
+                fpx[s] = xs;
+                fpd[s] = dxs;
+              }
             }
             LineP L;
             L.ecount = -1;
@@ -3613,7 +3634,7 @@ extern "C" int tc_abi_version(void) { return TC_ABI_VERSION; }
 // Every switch the library reads from the environment, parsed once per tc_env_create / tc_map_create by read_tuning()
 // -- the only place that looks at the environment.  INTEGRATION.md calls the shipped ones result-neutral.
 struct Tuning {
-  int fuse, env_grouped, envg_map_lds, first_per_env, stream, groups, seg_lds, frame_order, cand_grid, clip_merge, frame_cull;  // on / off
+  int fuse, env_grouped, envg_map_lds, first_per_env, stream, groups, seg_lds, frame_order, cand_grid, clip_merge, frame_cull, short_edges;  // on / off
   // tc_step_multi with observations, split form (default; 0 selects the fused K-step kernel): ONE
   // simulate launch loops over the K steps and leaves K draw lists per env, ONE raster launch of K x N workgroups
   // draws them.  Why: a frame costs between ~10 k clocks (nothing in view) and ~80 k (60 segments) to rasterise and an
@@ -3662,6 +3683,7 @@ static Tuning read_tuning() {
       {"TC_CAND_GRID", "1", "0: nearest-edge queries scan every edge instead of the candidate grid"},
       {"TC_CLIP_MERGE", "1", "0: the camera stage always runs its four clip passes one by one"},
       {"TC_FRAME_CULL", "1", "0: the camera stage never culls a whole frame from its pose (tc_cull.h)"},
+      {"TC_SHORT_EDGES", "0", "1: thickness 2 draws the quad's two short outline edges too (tc_line.h)"},
 #ifdef TC_ABLATE
       {"TC_PRINT_LDS", "", "set: tc_env_create prints its LDS layout"},
 #endif
@@ -3696,6 +3718,7 @@ static Tuning read_tuning() {
   t.cand_grid = on("TC_CAND_GRID");
   t.clip_merge = on("TC_CLIP_MERGE");
   t.frame_cull = on("TC_FRAME_CULL");
+  t.short_edges = on("TC_SHORT_EDGES");
   t.pipe = positive("TC_CHUNK") > 0;
   t.chunk = t.pipe ? positive("TC_CHUNK") : 16;
   t.frame_streams = atoi(sw("TC_FRAME_STREAMS")) == 1 ? 1 : 2;
@@ -4866,7 +4889,8 @@ static RArgs make_rargs(tc_env* e, const int* seg_g, const int* seg_n, int seg_c
   r.mask = mask;
   r.off_tab = e->r_off_tab;
   r.off_bits = e->r_off_bits;
-  r.flags = flags;
+  r.flags = flags & ~R_F_LONG_EDGES;
+  if (!e->tune.short_edges && tc_short_edges_skip(c.thickness, c.W, c.H)) r.flags |= R_F_LONG_EDGES;
   r.seg_row0 = 0;
   r.noise_row0 = 0;
   r.obs_row_stride = 0;
