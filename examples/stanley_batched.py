@@ -4,7 +4,7 @@
 controller reads cte / heading_error from the env's device tensors and writes the action tensor, the reference's
 wrappers (CTE sparse reward, CTE and crash termination) run inside the step kernel, finished envs re-spawn on the device.
 
-    python examples/stanley_batched.py [--envs 4096] [--steps 600] [--maneuver 3] [--randomize] [--max-episode-steps N] [--fused K]
+    python examples/stanley_batched.py [--envs 4096] [--steps 600] [--maneuver 3] [--randomize] [--max-episode-steps N] [--fused K [--packed]]
 
 --randomize: every episode of every env drives its own car, drawn on the device at the re-spawn (wheelbase, track width,
 speed and steering limits within +-20 %), plus the steering shift of the reference's TD3 study (examples/train_td3.py:37,
@@ -18,6 +18,10 @@ envs); the episodes finished and their mean length / return are read from vec.ep
 --fused K: the same run with the controller inside the simulate kernels (vec.set_controller): `drive` calls of K steps
 each, one launch sequence per K steps instead of one per step plus the torch glue; the per-step rewards, cte and episode
 ends come back in the call's rollout rows.  The default stays the torch loop below.
+
+--packed (with --fused K): class-mask frames leave the kernels bit-packed (obs_packing="bits": uint8 [C, H, W/8], an eighth
+of the bytes), and a sample of each call's rows is expanded on the device to float16 0.0 / 1.0 -- what a consumer that
+trains on a batch of the rollout does (tinycarlo_amd.unpack_obs).
 """
 import argparse
 import math
@@ -34,9 +38,19 @@ from tinycarlo_amd.wrapper import CrashTerminationWrapper, CTESparseRewardWrappe
 
 
 def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0", seed=2, randomize=False,
-        max_episode_steps=None, fused=0):
-    vec = TinyCarloVecEnv(bundled_config("config_simple_layout.yaml"), num_envs=num_envs, device=device,
-                          autoreset=True, spawn="device")
+        max_episode_steps=None, fused=0, packed=False):
+    config = bundled_config("config_simple_layout.yaml")
+    if packed:  # packing is for class masks: the bundled config with that format
+        if not fused:
+            raise ValueError("--packed goes with --fused K (the frames of a rollout)")
+        import yaml
+        with open(config) as f:
+            cfg = yaml.safe_load(f)
+        cfg["sim"]["observation_space_format"] = "classes"
+        cfg["map"]["json_path"] = os.path.join(os.path.dirname(config), cfg["map"]["json_path"])
+        config = cfg
+    vec = TinyCarloVecEnv(config, num_envs=num_envs, device=device, autoreset=True, spawn="device",
+                          obs_packing="bits" if packed else None)
     if randomize:
         p = vec.car_params
         vec.randomize_cars({name: (0.8 * getattr(p, name), 1.2 * getattr(p, name))
@@ -71,6 +85,9 @@ def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0",
             ret += roll["reward"].sum(0)
             cte_abs += roll["cte"].abs().mean(1).sum()
             ended += (roll["terminated"] | roll["truncated"]).sum()
+            if packed:  # a batch for the network: 256 random (step, env) rows of this call, float16 0.0 / 1.0
+                batch_idx = torch.randint(0, n * num_envs, (256,), device=device)
+                batch = vec.unpack_obs(roll["obs"], torch.float16, index=batch_idx)
     else:
         for _ in range(steps):
             cte, he = vec.out["cte"], vec.out["heading_error"]      # of the previous step, already on the device
@@ -88,6 +105,8 @@ def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0",
            "mean_reward_per_step": float(ret.mean()) / steps, "obs_shape": tuple(vec.out["obs"].shape)}
     if fused:
         out["steps_per_call"] = fused
+    if packed:
+        out["batch"] = (tuple(batch.shape), str(batch.dtype))
     if randomize:
         out["car_episodes_drawn"] = int(vec.car_episode.sum())
     if max_episode_steps:
@@ -107,5 +126,7 @@ if __name__ == "__main__":
     ap.add_argument("--randomize", action="store_true", help="per-episode car constants and steering shift")
     ap.add_argument("--max-episode-steps", type=int, default=None, help="time limit per episode (kept by the step kernel)")
     ap.add_argument("--fused", type=int, default=0, metavar="K", help="built-in controller: drive() calls of K steps")
+    ap.add_argument("--packed", action="store_true", help="with --fused: bit-packed class-mask frames, unpacked in batches")
     a = ap.parse_args()
-    print(run(a.envs, a.steps, a.maneuver, randomize=a.randomize, max_episode_steps=a.max_episode_steps, fused=a.fused))
+    print(run(a.envs, a.steps, a.maneuver, randomize=a.randomize, max_episode_steps=a.max_episode_steps, fused=a.fused,
+              packed=a.packed))

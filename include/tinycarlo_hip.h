@@ -52,6 +52,8 @@ extern "C" {
 #define TC_HAS_EPISODES 1
 /* Likewise additive within ABI 6: tc_env_set_controller, tc_controller, TC_CTRL_STANLEY. */
 #define TC_HAS_CONTROLLER 1
+/* Likewise additive within ABI 6: TC_FMT_CLASSES_BITS, tc_unpack_bits, TC_U8 / TC_F16 / TC_BF16. */
+#define TC_HAS_PACKED_OBS 1
 #define TC_MAX_LAYERS 16
 
 /* error codes */
@@ -65,10 +67,27 @@ extern "C" {
 /* observation formats (sim.observation_space_format, env.py:42,67-72) */
 #define TC_FMT_RGB 0     /* uint8 [N][H][W][3] */
 #define TC_FMT_CLASSES 1 /* uint8 [N][C][H][W], values 0/255 */
+/* Bit-packed class masks: uint8 [N][C][H][W/8].  Pixel (y, x) of class c is bit x & 7 of byte x >> 3 of row y of plane c; a
+ * set bit stands for 255 -- np.packbits(mask != 0, axis=-1, bitorder="little") of the TC_FMT_CLASSES frame, one eighth of its
+ * bytes.  All planes of an env are contiguous (a frame is C*H*W/8 bytes, see tc_env_obs_bytes).  An opt-in of the batched
+ * env, not a value of sim.observation_space_format: the reference has no such format.
+ *   - W % 32 != 0 with this format is TC_E_INVALID from tc_env_create and tc_env_set_camera.
+ *   - tc_env_set_noise works as for TC_FMT_CLASSES (the blobs are applied to the bit-planes before the store, same stream).
+ *   - the stand-alone tc_noise pass reads byte masks: on a packed env it returns TC_E_INVALID (out of scope).
+ *   - what is launched: tc_frame_kernel, tc_frame_recover_kernel and tc_raster_kernel exist for this format, the fused
+ *     tc_step_kernel / tc_drive_step_kernel do not.  tc_step / tc_reset / tc_render therefore take the two-launch form
+ *     (tc_env_kernel + tc_raster_kernel, what TC_FUSE=0 selects for the byte formats), K-step calls the streamed or chunked
+ *     frame-kernel forms, and TC_MULTI_SPLIT=0 is ignored.  tc_env_launch_info reports it.
+ *   - tc_unpack_bits expands packed frames on the device. */
+#define TC_FMT_CLASSES_BITS 2
 
-/* action dtypes for tc_step */
+/* dtypes: TC_F32 / TC_F64 are the action dtypes of tc_step; TC_U8, TC_F16, TC_BF16 and TC_F32 the output dtypes of
+ * tc_unpack_bits */
 #define TC_F32 0
 #define TC_F64 1
+#define TC_U8 2
+#define TC_F16 3
+#define TC_BF16 4
 
 /* step / reset flags */
 #define TC_F_NO_OBSERVATION 1u /* env.no_observation (env.py:60,78-81): obs left untouched, no camera work */
@@ -181,7 +200,7 @@ typedef struct {
   int32_t* status;             /* TC_S_* bits */
   double* laneline_distances;  /* [N][n_layers] */
   int32_t* nearest_edge;       /* [N][n_layers] layer-local edge index of Layer.get_nearest_edge(rear), -1 if info empty */
-  uint8_t* obs;                /* [N][C][H][W] or [N][H][W][3]; may be NULL if every call passes TC_F_NO_OBSERVATION */
+  uint8_t* obs;                /* [N][C][H][W], [N][H][W][3] or [N][C][H][W/8]; may be NULL if every call passes TC_F_NO_OBSERVATION */
   /* --- auto-reset (TC_F_AUTORESET) */
   uint8_t* needs_reset;        /* [N] */
   const int32_t* spawn_queue;  /* [N][spawn_queue_len] spawnable lanepath node ids drawn by the host RNG */
@@ -320,13 +339,13 @@ int tc_env_set_spawn_table(tc_env* env, const int32_t* nodes, int32_t n, uint64_
  * for a batch).  Every rendered step consumes one position of the blob stream; the position is a counter in device
  * memory advanced on the stream behind the launch, so a call captured into a HIP graph draws new blobs on every
  * replay.  tc_reset / tc_render frames carry no noise (the reference's reset() does not pass through the wrapper's
- * step()).  n_blobs = 0 switches the noise off.  Needs TC_FMT_CLASSES and max_radius in [2, 256]. */
+ * step()).  n_blobs = 0 switches the noise off.  Needs TC_FMT_CLASSES or TC_FMT_CLASSES_BITS and max_radius in [2, 256]. */
 int tc_env_set_noise(tc_env* env, int32_t n_blobs, int32_t max_radius, uint64_t seed);
 /* The noise pass alone, on the currently bound observation.  blobs: device int32 [N][n_layers * n_blobs][5] rows
  * (x, y, radius, mode, src) -- blob k belongs to plane k / n_blobs, mode 1 = copy from plane src, 0 = erase -- or
- * NULL to draw them on the device as tc_step does. */
+ * NULL to draw them on the device as tc_step does.  Byte class masks only: TC_E_INVALID on a TC_FMT_CLASSES_BITS env. */
 int tc_noise(tc_env* env, const int32_t* blobs, void* stream);
-/* bytes of one env's observation */
+/* bytes of one env's observation: C*H*W (classes), H*W*3 (rgb), C*H*W/8 (packed classes) */
 int64_t tc_env_obs_bytes(const tc_env* env);
 /* dynamic LDS bytes one workgroup of the step kernel uses (for occupancy reporting) */
 int64_t tc_env_lds_bytes(const tc_env* env);
@@ -458,6 +477,20 @@ int tc_render_segments(tc_env* env, const int32_t* segments, const int32_t* coun
 
 /* Re-render the observation of the current state without stepping (Camera.capture_frame, camera.py:52). */
 int tc_render(tc_env* env, uint32_t flags, void* stream);
+
+/* Expands bit-packed class masks (TC_FMT_CLASSES_BITS) on the device; needs no env handle.  A "frame" is planes*H*W/8 packed
+ * bytes -- the rows of a [K][N] rollout are simply K*N frames.  dst: [n_out][planes][H][W] of dst_dtype: TC_U8 gives 0 / 255,
+ * bit-identical to what TC_FMT_CLASSES would have written; TC_F16, TC_BF16 and TC_F32 give 0.0 / 1.0, which is the consumers'
+ * pre_obs(obs) = obs / 255 (examples/benchmark_tinycar_net.py:20: 255 / 255 is exactly 1.0 in each of them).
+ *   index = NULL: output frame j is source frame j (n_out <= n_src_frames).
+ *   else: device int64 [n_out]; output frame j is source frame index[j] -- a replay-buffer sample (examples/rl_utils.py),
+ *     repeats allowed, any order.  An index outside [0, n_src_frames) yields a frame of zeros; nothing is read out of bounds.
+ * packed, index and dst are device pointers; packed must be 4-byte and dst 16-byte aligned.  One launch on `stream`; neither
+ * allocates nor synchronises and can be captured into a HIP graph.  n_out = 0 is TC_OK without a launch.
+ * TC_E_INVALID, before any HIP call: NULL packed or dst, W % 32 != 0, a non-positive size, an unknown dtype, n_out < 0,
+ * index == NULL with n_out > n_src_frames, a misaligned pointer. */
+int tc_unpack_bits(const uint8_t* packed, int64_t n_src_frames, int32_t planes, int32_t H, int32_t W, const int64_t* index,
+                   int64_t n_out, void* dst, int32_t dst_dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,7 +27,10 @@ CAR_COLUMNS = ("wheelbase", "track_width", "max_velocity", "max_steering_angle",
                "max_deceleration", "steering_shift")
 MAX_TERMS, MAX_LAYERS = 8, 16
 FMT_RGB, FMT_CLASSES = 0, 1
+FMT_CLASSES_BITS = 2  # TC_FMT_CLASSES_BITS: bit-packed class masks, uint8 [N][C][H][W/8] (tinycarlo_amd/packing.py)
 F32, F64 = 0, 1
+U8, F16, BF16 = 2, 3, 4  # with F32: the output dtypes of tc_unpack_bits
+HAS_PACKED_OBS = 1  # TC_HAS_PACKED_OBS: additive within ABI 6
 F_NO_OBSERVATION, F_WRAPPED, F_AUTORESET, F_DEVICE_SPAWN = 1, 2, 4, 8
 S_UTURN_NO_EDGE, S_PICK_EMPTY, S_BAD_SPAWN, S_NOT_RESET, S_SPAWN_WRAPPED = 1, 2, 4, 8, 16
 S_TIME_LIMIT = 32  # tc_env_set_episodes: the episode reached its time limit in this step
@@ -39,7 +42,7 @@ EXPORTS = ["tc_abi_version", "tc_last_error", "tc_map_create", "tc_map_destroy",
            "tc_env_bind", "tc_env_set_camera", "tc_env_set_camera_per_env", "tc_env_set_car", "tc_env_set_car_per_env",
            "tc_env_set_car_randomization", "tc_env_set_episodes", "tc_env_set_episode_rollout", "tc_env_set_controller", "tc_env_set_terms", "tc_env_set_spawn_table", "tc_env_set_noise", "tc_noise", "tc_env_obs_bytes", "tc_env_lds_bytes", "tc_env_profile",
            "tc_env_profile_read", "tc_reset", "tc_step", "tc_step_multi", "tc_env_reserve_steps", "tc_env_launch_info", "tc_env_draw_list_stats", "tc_render",
-           "tc_render_segments"]
+           "tc_render_segments", "tc_unpack_bits"]
 
 _dp, _ip, _bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
 
@@ -162,6 +165,8 @@ def lib():
                                      C.POINTER(C.c_int32), C.c_char_p, C.c_int32]
     L.tc_render.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     L.tc_render_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    L.tc_unpack_bits.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                 C.c_int32, C.c_void_p]
     if L.tc_abi_version() != ABI_VERSION:
         raise NativeError(f"ABI mismatch: library {L.tc_abi_version()} vs binding {ABI_VERSION}")
     _lib = L

@@ -11,6 +11,22 @@
 //                         uint8 and stored with 16-byte-per-lane coalesced stores (zeros included: a class-mask
 //                         frame is written exactly once)
 #include <hip/hip_runtime.h>
+// TC_PART: the default library is this file compiled as six translation units side by side (Makefile), because one
+// compiler process over every kernel takes ~25 minutes: part 0 = the host code and every kernel but those of the other
+// parts, parts 1 / 3 = the tc_drive_step_kernel family (class masks / rgb), parts 4 / 5 = the tc_step_kernel family (class
+// masks / rgb), part 2 = the packed-observation kernels (TC_FMT_CLASSES_BITS frame / recover / raster variants,
+// tc_unpack_bits_kernel).  Parts 1-5 hold explicit instantiations only; part 0 declares them
+// `extern template`, so its kernel tables (step_kernel_of, ...) take the addresses without compiling the bodies.  Every
+// kernel is compiled from the same text with the same flags as in a one-unit build (TC_PART undefined: make dev, make
+// timing).  The lists of instantiations are TC_INST_* below and follow Kcodes / Thicks / Fmts / FrameFmts / DriveFeats.
+#if defined(TC_PART) && defined(TC_DEV_FAST)
+#error "the development builds are one translation unit"
+#endif
+#if defined(TC_PART) && TC_PART > 0
+#define TC_PLAIN_KERNEL static  // (kernels that are no templates live in part 0)
+#else
+#define TC_PLAIN_KERNEL
+#endif
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -1864,6 +1880,39 @@ struct RArgs {
 #define TC_BAND_VMCNT 0
 #endif
 #define TC_BAND_THROTTLE() asm volatile("s_waitcnt vmcnt(%0)" ::"n"(TC_BAND_VMCNT) : "memory")
+// Bytes of one env's observation: the one place that spells them out (raster_body's `out`, the fused kernel's step stride,
+// tc_env_obs_bytes).  TC_FMT_CLASSES_BITS needs W % 32 == 0 (fill_camera): a row is W / 8 bytes.
+__host__ __device__ __forceinline__ size_t tc_obs_bytes_of(int fmt, int C, int H, int W) {
+  return fmt == TC_FMT_CLASSES_BITS ? (size_t)C * H * (size_t)(W >> 3) : (size_t)H * W * (fmt == TC_FMT_CLASSES ? C : 3);
+}
+// the two class-mask formats: identical up to the store phase
+#define TC_FMT_IS_CLASSES(fmt) ((fmt) == TC_FMT_CLASSES || (fmt) == TC_FMT_CLASSES_BITS)
+// TC_FMT_CLASSES_BITS stores.  A packed row is the row's LDS words byte for byte (both little-endian), and rows follow each
+// other without padding on both sides, so rows y0..y1 of a plane are ONE run of nw 32-bit words: lane-consecutive 16-byte
+// stores when source and destination are both 16-byte aligned (wave-uniform; a frame is C*H*W/8 bytes and a plane H*W/8,
+// neither need be a multiple of 16, and with odd wpr nor need the LDS plane offset), 4-byte stores otherwise.  The odd
+// words behind the last whole 16 bytes go out as 4-byte stores: no byte of the run is left unwritten.
+__device__ __forceinline__ void packed_zero_words(unsigned char* dst, const int nw, const int tid) {
+  if ((((unsigned long long)dst) & 15ull) == 0) {
+    const int n4 = nw >> 2;
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    for (int q = tid; q < n4; q += TC_NT) ((uint4*)dst)[q] = z;
+    for (int i = (n4 << 2) + tid; i < nw; i += TC_NT) ((unsigned int*)dst)[i] = 0u;
+  } else {
+    for (int i = tid; i < nw; i += TC_NT) ((unsigned int*)dst)[i] = 0u;
+  }
+}
+// src_word0: index of the run's first word in the bit-plane region, whose start is 16-byte aligned
+__device__ __forceinline__ void packed_copy_words(unsigned char* dst, const unsigned int* src, const int src_word0, const int nw,
+                                                  const int tid) {
+  if ((((unsigned long long)dst) & 15ull) == 0 && (src_word0 & 3) == 0) {
+    const int n4 = nw >> 2;
+    for (int q = tid; q < n4; q += TC_NT) ((uint4*)dst)[q] = ((const uint4*)src)[q];
+    for (int i = (n4 << 2) + tid; i < nw; i += TC_NT) ((unsigned int*)dst)[i] = src[i];
+  } else {
+    for (int i = tid; i < nw; i += TC_NT) ((unsigned int*)dst)[i] = src[i];
+  }
+}
 template <bool THICK, int FMT, bool LDSONLY = false, int RB = RB_MAX>
 __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem, int env, unsigned char* obs_base,
                                             const int tid, const size_t seg_slot0, const int nseg_in,
@@ -1918,7 +1967,8 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
   }
 
   const int H = cam.H, W = cam.W, wpr = cam.wpr, C = a.C;
-  unsigned char* out = obs_base + (size_t)env * ((size_t)H * W * (FMT == TC_FMT_CLASSES ? C : 3));
+  constexpr bool CLS = TC_FMT_IS_CLASSES(FMT), BITS = FMT == TC_FMT_CLASSES_BITS;
+  unsigned char* out = obs_base + (size_t)env * tc_obs_bytes_of(FMT, C, H, W);
   int* lt = (int*)(smem + R_OFF_TAB);     // [RB*4][5] outline-edge parameters
   int* lc = lt + RB * 4 * 5;              // [RB*4] chunks per outline edge, then exclusive prefix
   int* fl = lc + RB * 4;                  // [RB] first fill row of the segment in this band
@@ -1935,11 +1985,15 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
   // is 15 % of the kernel's time for 9 % of its instructions).  A frame with no segment at all (37-57 % of the
   // benchmark's frames once cars have wandered off the road) is done here: no planes to clear, no tables, no expansion.
   unsigned int early_zero = 0;
-  if (FMT == TC_FMT_CLASSES && cam.n_bands == 1 && (W & 15) == 0 && a.noise_blobs == 0 && !DBG_ON(a.flags, DBG_SKIP_STORE)) {
+  if (CLS && cam.n_bands == 1 && (W & 15) == 0 && a.noise_blobs == 0 && !DBG_ON(a.flags, DBG_SKIP_STORE)) {
     const int per_plane = H * (W >> 4);
     const uint4 zero4 = make_uint4(0, 0, 0, 0);
     for (int c = 0; c < C; c++) {
       if ((used_layers >> c) & 1u) continue;
+      if (BITS) {  // the plane's H * wpr words
+        packed_zero_words(out + (size_t)c * H * wpr * 4, H * wpr, tid);
+        continue;
+      }
       uint4* po = (uint4*)(out + (size_t)c * H * W);
       for (int q = tid; q < per_plane; q += TC_NT) po[q] = zero4;
     }
@@ -1979,7 +2033,9 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
       if (!touched) {
         const uint4 z = make_uint4(0, 0, 0, 0);
         TC_BAND_THROTTLE();
-        if (FMT == TC_FMT_CLASSES) {
+        if (BITS) {
+          for (int c = 0; c < C; c++) packed_zero_words(out + ((size_t)c * H + y0) * wpr * 4, rows * wpr, tid);
+        } else if (CLS) {
           const int per_plane = rows * (W >> 4);
           for (int c = 0; c < C; c++) {
             uint4* dst = (uint4*)(out + ((size_t)c * H + y0) * W);
@@ -2215,7 +2271,7 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
       }
     }
     lds_sync();
-    if (FMT == TC_FMT_CLASSES && a.noise_blobs > 0) {
+    if (CLS && a.noise_blobs > 0) {
       // NoiseObservationWrapper (wrapper/observation.py:15-27) on the bit-planes, before they are expanded: the frame
       // never makes the extra round trip through HBM a pass of its own costs (71 us per step on cfg3 in round 1).
       // Every operation of the reference is per pixel -- plane c |= plane src & circle, or plane c &= ~circle, blob
@@ -2287,7 +2343,19 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
     const RCam& cam = a.cam;
     if (cam.n_bands > 1) TC_BAND_THROTTLE();
     if (DBG_ON(a.flags, DBG_SKIP_STORE)) {
-    } else if (FMT == TC_FMT_CLASSES) {
+    } else if (BITS) {
+      // packed class masks: the store phase is a copy of the band's rows, plane by plane (planes of layers without a
+      // segment: zeros, unless they went out at the head of the stage)
+      for (int c = 0; c < C; c++) {
+        if ((early_zero >> c) & 1u) continue;
+        unsigned char* po = out + ((size_t)c * H + y0) * wpr * 4;
+        const int w0 = c * cam.band_rows * wpr;
+        if ((used_layers >> c) & 1u)
+          packed_copy_words(po, bits + w0, w0, rows * wpr, tid);
+        else
+          packed_zero_words(po, rows * wpr, tid);
+      }
+    } else if (CLS) {
       if ((W & 15) == 0) {
         // 16 pixels -> one 16-byte store per lane, consecutive lanes on consecutive addresses
         // (two 16-byte stores per lane at a 32-byte lane stride were tried: 2x slower, half-line writes)
@@ -2478,7 +2546,7 @@ struct NArgs {
   unsigned int inv_cpr;  // 2^32 / (W / 16) + 1, for fdiv by the 16-pixel chunks per row
 };
 
-__global__ void tc_noise_tick(unsigned int* step, unsigned int n) { *step += n; }
+TC_PLAIN_KERNEL __global__ void tc_noise_tick(unsigned int* step, unsigned int n) { *step += n; }
 
 // q / d for q < 2^31 with inv = 2^32 / d + 1 (host): one multiply-high and a fix-up instead of a ~30-instruction
 // runtime division (as first written this kernel spent most of its ~12 k instructions per wavefront dividing indices)
@@ -2490,7 +2558,7 @@ __device__ __forceinline__ int fdiv(int q, int d, unsigned int inv) {
 }
 
 // LDS: bit-planes of one band | blob rows [nb][5] | per blob the span-table row of its radius [nb][max_radius]
-__global__ __launch_bounds__(TC_NT) void tc_noise_kernel(NArgs a) {
+TC_PLAIN_KERNEL __global__ __launch_bounds__(TC_NT) void tc_noise_kernel(NArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int env = blockIdx.x, tid = threadIdx.x;
   if (env >= a.N) return;
@@ -3418,7 +3486,7 @@ __device__ __forceinline__ void step_kernel_body() {
       else
         lds_sync();
       const StepArgs& sb = step_args();
-      const size_t obs_step = sb.ma.roll.obs ? (size_t)sb.a.N * ((size_t)sb.r.cam.H * sb.r.cam.W * (FMT == TC_FMT_CLASSES ? sb.r.C : 3)) : 0;
+      const size_t obs_step = sb.ma.roll.obs ? (size_t)sb.a.N * tc_obs_bytes_of(FMT, sb.r.C, sb.r.cam.H, sb.r.cam.W) : 0;
       unsigned char* obs_base = sb.ma.roll.obs ? sb.ma.roll.obs : sb.r.obs;
       raster_body<THICK, FMT, false, RBT>(sb.r, smem, env, obs_base + (size_t)k * obs_step, tid, 0, nseg, used, k);
       if (tid == 0) step_args().a.seg_n[env] = nseg;  // workload statistics only
@@ -3460,7 +3528,7 @@ __global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_drive
 #define TC_ORDER_BINS 256
 // (the keys are read ONCE, into LDS: the lengths may belong to a frame row another stream is about to redraw, and a key
 // that changed between the counting and the placing pass would break the permutation)
-__global__ __launch_bounds__(TC_ORDER_NT) void tc_order_kernel(const int* cost, int N, int G, int* order) {
+TC_PLAIN_KERNEL __global__ __launch_bounds__(TC_ORDER_NT) void tc_order_kernel(const int* cost, int N, int G, int* order) {
   __shared__ int hist[TC_ORDER_BINS], cursor[TC_ORDER_BINS];
   extern __shared__ unsigned char okeys[];  // [N]
   const int t = threadIdx.x;
@@ -3501,12 +3569,50 @@ __global__ __launch_bounds__(TC_ORDER_NT) void tc_order_kernel(const int* cost, 
 // (they count themselves into *resident).  One wavefront, so it cannot keep them off the chip itself; the frame
 // kernel behind it in stream order then finds its producers resident whatever it fills the chip with.  Bounded: after
 // `ticks` (100 MHz) it lets the frame kernel go regardless, whose workgroups have a bound of their own.
-__global__ __launch_bounds__(64) void tc_gate_kernel(const unsigned int* resident, unsigned int want, long long ticks) {
+TC_PLAIN_KERNEL __global__ __launch_bounds__(64) void tc_gate_kernel(const unsigned int* resident, unsigned int want, long long ticks) {
   const long long t0 = wall_clock64();
   while (__hip_atomic_load(resident, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want && wall_clock64() - t0 < ticks)
     __builtin_amdgcn_s_sleep(2);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The instantiations of parts 1-5 (see TC_PART), D = `template` where they are compiled, `extern template` in part 0.
+// (K, RB) pairs: StepKRb / FrameKRb of the codes 516, 5, 8, 9.
+#define TC_INST_STEP(D, KERN, C, K, RB, T, F)                         \
+  D __global__ void KERN<K, T, F, RB, C>(StepArgs);                     \
+  D __global__ void KERN<K, T, F, RB, (C) | TC_FEAT_CAR>(StepArgs);     \
+  D __global__ void KERN<K, T, F, RB, (C) | TC_FEAT_EP>(StepArgs);      \
+  D __global__ void KERN<K, T, F, RB, (C) | TC_FEAT_ALL>(StepArgs);
+#define TC_INST_STEP_T(D, KERN, C, K, RB, F) TC_INST_STEP(D, KERN, C, K, RB, true, F) TC_INST_STEP(D, KERN, C, K, RB, false, F)
+#define TC_INST_STEP_F(D, KERN, C, F)                                                             \
+  TC_INST_STEP_T(D, KERN, C, 5, 16, F) TC_INST_STEP_T(D, KERN, C, 5, RB_OF_K(5), F)                 \
+  TC_INST_STEP_T(D, KERN, C, 8, RB_OF_K(8), F) TC_INST_STEP_T(D, KERN, C, 9, RB_OF_K(9), F)
+#define TC_INST_PART1(D) TC_INST_STEP_F(D, tc_drive_step_kernel, TC_FEAT_CTRL, TC_FMT_CLASSES)
+#define TC_INST_PART3(D) TC_INST_STEP_F(D, tc_drive_step_kernel, TC_FEAT_CTRL, TC_FMT_RGB)
+#define TC_INST_PART4(D) TC_INST_STEP_F(D, tc_step_kernel, 0u, TC_FMT_CLASSES)
+#define TC_INST_PART5(D) TC_INST_STEP_F(D, tc_step_kernel, 0u, TC_FMT_RGB)
+#define TC_INST_PFRAME2(D, K, RB, T)                                                        \
+  D __global__ void tc_frame_kernel<K, T, TC_FMT_CLASSES_BITS, RB>(FrameArgs);                \
+  D __global__ void tc_frame_recover_kernel<K, T, TC_FMT_CLASSES_BITS, RB>(FrameArgs);
+#define TC_INST_PFRAME(D, K, RB) TC_INST_PFRAME2(D, K, RB, true) TC_INST_PFRAME2(D, K, RB, false)
+#define TC_INST_PART2(D)                                                                                                  \
+  TC_INST_PFRAME(D, 5, 16) TC_INST_PFRAME(D, 5, RB_OF_K(5)) TC_INST_PFRAME(D, 8, RB_OF_K(8)) TC_INST_PFRAME(D, 9, RB_OF_K(9)) \
+  D __global__ void tc_raster_kernel<true, TC_FMT_CLASSES_BITS>(RArgs);                                                     \
+  D __global__ void tc_raster_kernel<false, TC_FMT_CLASSES_BITS>(RArgs);
+#define TC_INST_UNPACK(D)                                                                                                          \
+  D __global__ void tc_unpack_bits_kernel<TC_U8>(const unsigned int*, long long, long long, const long long*, long long, uint4*);   \
+  D __global__ void tc_unpack_bits_kernel<TC_F16>(const unsigned int*, long long, long long, const long long*, long long, uint4*);  \
+  D __global__ void tc_unpack_bits_kernel<TC_BF16>(const unsigned int*, long long, long long, const long long*, long long, uint4*); \
+  D __global__ void tc_unpack_bits_kernel<TC_F32>(const unsigned int*, long long, long long, const long long*, long long, uint4*);
+#if defined(TC_PART) && TC_PART == 0
+TC_INST_PART1(extern template)
+TC_INST_PART2(extern template)
+TC_INST_PART3(extern template)
+TC_INST_PART4(extern template)
+TC_INST_PART5(extern template)
+#endif
+
+#if !defined(TC_PART) || TC_PART == 0
 // ---------------------------------------------------------------------------------------------
 // From run-time choices to a kernel: lift(f, Among<T, ..>{v}, ..) calls f with one std::integral_constant per choice --
 // the value of the list that v equals, the LAST of the list when it equals none -- so f can use them as template arguments.
@@ -3558,7 +3664,9 @@ using Bools = Among<bool, true, false>;
 using Kvars = Among<int, TC_DEV_KV>;
 using Kcodes = Among<int, 0>;
 using Thicks = Among<bool, true>;
-using Fmts = Among<int, TC_DEV_FMTV>;
+// (the fused step kernels have no packed variant: a packed dev build compiles their byte class-mask form, which a packed env never launches)
+using Fmts = Among<int, (TC_DEV_FMTV == TC_FMT_CLASSES_BITS ? TC_FMT_CLASSES : TC_DEV_FMTV)>;
+using FrameFmts = Among<int, TC_DEV_FMTV>;
 template <int> struct StepKRb { static constexpr int K = TC_DEV_SK, RB = TC_DEV_SRB; };
 template <int> struct FrameKRb { static constexpr int K = TC_DEV_FK, RB = TC_DEV_FRB; };
 #else
@@ -3566,6 +3674,10 @@ using Kvars = Among<int, 5, 8, 9, 13>;
 using Kcodes = Among<int, 516, 5, 8, 9>;
 using Thicks = Bools;
 using Fmts = Among<int, TC_FMT_CLASSES, TC_FMT_RGB>;
+// tc_frame_kernel, tc_frame_recover_kernel and tc_raster_kernel also exist for packed class masks (TC_FMT_CLASSES_BITS); the
+// fused tc_step_kernel / tc_drive_step_kernel family -- the bulk of the build -- does not: plan_call() never sends a packed
+// env there
+using FrameFmts = Among<int, TC_FMT_CLASSES, TC_FMT_CLASSES_BITS, TC_FMT_RGB>;
 template <int CODE> struct StepKRb { static constexpr int K = CODE == 516 ? 5 : CODE, RB = CODE == 516 ? 16 : RB_OF_K(CODE); };
 template <int CODE> using FrameKRb = StepKRb<CODE>;
 #endif
@@ -3599,12 +3711,77 @@ static frame_kern_t frame_kernel_of(int kcode, bool thick, int fmt, bool recover
         if constexpr (rec) return tc_frame_recover_kernel<FrameKRb<kc>::K, t, f, FrameKRb<kc>::RB>;
         else return tc_frame_kernel<FrameKRb<kc>::K, t, f, FrameKRb<kc>::RB>;
       },
-      Kcodes{kcode}, Thicks{thick}, Fmts{fmt}, Bools{recover});
+      Kcodes{kcode}, Thicks{thick}, FrameFmts{fmt}, Bools{recover});
 }
 static raster_kern_t raster_kernel_of(bool thick, int fmt) {
-  return lift([](auto t, auto f) -> raster_kern_t { return tc_raster_kernel<t, f>; }, Thicks{thick}, Fmts{fmt});
+  return lift([](auto t, auto f) -> raster_kern_t { return tc_raster_kernel<t, f>; }, Thicks{thick}, FrameFmts{fmt});
 }
 
+#endif  // part 0: the kernel tables
+
+// ---------------------------------------------------------------------------------------------
+// tc_unpack_bits: packed class masks (TC_FMT_CLASSES_BITS) -> [n_out][planes][H][W] of u8 0/255 or f16 / bf16 / f32 0.0/1.0,
+// optionally gathered through an index (the replay-buffer sample).  Bandwidth only: 1 bit read, 1-4 bytes written per pixel.
+// W % 32 == 0, so a frame is one run of 32-bit words on the packed side (pixel p of the frame is bit p & 31 of word p >> 5)
+// and one run of pixels on the other: a lane owns the P = 16 / 8 / 4 pixels of ONE 16-byte store, consecutive lanes store to
+// consecutive addresses, and the 2 / 4 / 8 lanes that share a packed word read it with one address (a wavefront reads
+// 128 / 64 / 32 consecutive bytes per round, once).  Workgroup (x, y) strides over the 256-store chunks of a frame and over
+// the output frames, so one launch covers any n_out; the frame's source index is one scalar load per frame.
+// An index outside [0, n_src) reads nothing and stores zeros.
+template <int DT>
+__global__ __launch_bounds__(256) void tc_unpack_bits_kernel(const unsigned int* __restrict__ src, const long long n_src,
+                                                             const long long frame_words, const long long* __restrict__ index,
+                                                             const long long n_out, uint4* __restrict__ dst) {
+  constexpr int P = DT == TC_U8 ? 16 : DT == TC_F32 ? 4 : 8;  // pixels of one 16-byte store
+  constexpr unsigned int ONE16 = DT == TC_F16 ? 0x3C00u : 0x3F80u;  // 1.0 as f16 / bf16
+  const long long items = frame_words * (32 / P);              // 16-byte stores per frame
+  for (long long j = blockIdx.y; j < n_out; j += gridDim.y) {
+    const long long f = index ? index[j] : j;
+    const bool inside = f >= 0 && f < n_src;  // (workgroup-uniform)
+    const unsigned int* sf = src + (inside ? f : 0) * frame_words;
+    uint4* df = dst + j * items;
+    for (long long it = (long long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long long)gridDim.x * 256) {
+      const long long p0 = it * P;
+      unsigned int b = 0;
+      if (inside) b = (sf[p0 >> 5] >> (unsigned)(p0 & 31)) & ((1u << P) - 1u);
+      uint4 o;
+      if (DT == TC_U8) {
+        o.x = spread4(b & 15u);
+        o.y = spread4((b >> 4) & 15u);
+        o.z = spread4((b >> 8) & 15u);
+        o.w = spread4(b >> 12);
+      } else if (DT == TC_F32) {
+        o.x = (b & 1u) ? 0x3F800000u : 0u;
+        o.y = (b & 2u) ? 0x3F800000u : 0u;
+        o.z = (b & 4u) ? 0x3F800000u : 0u;
+        o.w = (b & 8u) ? 0x3F800000u : 0u;
+      } else {
+        o.x = ((b & 1u) ? ONE16 : 0u) | ((b & 2u) ? ONE16 << 16 : 0u);
+        o.y = ((b & 4u) ? ONE16 : 0u) | ((b & 8u) ? ONE16 << 16 : 0u);
+        o.z = ((b & 16u) ? ONE16 : 0u) | ((b & 32u) ? ONE16 << 16 : 0u);
+        o.w = ((b & 64u) ? ONE16 : 0u) | ((b & 128u) ? ONE16 << 16 : 0u);
+      }
+      df[it] = o;
+    }
+  }
+}
+
+#if defined(TC_PART) && TC_PART == 1
+TC_INST_PART1(template)
+#elif defined(TC_PART) && TC_PART == 2
+TC_INST_PART2(template)
+TC_INST_UNPACK(template)
+#elif defined(TC_PART) && TC_PART == 3
+TC_INST_PART3(template)
+#elif defined(TC_PART) && TC_PART == 4
+TC_INST_PART4(template)
+#elif defined(TC_PART) && TC_PART == 5
+TC_INST_PART5(template)
+#elif defined(TC_PART)
+TC_INST_UNPACK(extern template)
+#endif
+
+#if !defined(TC_PART) || TC_PART == 0
 // =============================================================================================
 // Host side: C ABI
 // =============================================================================================
@@ -4078,8 +4255,12 @@ static void fill_car_constants(DevCar& c, const tc_car_params* car) {
 static int fill_camera(tc_env* e, const tc_camera_params* cam) {
   if (cam->height < 1 || cam->width < 1 || cam->height > 16384 || cam->width > 16384 || cam->line_thickness < 1 ||
       cam->line_thickness > 255 || !(cam->max_range > 0) ||
-      (cam->format != TC_FMT_RGB && cam->format != TC_FMT_CLASSES)) {
-    set_err("camera: need height,width,line_thickness >= 1, max_range > 0, format rgb|classes");
+      (cam->format != TC_FMT_RGB && !TC_FMT_IS_CLASSES(cam->format))) {
+    set_err("camera: need height,width,line_thickness >= 1, max_range > 0, format rgb|classes|classes_bits");
+    return TC_E_INVALID;
+  }
+  if (cam->format == TC_FMT_CLASSES_BITS && cam->width % 32 != 0) {
+    set_err("camera: TC_FMT_CLASSES_BITS needs a width that is a multiple of 32 (a packed row is the row's 32-bit words)");
     return TC_E_INVALID;
   }
   DevCam& c = e->k.cam;
@@ -4281,8 +4462,8 @@ static int raise_lds_limits(const tc_env* e) {
   if (lds > 48 * 1024)  // every tc_step_kernel and tc_frame_kernel variant
     for (int kcode : {516, 5, 8, 9})
       for (int t = 0; t < 2; t++)
-        for (int fmt : {TC_FMT_CLASSES, TC_FMT_RGB}) {
-          for (unsigned feat = 0; feat <= (TC_FEAT_CTRL | TC_FEAT_ALL); feat++)
+        for (int fmt : {TC_FMT_CLASSES, TC_FMT_CLASSES_BITS, TC_FMT_RGB}) {
+          for (unsigned feat = 0; feat <= (TC_FEAT_CTRL | TC_FEAT_ALL) && fmt != TC_FMT_CLASSES_BITS; feat++)
             raise((const void*)step_kernel_of(kcode, t, fmt, feat), lds, (feat & TC_FEAT_CTRL) ? "tc_drive_step_kernel" : "tc_step_kernel");
           raise((const void*)frame_kernel_of(kcode, t, fmt, false), lds, "tc_frame_kernel");
         }
@@ -4294,7 +4475,7 @@ static int raise_lds_limits(const tc_env* e) {
             (feat & TC_FEAT_CTRL) ? "tc_drive_envg_kernel" : "tc_envg_kernel");
   if (e->r_lds > 48 * 1024)
     for (int t = 0; t < 2; t++)
-      for (int fmt : {TC_FMT_CLASSES, TC_FMT_RGB}) raise((const void*)raster_kernel_of(t, fmt), e->r_lds, "tc_raster_kernel");
+      for (int fmt : {TC_FMT_CLASSES, TC_FMT_CLASSES_BITS, TC_FMT_RGB}) raise((const void*)raster_kernel_of(t, fmt), e->r_lds, "tc_raster_kernel");
   if (total > 48 * 1024) {
     static const int kvs[4] = {5, 8, 9, 13};
     for (int i = 0; i < 64; i++)  // every tc_env_kernel / tc_drive_env_kernel variant
@@ -4402,7 +4583,7 @@ extern "C" int tc_env_create(const tc_map* map, const tc_car_params* car, const 
   }
   rc = raise_lds_limits(e.get());
   if (rc != TC_OK) return rc;
-  e->obs_bytes = (int64_t)dc.H * dc.W * (dc.format == TC_FMT_CLASSES ? m.C : 3);
+  e->obs_bytes = (int64_t)tc_obs_bytes_of(dc.format, m.C, dc.H, dc.W);
   rc = alloc_draw_lists(e.get());
   if (rc != TC_OK) return rc;
   alloc_orders(e.get());
@@ -4695,7 +4876,7 @@ extern "C" int tc_env_set_noise(tc_env* e, int32_t n_blobs, int32_t max_radius, 
     e->noise_blobs = 0;
     return TC_OK;
   }
-  if (e->k.cam.format != TC_FMT_CLASSES) {
+  if (!TC_FMT_IS_CLASSES(e->k.cam.format)) {
     set_err("tc_env_set_noise: only class-mask observations (wrapper/observation.py:7)");
     return TC_E_INVALID;
   }
@@ -4775,6 +4956,10 @@ extern "C" int tc_noise(tc_env* e, const int32_t* blobs, void* stream) {
   }
   if (e->noise_blobs < 1) {
     set_err("tc_noise: call tc_env_set_noise first");
+    return TC_E_INVALID;
+  }
+  if (e->k.cam.format == TC_FMT_CLASSES_BITS) {
+    set_err("tc_noise: the stand-alone pass reads byte class masks; a packed env gets its noise inside the raster stage");
     return TC_E_INVALID;
   }
   return launch_noise(e, blobs, stream);
@@ -4894,7 +5079,7 @@ static RArgs make_rargs(tc_env* e, const int* seg_g, const int* seg_n, int seg_c
   r.seg_row0 = 0;
   r.noise_row0 = 0;
   r.obs_row_stride = 0;
-  if (with_noise && e->noise_blobs > 0 && c.format == TC_FMT_CLASSES) {
+  if (with_noise && e->noise_blobs > 0 && TC_FMT_IS_CLASSES(c.format)) {
     r.noise_blobs = e->noise_blobs;
     r.noise_max_radius = e->noise_max_radius;
     r.noise_hw = e->noise_hw;
@@ -4921,7 +5106,7 @@ static int launch_raster(tc_env* e, const int* seg_g, const int* seg_n, int seg_
 
 static int noise_advance(tc_env* e, int mode, bool rendered, int nsteps, void* stream) {
   // the fused noise consumed one position of the blob stream per step of this launch
-  if (rendered && mode == MODE_STEP && e->noise_blobs > 0 && e->k.cam.format == TC_FMT_CLASSES) {
+  if (rendered && mode == MODE_STEP && e->noise_blobs > 0 && TC_FMT_IS_CLASSES(e->k.cam.format)) {
     hipLaunchKernelGGL(tc_noise_tick, dim3(1), dim3(1), 0, (hipStream_t)stream, e->noise_step, (unsigned int)nsteps);
     HIP_TRY(hipGetLastError());
   }
@@ -4945,11 +5130,14 @@ struct CallPlan {
 static CallPlan plan_call(const tc_env* e, uint32_t flags, int nsteps, bool obs, bool all) {
   CallPlan p;
   // (the register-hungry K = 13 simulate stage spills when fused, so it stays two launches)
-  const bool can_fuse = e->tune.fuse && e->kvar != 13;
+  const bool can_frames = e->tune.fuse && e->kvar != 13;
+  // packed class masks have tc_frame_kernel and tc_raster_kernel variants only: a single step is the two-launch form, K steps
+  // are always split (TC_MULTI_SPLIT=0 is ignored)
+  const bool can_fuse = can_frames && e->k.cam.format != TC_FMT_CLASSES_BITS;
   p.do_raster = !(flags & (TC_F_NO_OBSERVATION | DBG_SKIP_CAMERA)) && obs;
   p.split = p.do_raster && nsteps > 1 && (e->tune.multi_split || !can_fuse);
   p.fused = p.do_raster && can_fuse && !p.split;
-  p.frames = p.split && can_fuse;
+  p.frames = p.split && can_frames;
   p.piped = p.frames && e->tune.env_grouped && e->tune.pipe && all;
   p.streamed = p.piped && e->tune.stream && e->streamed.rows >= 2 && e->st_words;
   p.steps = nsteps;
@@ -5361,6 +5549,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
   if (plan.fused) {  // one launch: simulate + raster by the same wavefront
     // (component groups that fit the K = 5 register cache: the K = 5 kernel with 16-segment batches, as for the frame kernel --
     // its simulate stage then walks the map's lane-line nodes in windows of 320 instead of 576)
+    assert(fmt != TC_FMT_CLASSES_BITS);  // (plan_call)
     step_kern_t fk = step_kernel_of(e->kframe == 516 ? 516 : kv, thick, fmt, feat);
     sa.r = make_rargs(e, e->k.seg_g, e->k.seg_n, e->k.seg_cap, nullptr, flags, 0, nullptr, mode == MODE_STEP);
     // covers both stages and the parked state; behind it, up to the size that costs the CU no workgroup, the head of the
@@ -5511,3 +5700,40 @@ extern "C" int tc_render_segments(tc_env* e, const int32_t* segments, const int3
 extern "C" int tc_render(tc_env* e, uint32_t flags, void* stream) {
   return launch(e, MODE_RENDER, nullptr, TC_F32, nullptr, nullptr, nullptr, flags & ~TC_F_NO_OBSERVATION, stream);
 }
+
+extern "C" int tc_unpack_bits(const uint8_t* packed, int64_t n_src_frames, int32_t planes, int32_t H, int32_t W,
+                              const int64_t* index, int64_t n_out, void* dst, int32_t dst_dtype, void* stream) {
+  // (every check comes before the first HIP call: a bad argument is reported on a machine without a device too)
+  if (!packed || !dst || n_src_frames < 1 || planes < 1 || H < 1 || W < 1 || W % 32 != 0 || n_out < 0 ||
+      (!index && n_out > n_src_frames) ||
+      (dst_dtype != TC_U8 && dst_dtype != TC_F16 && dst_dtype != TC_BF16 && dst_dtype != TC_F32)) {
+    set_err("tc_unpack_bits: need packed and dst, positive sizes, W % 32 == 0, dst_dtype TC_U8|TC_F16|TC_BF16|TC_F32, "
+            "n_out >= 0, and n_out <= n_src_frames without an index");
+    return TC_E_INVALID;
+  }
+  if (((uintptr_t)packed & 3u) || ((uintptr_t)dst & 15u)) {
+    set_err("tc_unpack_bits: packed must be 4-byte aligned and dst 16-byte aligned");
+    return TC_E_INVALID;
+  }
+  if (n_out == 0) return TC_OK;
+  const long long frame_words = (long long)planes * H * (W / 32);
+  const int per_word = dst_dtype == TC_U8 ? 2 : dst_dtype == TC_F32 ? 8 : 4;  // 16-byte stores per packed word
+  const long long chunks = (frame_words * per_word + 255) / 256;
+  // enough workgroups to fill the device several times over, each with several stores in flight per lane
+  const unsigned int gx = (unsigned int)(chunks < 64 ? chunks : (chunks + 3) / 4 < 64 ? 64 : (chunks + 3) / 4 < 1024 ? (chunks + 3) / 4 : 1024);
+  const long long want_y = (32768 + gx - 1) / gx;
+  const unsigned int gy = (unsigned int)(n_out < want_y ? n_out : want_y);
+  const dim3 grid(gx, gy), block(256);
+  const unsigned int* src = (const unsigned int*)packed;
+  const long long* idx = (const long long*)index;
+  hipStream_t st = (hipStream_t)stream;
+  switch (dst_dtype) {
+    case TC_U8: hipLaunchKernelGGL(tc_unpack_bits_kernel<TC_U8>, grid, block, 0, st, src, (long long)n_src_frames, frame_words, idx, (long long)n_out, (uint4*)dst); break;
+    case TC_F16: hipLaunchKernelGGL(tc_unpack_bits_kernel<TC_F16>, grid, block, 0, st, src, (long long)n_src_frames, frame_words, idx, (long long)n_out, (uint4*)dst); break;
+    case TC_BF16: hipLaunchKernelGGL(tc_unpack_bits_kernel<TC_BF16>, grid, block, 0, st, src, (long long)n_src_frames, frame_words, idx, (long long)n_out, (uint4*)dst); break;
+    default: hipLaunchKernelGGL(tc_unpack_bits_kernel<TC_F32>, grid, block, 0, st, src, (long long)n_src_frames, frame_words, idx, (long long)n_out, (uint4*)dst); break;
+  }
+  HIP_TRY(hipGetLastError());
+  return TC_OK;
+}
+#endif  // part 0: the host side

@@ -173,7 +173,7 @@ class TinyCarloVecEnv(gym.Env):
     def __init__(self, config: Union[str, Dict[str, Any]], num_envs: Optional[int] = None,
                  device: Union[None, str, torch.device] = None, render_mode: Optional[str] = None,
                  return_numpy: bool = False, autoreset: bool = False, spawn_queue_len: int = 64,
-                 spawn: str = "host"):
+                 spawn: str = "host", obs_packing: Optional[str] = None):
         self.config, self.config_path = load_config(config)
         sim = self.config["sim"]
         self.fps: int = sim.get("fps", 30)
@@ -213,12 +213,27 @@ class TinyCarloVecEnv(gym.Env):
         self.n_classes = len(self.layer_names)
         H, W = self.camera.resolution
         self._fmt = nat.FMT_CLASSES if self.observation_space_format == "classes" else nat.FMT_RGB
+        # obs_packing="bits": class masks leave the kernels bit-packed, uint8 [C, H, W/8] per env (TC_FMT_CLASSES_BITS,
+        # tinycarlo_amd/packing.py); unpack_obs expands them on the device.  An opt-in of the batched env, not a value of
+        # sim.observation_space_format: the reference has no such format.
+        if obs_packing not in (None, "bits"):
+            raise ValueError("obs_packing must be None or 'bits'")
+        if obs_packing == "bits":
+            if self.observation_space_format != "classes":
+                raise ValueError("obs_packing='bits' needs observation_space_format='classes'")
+            if W % 32 != 0:
+                raise ValueError(f"obs_packing='bits' needs a camera width that is a multiple of 32, not {W}")
+            if render_mode == "rgb_array":
+                raise ValueError("obs_packing='bits' cannot be combined with render_mode='rgb_array'")
+            self._fmt = nat.FMT_CLASSES_BITS
+        self.obs_packing = obs_packing
 
         # spaces (env.py:64-73): per-env spaces; batched tensors carry a leading num_envs axis
         self.single_action_space = gym.spaces.Dict({
             "car_control": gym.spaces.Box(-1, 1, shape=(2,), dtype=np.float32),
             "maneuver": gym.spaces.Discrete(4)})
-        obs_shape = (self.n_classes, H, W) if self._fmt == nat.FMT_CLASSES else (H, W, 3)
+        obs_shape = ((self.n_classes, H, W // 8) if self._fmt == nat.FMT_CLASSES_BITS else
+                     (self.n_classes, H, W) if self._fmt == nat.FMT_CLASSES else (H, W, 3))
         self.single_observation_space = gym.spaces.Box(low=0, high=255, shape=obs_shape, dtype=np.uint8)
         self.action_space = self.single_action_space
         self.observation_space = self.single_observation_space
@@ -629,7 +644,7 @@ class TinyCarloVecEnv(gym.Env):
     def set_noise(self, n_blobs: int, max_radius: int = 100, seed: int = 0) -> None:
         """Blob noise on class-mask observations after every step (tc_env_set_noise); n_blobs = 0 switches it off.
         Blobs are drawn on the device -- the reference's global ``np.random`` stream cannot be reproduced for a batch."""
-        if n_blobs and self._fmt != nat.FMT_CLASSES:
+        if n_blobs and self._fmt not in (nat.FMT_CLASSES, nat.FMT_CLASSES_BITS):
             raise ValueError("observation noise needs observation_space_format='classes' (wrapper/observation.py:7)")
         self._push_noise(int(n_blobs), int(max_radius), int(seed) & 0xFFFFFFFFFFFFFFFF)
         self.noise = (int(n_blobs), int(max_radius), int(seed) & 0xFFFFFFFFFFFFFFFF)
@@ -648,6 +663,13 @@ class TinyCarloVecEnv(gym.Env):
             nat.check(nat.lib().tc_noise(self._h, bt.data_ptr() if bt is not None else None, self._stream()), "tc_noise")
         self._keep = (bt,)
         return self.out["obs"]
+
+    @staticmethod
+    def unpack_obs(packed: torch.Tensor, dtype: torch.dtype = torch.float32, index: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Bit-packed observations -> [..., C, H, W] of ``dtype`` on the device (tinycarlo_amd.packing.unpack_obs)."""
+        from .packing import unpack_obs
+        return unpack_obs(packed, dtype=dtype, index=index, out=out)
 
     def _to_dev(self, key: str, a, dtype: torch.dtype, shape: Tuple[int, ...]) -> torch.Tensor:
         if isinstance(a, torch.Tensor):
