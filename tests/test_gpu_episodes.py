@@ -12,6 +12,7 @@ import pytest
 
 import orc
 from common import load_cfg
+from feature_ref import Ref  # the expected run: an oracle env plus rules 1-3 in numpy
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -62,67 +63,6 @@ def actions(K, N, seed, lo=0.5):
 def bits(a):
     a = np.ascontiguousarray(a)
     return a.view(np.int64) if a.dtype == np.float64 else a
-
-
-class Ref:
-    """the expected run: an oracle env plus rules 1-3 in numpy"""
-
-    def __init__(self, oenv, limit, length0=None):
-        N = oenv.num_envs
-        self.o, self.N = oenv, N
-        self.limit = np.broadcast_to(np.asarray(limit, dtype=np.int64), (N,)).copy()
-        self.ep = {"length": np.zeros(N, np.int32), "ret": np.zeros(N, np.float64), "count": np.zeros(N, np.int32),
-                   "last_length": np.zeros(N, np.int32), "last_return": np.zeros(N, np.float64),
-                   "length_sum": np.zeros(N, np.int64), "return_sum": np.zeros(N, np.float64)}
-        if length0 is not None:
-            self.ep["length"][:] = length0
-        self.respawns = np.zeros(N, np.int64)
-        self.by_limit = np.zeros(N, bool)
-        self.by_other = np.zeros(N, bool)
-
-    def reset(self, seed, mask=None):
-        self.o.reset(seed=seed, mask=mask)
-        sel = np.ones(self.N, bool) if mask is None else np.asarray(mask).astype(bool)
-        self.ep["length"][sel] = 0
-        self.ep["ret"][sel] = 0.0
-
-    def step(self, cc, man):
-        o, ep = self.o, self.ep
-        fresh = o._aux["needs_reset"].numpy().astype(bool) if o.autoreset else np.zeros(self.N, bool)
-        o.step_device(torch.from_numpy(np.ascontiguousarray(cc)), torch.from_numpy(np.ascontiguousarray(man)))
-        out = {k: v.numpy().copy() for k, v in o.out.items()}
-        left_alone = (out["status"] & S_NOT_RESET) != 0
-        ep["length"][fresh] = 0
-        ep["ret"][fresh] = 0.0
-        run = ~fresh & ~left_alone
-        ep["length"][run] += 1
-        tl = run & (self.limit > 0) & (ep["length"] >= self.limit)
-        out["truncated"] = out["truncated"] | tl.astype(np.uint8)
-        out["status"] = out["status"] | (tl.astype(np.int32) * S_TIME_LIMIT)
-        for i in np.flatnonzero(run):  # one float64 add per step, in step order
-            ep["ret"][i] = ep["ret"][i] + out["reward"][i]
-        done = run & ((out["terminated"] | out["truncated"]) != 0)
-        ep["last_length"][done] = ep["length"][done]
-        ep["last_return"][done] = ep["ret"][done]
-        ep["count"][done] += 1
-        ep["length_sum"][done] += ep["length"][done]
-        for i in np.flatnonzero(done):
-            ep["return_sum"][i] = ep["return_sum"][i] + ep["ret"][i]
-        o.request_reset(torch.from_numpy(tl))  # the device re-spawns these on its next step: so must the oracle
-        self.respawns += fresh
-        self.by_limit |= tl
-        self.by_other |= done & ~tl
-        out["state"] = {k: v.numpy().copy() for k, v in o.state.items()}
-        out["needs_reset"] = o._aux["needs_reset"].numpy().copy()
-        out["spawn_cursor"] = o._aux["spawn_cursor"].numpy().copy()
-        out["ep"] = {k: v.copy() for k, v in ep.items()}
-        return out
-
-    def assert_not_vacuous(self, twice=True):
-        assert self.by_limit.any(), "no env was truncated by the limit"
-        assert self.by_other.any(), "no env ended by a termination / car truncation before its limit"
-        if twice:
-            assert self.respawns.max() >= 2, "no env was re-spawned twice"
 
 
 def check_step(env, exp, label, obs=True):
