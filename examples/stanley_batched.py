@@ -4,7 +4,7 @@
 controller reads cte / heading_error from the env's device tensors and writes the action tensor, the reference's
 wrappers (CTE sparse reward, CTE and crash termination) run inside the step kernel, finished envs re-spawn on the device.
 
-    python examples/stanley_batched.py [--envs 4096] [--steps 600] [--maneuver 3] [--randomize] [--max-episode-steps N] [--fused K [--packed]]
+    python examples/stanley_batched.py [--envs 4096] [--steps 600] [--maneuver 3] [--randomize] [--max-episode-steps N] [--fused K [--packed] [--randomize-cameras]]
 
 --randomize: every episode of every env drives its own car, drawn on the device at the re-spawn (wheelbase, track width,
 speed and steering limits within +-20 %), plus the steering shift of the reference's TD3 study (examples/train_td3.py:37,
@@ -22,6 +22,12 @@ ends come back in the call's rollout rows.  The default stays the torch loop bel
 --packed (with --fused K): class-mask frames leave the kernels bit-packed (obs_packing="bits": uint8 [C, H, W/8], an eighth
 of the bytes), and a sample of each call's rows is expanded on the device to float16 0.0 / 1.0 -- what a consumer that
 trains on a batch of the rollout does (tinycarlo_amd.unpack_obs).
+
+--randomize-cameras (with --fused K): every episode of every env looks through its own camera, as the data collection of the
+reference's examples/train_stanley_il.py:53-57 does -- an integer pitch from [10, 20) and an integer fov from [90, 130),
+here a bank of the 400 combinations from which each re-spawn draws on the device (vec.randomize_cameras); the index each
+frame was drawn with comes back in the rollout's "camera" rows (vec.camera_bank_params[index]: pitch, roll, yaw, fov, position).
+With --max-episode-steps, so that episodes end, this is that data collection entirely on the device.
 """
 import argparse
 import math
@@ -38,7 +44,7 @@ from tinycarlo_amd.wrapper import CrashTerminationWrapper, CTESparseRewardWrappe
 
 
 def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0", seed=2, randomize=False,
-        max_episode_steps=None, fused=0, packed=False):
+        max_episode_steps=None, fused=0, packed=False, randomize_cameras=False):
     config = bundled_config("config_simple_layout.yaml")
     if packed:  # packing is for class masks: the bundled config with that format
         if not fused:
@@ -56,6 +62,10 @@ def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0",
         vec.randomize_cars({name: (0.8 * getattr(p, name), 1.2 * getattr(p, name))
                             for name in ("wheelbase", "track_width", "max_velocity", "max_steering_angle")}
                            | {"steering_shift": (-0.01, 0.0)}, seed=seed)
+    if randomize_cameras:
+        if not fused:
+            raise ValueError("--randomize-cameras goes with --fused K (the camera of a frame comes back in the rollout rows)")
+        vec.randomize_cameras(orientation={"pitch": range(10, 20)}, fov=range(90, 130), seed=seed)
     env = CrashTerminationWrapper(CTETerminationWrapper(CTESparseRewardWrapper(vec, 0.01), 0.07, number_of_steps=5))
     if max_episode_steps:
         vec.set_time_limit(max_episode_steps)
@@ -74,7 +84,7 @@ def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0",
         calls = [min(fused, steps - s0) for s0 in range(0, steps, fused)]
         prepared = {}
         for n in set(calls):  # (a shorter last call has rows of its own)
-            roll = vec.alloc_rollout(n, keys=("obs", "reward", "terminated", "truncated", "cte"))
+            roll = vec.alloc_rollout(n, keys=("obs", "reward", "terminated", "truncated", "cte") + (("camera",) if randomize_cameras else ()))
             prepared[n] = (vec.prepare_drive(man.expand(n, num_envs).contiguous(), roll), roll)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -109,6 +119,9 @@ def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0",
         out["batch"] = (tuple(batch.shape), str(batch.dtype))
     if randomize:
         out["car_episodes_drawn"] = int(vec.car_episode.sum())
+    if randomize_cameras:
+        out.update(cameras_in_bank=len(vec.camera_bank_params), camera_episodes_drawn=int(vec.camera_episode.sum()),
+                   cameras_in_last_call=int(roll["camera"].unique().numel()))
     if max_episode_steps:
         es = vec.episode_stats
         n_ep = int(es["count"].sum())
@@ -127,6 +140,7 @@ if __name__ == "__main__":
     ap.add_argument("--max-episode-steps", type=int, default=None, help="time limit per episode (kept by the step kernel)")
     ap.add_argument("--fused", type=int, default=0, metavar="K", help="built-in controller: drive() calls of K steps")
     ap.add_argument("--packed", action="store_true", help="with --fused: bit-packed class-mask frames, unpacked in batches")
+    ap.add_argument("--randomize-cameras", action="store_true", help="with --fused: per-episode pitch / fov from a 400-camera bank")
     a = ap.parse_args()
     print(run(a.envs, a.steps, a.maneuver, randomize=a.randomize, max_episode_steps=a.max_episode_steps, fused=a.fused,
-              packed=a.packed))
+              packed=a.packed, randomize_cameras=a.randomize_cameras))

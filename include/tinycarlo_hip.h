@@ -54,6 +54,8 @@ extern "C" {
 #define TC_HAS_CONTROLLER 1
 /* Likewise additive within ABI 6: TC_FMT_CLASSES_BITS, tc_unpack_bits, TC_U8 / TC_F16 / TC_BF16. */
 #define TC_HAS_PACKED_OBS 1
+/* Likewise additive within ABI 6: tc_env_set_camera_bank, tc_camera_bank. */
+#define TC_HAS_CAMERA_BANK 1
 #define TC_MAX_LAYERS 16
 
 /* error codes */
@@ -223,8 +225,44 @@ int tc_env_set_camera(tc_env* env, const tc_camera_params* cam);
 /* Per-env cameras (domain randomisation: examples/train_stanley_il.py:53-57 changes camera.orientation / fov and
  * calls update_params() once per episode; batched, that is one E and K per env).  E: device double [N][12],
  * K: device double [N][9], caller owned and read by every launch until replaced; (NULL, NULL) returns to the shared
- * camera of tc_env_create / tc_env_set_camera.  Resolution, max_range, thickness and format stay shared. */
+ * camera of tc_env_create / tc_env_set_camera.  Resolution, max_range, thickness and format stay shared.  Removes a
+ * camera bank (tc_env_set_camera_bank), whatever the arguments. */
 int tc_env_set_camera_per_env(tc_env* env, const double* E, const double* K);
+/* Per-EPISODE cameras from a bank (the data collection of examples/train_stanley_il.py:53-57 -- a new pitch and fov, then
+ * update_params() and reset(), for every episode -- without leaving a K-step call at each termination).  The bank is `count`
+ * cameras computed on the host like the shared one (so no trigonometry on the device); env i uses camera index[i], and every
+ * re-spawn of env i by the library (tc_reset of an env the mask selects, or a TC_F_AUTORESET re-spawn in either spawn mode
+ * and in every kernel form), before the new pose is set, draws its next one:
+ *   z        = SplitMix64(SplitMix64(seed)[0x63616D])[(env_offset + i) << 32 | episode[i]]
+ *   index[i] = ((z >> 32) * count) >> 32
+ *   episode[i] += 1
+ * (tinycarlo_amd/csrc/tc_rng.h: tc_camera_index; a stream of its own, and a counter apart from the cars').
+ * The index in force when a step was simulated travels WITH that (step, env) to wherever its frame is drawn -- in a streamed,
+ * chunked or recovered K-step call that is possibly after the env has re-spawned again -- so a frame is always projected with
+ * the E and K of the episode it belongs to.  index_rows[k][i] receives the index in force at step k of a tc_step_multi call.
+ * Everything else is as with per-env cameras: resolution, max_range, thickness and format stay shared, draw-list capacity and
+ * plan hold for arbitrary E / K, and the whole-frame cull is off while a bank is installed.  A bank and the static rows of
+ * tc_env_set_camera_per_env exclude each other: installing one removes the other.  bank = NULL returns to the shared camera.
+ * seed, count and env_offset sit in a library-owned device table updated in place (a captured graph sees new settings
+ * without re-capture; a call that changes them waits for the device); the pointers are kernel arguments of the launches
+ * enqueued afterwards (a call that only changes them does not wait).  Because of that wait, do not change seed, count or
+ * env_offset while a stream is being captured (the capture would fail); a call that only installs other index_rows, as one
+ * per K-step call does, is safe there.  An index found outside [0, count) in `index` is read
+ * as count - 1; nothing is read out of bounds.
+ * TC_E_INVALID: a NULL E, K, index or episode, count < 1, n_rows < 0, index_rows with n_rows = 0, and from a tc_step_multi
+ * call of more than n_rows steps while index_rows is set. */
+typedef struct {
+  const double* E;     /* device [count][12] */
+  const double* K;     /* device [count][9] */
+  int32_t count;       /* cameras in the bank */
+  uint32_t env_offset; /* index of env 0 in a larger population (shards draw what one batch would) */
+  uint64_t seed;
+  int32_t* index;      /* device [N], in/out, caller owned: the camera each env uses */
+  int32_t* episode;    /* device [N], in/out, caller owned: cameras drawn so far */
+  int32_t* index_rows; /* device [n_rows][N], out, or NULL */
+  int32_t n_rows;      /* rows of index_rows (0 when it is NULL) */
+} tc_camera_bank;
+int tc_env_set_camera_bank(tc_env* env, const tc_camera_bank* bank); /* NULL = off */
 /* New shared car (Car constants assigned at run time: the reference's Car.step reads them on every step, car.py:70-125).
  * Takes effect for launches enqueued afterwards; T must stay the value of tc_env_create. */
 int tc_env_set_car(tc_env* env, const tc_car_params* car);

@@ -37,9 +37,10 @@ S_TIME_LIMIT = 32  # tc_env_set_episodes: the episode reached its time limit in 
 HAS_EPISODES = 1   # TC_HAS_EPISODES: additive within ABI 6
 HAS_CONTROLLER = 1  # TC_HAS_CONTROLLER: likewise
 CTRL_STANLEY = 1    # TC_CTRL_STANLEY
+HAS_CAMERA_BANK = 1  # TC_HAS_CAMERA_BANK: likewise
 
 EXPORTS = ["tc_abi_version", "tc_last_error", "tc_map_create", "tc_map_destroy", "tc_env_create", "tc_env_destroy",
-           "tc_env_bind", "tc_env_set_camera", "tc_env_set_camera_per_env", "tc_env_set_car", "tc_env_set_car_per_env",
+           "tc_env_bind", "tc_env_set_camera", "tc_env_set_camera_per_env", "tc_env_set_camera_bank", "tc_env_set_car", "tc_env_set_car_per_env",
            "tc_env_set_car_randomization", "tc_env_set_episodes", "tc_env_set_episode_rollout", "tc_env_set_controller", "tc_env_set_terms", "tc_env_set_spawn_table", "tc_env_set_noise", "tc_noise", "tc_env_obs_bytes", "tc_env_lds_bytes", "tc_env_profile",
            "tc_env_profile_read", "tc_reset", "tc_step", "tc_step_multi", "tc_env_reserve_steps", "tc_env_launch_info", "tc_env_draw_list_stats", "tc_render",
            "tc_render_segments", "tc_unpack_bits"]
@@ -86,6 +87,11 @@ class EpisodeBuffers(C.Structure):  # tc_episode_buffers: device arrays of N, le
 class ControllerC(C.Structure):  # tc_controller: gains by value, the rows device arrays [n_rows][N] (steer_last [N]) or NULL
     _fields_ = [("kind", C.c_int32), ("n_rows", C.c_int32), ("k", C.c_double), ("speed", C.c_double),
                 ("steer_noise", C.c_void_p), ("steer_rows", C.c_void_p), ("steer_last", C.c_void_p)]
+
+
+class CameraBankC(C.Structure):  # tc_camera_bank: device pointers; index / episode [N], index_rows [n_rows][N] or NULL
+    _fields_ = [("E", C.c_void_p), ("K", C.c_void_p), ("count", C.c_int32), ("env_offset", C.c_uint32), ("seed", C.c_uint64),
+                ("index", C.c_void_p), ("episode", C.c_void_p), ("index_rows", C.c_void_p), ("n_rows", C.c_int32)]
 
 
 class TermC(C.Structure):  # tc_term
@@ -138,6 +144,7 @@ def lib():
     L.tc_env_bind.argtypes = [C.c_void_p, C.POINTER(Buffers)]
     L.tc_env_set_camera.argtypes = [C.c_void_p, C.POINTER(CameraParamsC)]
     L.tc_env_set_camera_per_env.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tc_env_set_camera_bank.argtypes = [C.c_void_p, C.POINTER(CameraBankC)]
     L.tc_env_set_car.argtypes = [C.c_void_p, C.POINTER(CarParamsC)]
     L.tc_env_set_car_per_env.argtypes = [C.c_void_p, C.c_void_p]
     L.tc_env_set_car_randomization.argtypes = [C.c_void_p, _dp, _dp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]

@@ -41,6 +41,15 @@ TC_HD double tc_car_draw(uint64_t z, int j, double lo, double hi) {
   return lo + (hi - lo) * u;
 }
 
+// Per-episode camera from a bank of `count` (> 0) cameras (tc_env_set_camera_bank).  Episode `episode` of env `env` (global
+// index, as for the cars) takes the camera whose index is the high 32 bits of output (env << 32 | episode) of the sub-stream
+// s' = SplitMix64(seed)[0x63616D] ("cam": apart from the car and spawn streams of the same seed), scaled by count as in
+// tc_spawn_index.  count == 1 gives 0.
+TC_HD uint32_t tc_camera_index(uint64_t seed, uint32_t env, uint32_t episode, uint32_t count) {
+  const uint64_t z = tc_splitmix64_at(tc_splitmix64_at(seed, 0x63616Dull), ((uint64_t)env << 32) | episode);
+  return (uint32_t)(((z >> 32) * (uint64_t)count) >> 32);
+}
+
 // One blob of NoiseObservationWrapper (wrapper/observation.py:18-20): centre (x, y) inside the frame, radius in
 // [1, max_radius), mode 1 = "copy in" with probability 0.3 (else erase), src = the plane copied from.  Blob k of
 // (env, step) takes two outputs of the sub-stream SplitMix64(seed)[env << 32 | step].  The reference draws these

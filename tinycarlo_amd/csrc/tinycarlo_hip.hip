@@ -260,7 +260,8 @@ struct LiveLds {
   int cursor0;      // its value in the caller's buffer (stored back only when it changed)
   int trunc, status, terminated;
   int ep_len;  // running episode's length (tc_env_set_episodes; touched by the TC_FEAT_EP kernels only)
-  int pad[2];
+  int cam_idx;  // the env's camera of the bank (tc_env_set_camera_bank; touched only while one is installed)
+  int pad;
   int cnt[TC_MAX_TERMS];  // steps_true of the consecutive-step terms
   int ne[TC_MAX_LAYERS];
   double ep_ret;  // running episode's return (likewise)
@@ -289,8 +290,11 @@ struct KArgs {
   LdsLayout lds;
   int N;
   int env0;    // first env of this launch (a step may be issued as several sub-batches)
-  const double* cam_E;  // optional per-env extrinsics [N][12] (NULL: cam.E for every env)
-  const double* cam_K;  // optional per-env intrinsics [N][9]
+  // optional camera rows (NULL: cam.E / cam.K for every env): one per env ([N][12] / [N][9], tc_env_set_camera_per_env: row
+  // = env), or a bank of cameras ([count][12] / [count][9], tc_env_set_camera_bank: row = the index that travels with the
+  // (step, env), see CamBank)
+  const double* cam_E;
+  const double* cam_K;
   int* seg_g;  // [N][seg_cap][5] draw list of the current frame (library owned)
   int* seg_n;  // [N]
   int seg_cap;
@@ -420,6 +424,44 @@ __device__ __forceinline__ void car_respawn(const CarRows& cr, int env, bool wri
       if (writer) row[j] = v;
     }
   if (writer) cr.episode[env] = ep + 1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Camera bank (tc_env_set_camera_bank): KArgs::cam_E / cam_K hold `count` cameras, each env an index into them that every
+// re-spawn re-draws (tc_camera_index, tc_rng.h).  E is consumed where the pose row is formed, K later by the frame stage --
+// in a K-step call possibly after the env has re-spawned again -- so the index in force at a step travels with that
+// (step, env): entry 12 of its pose row (or a register, where the same wavefront draws the frame).  A run-time branch on
+// TC_FI_CAM_BANK in every simulate kernel (no instantiation of its own, as cam_E is); the frame kernels branch on FrameArgs::bank.
+// Set by the library in StepArgs::flags of every launch while a bank is installed: the kernels branch on this bit of a word
+// they hold anyway instead of fetching a pointer of their argument block per step to test it (never taken from the caller).
+#define TC_FI_CAM_BANK 0x80000000u
+struct CamDrawTab {  // library owned, updated in place by tc_env_set_camera_bank (a captured graph sees new settings)
+  unsigned long long seed;
+  unsigned int count, env_offset;
+};
+struct CamBank {
+  int* index;             // [N] the camera each env uses now (caller owned); NULL: no bank (TC_FI_CAM_BANK clear)
+  int* rows;              // [K][N] the index in force at each step of a K-step call, first row of this launch; or NULL
+  int* episode;           // [N] cameras drawn so far (caller owned)
+  const CamDrawTab* tab;
+};
+typedef const __attribute__((address_space(4))) CamDrawTab* CamDrawTabConst;  // never written by a kernel: scalar loads
+// an index as read from memory, kept inside the bank whatever the caller's buffer holds
+__device__ __forceinline__ int cam_clamp(const CamBank& cb, int idx) {
+  const unsigned int last = ((CamDrawTabConst)(unsigned long long)cb.tab)->count - 1u;
+  return (int)((unsigned int)idx < last ? (unsigned int)idx : last);
+}
+// A re-spawn of env `env`: the camera of its next episode.  The writer stores index and counter (as car_respawn does).
+template <bool UNI>
+__device__ __forceinline__ int cam_respawn(const CamBank& cb, int env, bool writer) {
+  const CamDrawTabConst t = (CamDrawTabConst)(unsigned long long)cb.tab;
+  const int ep = UNI ? uni_i(cb.episode[env]) : cb.episode[env];
+  const int idx = (int)tc_camera_index(t->seed, (uint32_t)(t->env_offset + (unsigned int)env), (uint32_t)ep, t->count);
+  if (writer) {
+    cb.index[env] = idx;
+    cb.episode[env] = ep + 1;
+  }
+  return idx;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1152,6 +1194,11 @@ __device__ __forceinline__ void ctrl_in(const KArgs& a, unsigned char* smem, int
   if (tid == 51) lv->cte = a.b.cte[env];
   if (tid == 52) lv->he = a.b.heading_error[env];
 }
+// The env's camera of the bank: caller's buffer -> LiveLds, likewise before live_in (only while a bank is installed).
+__device__ __forceinline__ void cam_in(const KArgs& a, const CamBank& cb, unsigned char* smem, int env, const int tid = threadIdx.x) {
+  LiveLds* lv = (LiveLds*)(smem + a.lds.off_live);
+  if (tid == 53) lv->cam_idx = cam_clamp(cb, cb.index[env]);
+}
 __device__ __forceinline__ void ep_out(const KArgs& a, const EpArgs& ep, unsigned char* smem, int env, const int tid = threadIdx.x) {
   const LiveLds* lv = (const LiveLds*)(smem + a.lds.off_live);
   if (tid == 50) {
@@ -1182,7 +1229,8 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
                                 const void* car_control, int cdtype,
                                 const int* maneuver, const int* spawn_nodes, const unsigned char* mask,
                                 unsigned int flags, const RollStep& roll, const int tid, MapCache<K>& mc, FramePose& fp,
-                                const CarRows& cr = CarRows(), const EpArgs& ep = EpArgs(), const CtrlArgs& ct = CtrlArgs()) {
+                                int& cam_row, const CarRows& cr = CarRows(), const EpArgs& ep = EpArgs(),
+                                const CtrlArgs& ct = CtrlArgs(), const CamBank& cb = CamBank()) {
   constexpr bool PER = (FEAT & TC_FEAT_CAR) != 0, EP = (FEAT & TC_FEAT_EP) != 0, CTRL = (FEAT & TC_FEAT_CTRL) != 0;
 
   TSTAMP(0);
@@ -1218,6 +1266,9 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
   int cursor = uni_i(lv->cursor);
   int my_cnt = tid < TC_MAX_TERMS ? lv->cnt[tid] : 0;  // lane t: steps_true of term slot t
   int ep_len = EP ? uni_i(lv->ep_len) : 0;
+  // which camera row this step's frame uses: the env's own (shared camera: unused), or its index into the bank
+  const bool bank = (flags & TC_FI_CAM_BANK) != 0;
+  cam_row = bank ? uni_i(lv->cam_idx) : env;
 
   int status = 0, trunc = 0;
   PathInfo pinfo;
@@ -1228,6 +1279,7 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
   double ctrl_steer = 0.0;  // CTRL: this step's command before noise (0 when no action is applied)
   if (mode == MODE_RESET) {
     if (PER) car_respawn<true>(cr, env, true);
+    if (bank) cam_row = cam_respawn<true>(cb, env, tid == 0);
     d_reset(m, PER ? car_of<true>(a.car, crow) : a.car, s, checked_spawn(m, spawn_nodes[env], status));
     fresh = true;
     have_trig = true;
@@ -1242,6 +1294,7 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
         node = b.spawn_queue[(size_t)env * b.spawn_queue_len + ((unsigned)cur % (unsigned)b.spawn_queue_len)];
       }
       if (PER) car_respawn<true>(cr, env, true);
+      if (bank) cam_row = cam_respawn<true>(cb, env, tid == 0);
       d_reset(m, PER ? car_of<true>(a.car, crow) : a.car, s, checked_spawn(m, node, status));
       fresh = true;
       have_trig = true;
@@ -1331,6 +1384,10 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
       if (roll.lp_len) roll.lp_len[roll.row0 + env] = s.lp_len;
       if (CTRL && mode == MODE_STEP) ctrl_store(ct, env, roll.row0 + env, ctrl_steer);
       if (EP) lv->ep_len = ep_len;
+      if (bank) {
+        if (fresh) lv->cam_idx = cam_row;
+        if (cb.rows && mode == MODE_STEP) cb.rows[roll.row0 + env] = cam_row;
+      }
       if (!late) {
         lv->reward = reward;
         lv->terminated = terminated;
@@ -1524,11 +1581,13 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
 // workgroup that gave up waiting leaves in place of its draw-list length
 #define TC_POSE_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define TC_FRAME_SKIPPED (-2)
-__device__ __forceinline__ void cam_pose12(const KArgs& a, int env, const FramePose& fp, double* pose) {
-  double Ec[12];  // this env's camera (camera.py:23-24,48-50): shared, or its own after tc_env_set_camera_per_env
+__device__ __forceinline__ void cam_pose12(const KArgs& a, int cam_row, const FramePose& fp, double* pose) {
+  // this env's camera (camera.py:23-24,48-50): shared, or row cam_row of the camera rows (its own after
+  // tc_env_set_camera_per_env, its episode's of the bank after tc_env_set_camera_bank)
+  double Ec[12];
   if (a.cam_E) {
 #pragma unroll
-    for (int i = 0; i < 12; i++) Ec[i] = a.cam_E[(size_t)env * 12 + i];
+    for (int i = 0; i < 12; i++) Ec[i] = a.cam_E[(size_t)cam_row * 12 + i];
   } else {
     const __attribute__((address_space(4))) double* ee = (const __attribute__((address_space(4))) double*)(unsigned long long)a.cam.E;
 #pragma unroll
@@ -1599,7 +1658,7 @@ __device__ __forceinline__ bool cam_cull(const KArgs& a, const double* pose) {
 }
 
 template <int K>
-__device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, int env, const double* pose_in, MapCache<K>& mc,
+__device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, int env, int cam_row, const double* pose_in, MapCache<K>& mc,
                                          const bool mc_loaded, const int tid, const int seg_row, int& nseg_out,
                                          unsigned int& used_out, const bool store_n = true) {
   unsigned int my_layers = 0;  // layers this lane put a segment into the draw list for
@@ -1633,7 +1692,7 @@ __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, in
   double Kc[9];
   if (a.cam_K) {  // (a branch, not a select of pointers: the shared camera's K then comes in scalar loads)
 #pragma unroll
-    for (int i = 0; i < 9; i++) Kc[i] = a.cam_K[(size_t)env * 9 + i];
+    for (int i = 0; i < 9; i++) Kc[i] = a.cam_K[(size_t)cam_row * 9 + i];  // (the row that came with the pose, not the env's latest)
   } else {
     const __attribute__((address_space(4))) double* kk = (const __attribute__((address_space(4))) double*)(unsigned long long)cam.K;
 #pragma unroll
@@ -2705,6 +2764,7 @@ struct StepArgs {
   CarRows cr;            // per-env cars: read by the TC_FEAT_CAR kernels only (last, so every other member keeps its offset)
   EpArgs ep;             // episodes: read by the TC_FEAT_EP kernels only (behind it, for the same reason)
   CtrlArgs ct;           // built-in controller: read by the TC_FEAT_CTRL kernels only (likewise)
+  CamBank cb;            // camera bank: index NULL = none (likewise behind the others)
 };
 
 // The launch arguments, read through a pointer the optimiser cannot see through.  Inside the step loop of tc_step_multi
@@ -2752,6 +2812,7 @@ __device__ __forceinline__ void env_kernel_body() {
   if (s0.mode == MODE_RESET && s0.mask && !s0.mask[env]) return;  // whole workgroup skips
   if (EP) ep_in(s0.a, s0.ep, smem, env);
   if (CTRL) ctrl_in(s0.a, smem, env);
+  if (s0.flags & TC_FI_CAM_BANK) cam_in(s0.a, s0.cb, smem, env);
   live_in(s0.a, smem, env, s0.mode, s0.flags);
   const int nsteps = s0.ma.nsteps;
   long long t_prev = 0;
@@ -2780,15 +2841,18 @@ __device__ __forceinline__ void env_kernel_body() {
     MapCache<K> mc = {};  // (initialised: a path that leaves it unset would otherwise make it a loop-carried value -- 30
                           // registers per lane held across the whole step body, raster stage included)
     FramePose fp;
+    int cam_row;
     sim_body<K, FEAT>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
-                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr, sa.ep, sa.ct);
+                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, cam_row, sa.cr, sa.ep,
+                         sa.ct, sa.cb);
     if (sa.ma.pose_rows) {
       double pose[12];
-      cam_pose12(sa.a, env, fp, pose);
+      cam_pose12(sa.a, cam_row, fp, pose);
       if (tid == 0) {
         double2* o = (double2*)(step_args().ma.pose_rows + (row0 + env) * TC_POSE_ROW);
 #pragma unroll
         for (int i = 0; i < 6; i++) o[i] = make_double2(pose[2 * i], pose[2 * i + 1]);
+        if (sa.flags & TC_FI_CAM_BANK) ((long long*)o)[12] = cam_row;  // (the bank index of this (step, env): see CamBank)
       }
     }
     if (CAM && sa.ma.cam_here) {
@@ -2796,8 +2860,8 @@ __device__ __forceinline__ void env_kernel_body() {
         int nseg;
         unsigned int used;
         double pose[12];
-        cam_pose12(sa.a, env, fp, pose);
-        cam_body<K>(sa.a, smem, env, pose, mc, sa.mode != MODE_RENDER, tid, seg_row, nseg, used);  // (tc_render skips phase B's fetch)
+        cam_pose12(sa.a, cam_row, fp, pose);
+        cam_body<K>(sa.a, smem, env, cam_row, pose, mc, sa.mode != MODE_RENDER, tid, seg_row, nseg, used);  // (tc_render skips phase B's fetch)
       }
       else if (tid == 0)
         step_args().a.seg_n[(size_t)seg_row * sa.a.N + env] = 0;
@@ -2933,6 +2997,10 @@ __device__ __forceinline__ void envg_kernel_body() {
     g_ep_len[grp] = s0.ep.length[env];
     if (sub == 0) g_ep_ret[grp] = s0.ep.ret[env];
   }
+  // the env's camera of the bank (tc_env_set_camera_bank), in LDS for the same reason; every lane of the group writes the
+  // same value, and only lanes of this wavefront read it (LDS operations of a wavefront complete in order)
+  __shared__ int g_cam_idx[TC_ENVG_NT / TC_EL];
+  if (s0.flags & TC_FI_CAM_BANK) g_cam_idx[grp] = cam_clamp(s0.cb, s0.cb.index[env]);
   double cte = 0, he = 0, reward = 0;
   if (CTRL) {  // what the env reported after the step before this launch: the controller's input at the first step
     cte = s0.a.b.cte[env];
@@ -2992,6 +3060,7 @@ __device__ __forceinline__ void envg_kernel_body() {
         node = b.spawn_queue[(size_t)env * b.spawn_queue_len + ((unsigned)cur % (unsigned)b.spawn_queue_len)];
       }
       if (PER) car_respawn<false>(sa.cr, env, live && sub == 0);  // (one lane of the group writes the row and counter)
+      if (flags & TC_FI_CAM_BANK) g_cam_idx[grp] = cam_respawn<false>(sa.cb, env, live && sub == 0);
       d_reset(m, PER ? car_of<false>(a.car, sa.cr.rows + (size_t)env * TC_CAR_NP) : a.car, s, checked_spawn(m, node, status));
       fresh = true;
       have_trig = true;
@@ -3025,6 +3094,9 @@ __device__ __forceinline__ void envg_kernel_body() {
     // ---- this step's pose row, as early as the pose is final (nothing below moves the car): in a streamed call the frame
     // workgroups of this (step, env) are waiting for it, and what follows -- lanepath tracking, distances, reward, rollout
     // rows -- is most of the step
+    const bool bank = (flags & TC_FI_CAM_BANK) != 0;
+    const int cam_row = bank ? g_cam_idx[grp] : (live ? env : 0);  // camera row of this step's frame (see CamBank)
+    if (bank && sa.cb.rows && live && sub == 0) sa.cb.rows[row0 + env] = cam_row;
     if (sa.ma.pose_rows) {
       // car.py:159-165 takes cos(-theta), sin(-theta): tc_cos is exactly even and tc_sin exactly odd, so the values of
       // the front-axle update are reused bit for bit (as in sim_body)
@@ -3034,7 +3106,7 @@ __device__ __forceinline__ void envg_kernel_body() {
       fp.cth = have_trig ? s.cth : tc_cos(-s.theta);
       fp.sth = have_trig ? -s.sth : tc_sin(-s.theta);
       double pose[12];
-      cam_pose12(sa.a, live ? env : 0, fp, pose);
+      cam_pose12(sa.a, cam_row, fp, pose);
       if (live && sub == 0) {
         if (sa.ma.resident) {
           // streamed call: the frame workgroup of this (step, env) may already be polling the row.  Each entry is one
@@ -3045,10 +3117,13 @@ __device__ __forceinline__ void envg_kernel_body() {
 #pragma unroll
           for (int i = 0; i < 12; i++)
             __hip_atomic_store(o + i, (unsigned long long)__double_as_longlong(pose[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          // with a bank, a thirteenth entry of the same kind: the index this (step, env) was posed with (never all ones)
+          if (bank) __hip_atomic_store(o + 12, (unsigned long long)(unsigned int)cam_row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
           double2* o = (double2*)(sa.ma.pose_rows + (row0 + env) * TC_POSE_ROW);
 #pragma unroll
           for (int i = 0; i < 6; i++) o[i] = make_double2(pose[2 * i], pose[2 * i + 1]);
+          if (bank) ((long long*)o)[12] = cam_row;
         }
       }
     }
@@ -3289,6 +3364,9 @@ struct FrameArgs {
   // Streamed call (launch()): this kernel runs BESIDE the simulate launch that produces its pose rows.
   int gate;                 // 0: the rows are complete (written by an earlier launch); 1: wait for the row (bounded: gate_ticks);
                             // 2: tc_frame_recover_kernel, behind the simulate launch: draws what a gate-1 workgroup gave up on
+  int bank;                 // cameras in a.cam_E / a.cam_K when they are a bank (tc_env_set_camera_bank): entry 12 of a pose row
+                            // then holds the frame's index into it; 0: no bank (the camera row is the env).  (Beside `gate`:
+                            // the two are read together)
   int recover_rows;         // gate 2: rows of the call
   unsigned int* abort_word; // gate 1: set by the first workgroup whose wait ran out; the others then give up at once
   unsigned int* resident;   // gate 2: workgroup 0 clears this and abort_word for the next call
@@ -3311,16 +3389,21 @@ __device__ __forceinline__ const FrameArgs& frame_args() {
 // wait ends -- but nothing relies on that: a wait that outlasts gate_ticks marks the frame skipped, tells the others and
 // returns false, and tc_frame_recover_kernel, behind the simulate launch, draws the frame.  `wait` false: the row is known
 // to be there (gate 2, or read before by this workgroup) -- one read.
-__device__ __forceinline__ bool frame_pose(const size_t slot0, const int env, const int row, const bool wait, double* pose) {
+// cam_row: the frame's row of the camera rows -- the env, or with a bank the index the simulate stage left in entry 12,
+// polled and validated like the other twelve (kept inside the bank whatever the memory holds).
+__device__ __forceinline__ bool frame_pose(const size_t slot0, const int env, const int row, const bool wait, double* pose, int& cam_row) {
   const FrameArgs& fa = frame_args();
   const int tid = threadIdx.x;
-  if (fa.gate) {
+  const int gate = fa.gate, bank = fa.bank;
+  const int np = bank ? 13 : 12;
+  cam_row = env;
+  if (gate) {
     unsigned long long* prow = (unsigned long long*)(fa.pose_rows + (slot0 + env) * TC_POSE_ROW);
     unsigned long long v = 0;
     bool give_up = wait && fa.gate == 1 && fa.gate_test > 0 && (row + env) % fa.gate_test == 0;
     long long t0 = 0;
     while (!give_up) {
-      v = tid < 12 ? __hip_atomic_load(prow + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+      v = tid < np ? __hip_atomic_load(prow + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
       if (__ballot(v == TC_POSE_EMPTY) == 0 || fa.gate == 2 || !wait) break;
       const long long now = wall_clock64();
       if (t0 == 0) t0 = now;
@@ -3343,6 +3426,10 @@ __device__ __forceinline__ bool frame_pose(const size_t slot0, const int env, co
                                    ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)vhi, i) << 32);
       pose[i] = __longlong_as_double((long long)q);
     }
+    if (bank) {
+      const unsigned int idx = (unsigned int)__builtin_amdgcn_readlane((int)vlo, 12);
+      cam_row = (int)(idx < (unsigned int)bank ? idx : (unsigned int)bank - 1u);
+    }
   } else {
     // written by an earlier launch, complete and visible before this kernel started: one address for the whole wavefront,
     // read through the scalar cache
@@ -3350,6 +3437,10 @@ __device__ __forceinline__ bool frame_pose(const size_t slot0, const int env, co
         (const __attribute__((address_space(4))) double*)(unsigned long long)(fa.pose_rows + (slot0 + env) * TC_POSE_ROW);
 #pragma unroll
     for (int i = 0; i < 12; i++) pose[i] = pr[i];
+    if (bank) {
+      const unsigned int idx = ((const __attribute__((address_space(4))) unsigned int*)(unsigned long long)pr)[24];
+      cam_row = (int)(idx < (unsigned int)bank ? idx : (unsigned int)bank - 1u);
+    }
   }
   return true;
 }
@@ -3366,12 +3457,13 @@ __device__ __forceinline__ void frame_one(unsigned char* smem, const int env, co
     const int row = fa.r.seg_row0 + rowy;
     const size_t slot0 = (size_t)row * fa.a.N;
     double pose[12];
-    if (!frame_pose(slot0, env, row, true, pose)) return;
+    int cam_row;
+    if (!frame_pose(slot0, env, row, true, pose, cam_row)) return;
     MapCache<K> mc;
     TSTAMP_CLEAR();
     TSTAMP(3);
     TSTAMP_REAL(30);
-    cam_body<K>(fa.a, smem, env, pose, mc, false, tid, row, nseg, used, false);
+    cam_body<K>(fa.a, smem, env, cam_row, pose, mc, false, tid, row, nseg, used, false);
   }
   const FrameArgs& fr = frame_args();
   const size_t slot0 = (size_t)(fr.r.seg_row0 + rowy) * fr.a.N;
@@ -3395,7 +3487,7 @@ __device__ __forceinline__ void frame_one(unsigned char* smem, const int env, co
     const size_t slot = (size_t)(fe.r.seg_row0 + rowy) * fe.a.N + env;
     if (tid == 0) fe.a.seg_n[slot] = nseg;  // workload statistics, the next dispatch's order, "drawn" for the recover pass
     // a streamed call's row goes back to "not written yet" for the next call (which starts behind this kernel)
-    if (fe.gate && tid < 12)
+    if (fe.gate && tid < (fe.bank ? 13 : 12))
       __hip_atomic_store((unsigned long long*)(fe.pose_rows + slot * TC_POSE_ROW) + tid, TC_POSE_EMPTY, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -3457,6 +3549,7 @@ __device__ __forceinline__ void step_kernel_body() {
   if (s0.mode == MODE_RESET && s0.mask && !s0.mask[env]) return;  // whole workgroup skips
   if (EP) ep_in(s0.a, s0.ep, smem, env);
   if (CTRL) ctrl_in(s0.a, smem, env);
+  if (s0.flags & TC_FI_CAM_BANK) cam_in(s0.a, s0.cb, smem, env);
   live_in(s0.a, smem, env, s0.mode, s0.flags);
   const int nsteps = s0.ma.nsteps;
   long long t_prev = 0;
@@ -3473,14 +3566,16 @@ __device__ __forceinline__ void step_kernel_body() {
     MapCache<K> mc = {};  // (initialised: a path that leaves it unset would otherwise make it a loop-carried value -- 30
                           // registers per lane held across the whole step body, raster stage included)
     FramePose fp;
+    int cam_row;  // (the bank index stays in a register: the same wavefront draws the frame)
     sim_body<K, FEAT>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
-                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, sa.cr, sa.ep, sa.ct);
+                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, cam_row, sa.cr, sa.ep,
+                         sa.ct, sa.cb);
     if (wants_frame(sa)) {
       int nseg;
       unsigned int used;
       double pose[12];
-      cam_pose12(sa.a, env, fp, pose);
-      cam_body<K>(sa.a, smem, env, pose, mc, sa.mode != MODE_RENDER, tid, 0, nseg, used, false);  // (tc_render skips phase B's fetch)
+      cam_pose12(sa.a, cam_row, fp, pose);
+      cam_body<K>(sa.a, smem, env, cam_row, pose, mc, sa.mode != MODE_RENDER, tid, 0, nseg, used, false);  // (tc_render skips phase B's fetch)
       if (nseg > sa.a.seg_lds_cap)
         __syncthreads();  // draw-list entries that went through global memory are visible to this wavefront (vmcnt(0) + barrier)
       else
@@ -3986,6 +4081,11 @@ struct tc_env {
   DevPtr<CtrlTab> ctrl_tab;  // device copy of the gains (updated in place), or NULL
   CtrlTab ctrl_host{};   // what ctrl_tab holds
   int ctrl_rows = 0;     // rows of ct.noise / ct.rows
+  CamBank cb{};          // camera bank (tc_env_set_camera_bank); index NULL = off.  k.cam_E / k.cam_K then point to the bank
+  DevPtr<CamDrawTab> cam_tab;  // device copy of the draw settings (updated in place), or NULL
+  CamDrawTab cam_host{};       // what cam_tab holds
+  int cam_count = 0;     // cameras in the bank (0 = off)
+  int cam_rows = 0;      // rows of cb.rows
   bool bound = false;
   int64_t obs_bytes = 0;
   int r_off_tab = 0, r_off_bits = 0, r_lds = 0;
@@ -4818,7 +4918,48 @@ extern "C" int tc_env_set_camera_per_env(tc_env* e, const double* E, const doubl
   if (!e || ((E == nullptr) != (K == nullptr))) return TC_E_INVALID;
   e->k.cam_E = E;
   e->k.cam_K = K;
+  memset(&e->cb, 0, sizeof(e->cb));  // (static rows and a bank exclude each other: installing one removes the other)
+  e->cam_count = e->cam_rows = 0;
   cover_cull(e);  // (per-env cameras: the cull is off, its cover is the shared camera's)
+  return TC_OK;
+}
+
+extern "C" int tc_env_set_camera_bank(tc_env* e, const tc_camera_bank* b) {
+  if (!e) return TC_E_INVALID;
+  if (!b) {  // bank off: back to the shared camera (the table stays for a graph captured earlier)
+    if (e->cb.index) e->k.cam_E = e->k.cam_K = nullptr;
+    memset(&e->cb, 0, sizeof(e->cb));
+    e->cam_count = e->cam_rows = 0;
+    cover_cull(e);
+    return TC_OK;
+  }
+  if (!b->E || !b->K || !b->index || !b->episode || b->count < 1) {
+    set_err("tc_env_set_camera_bank: E, K, index and episode are required, and count must be at least 1");
+    return TC_E_INVALID;
+  }
+  if (b->n_rows < 0 || (b->index_rows && b->n_rows < 1)) {
+    set_err("tc_env_set_camera_bank: index_rows need n_rows >= 1 (and n_rows must not be negative)");
+    return TC_E_INVALID;
+  }
+  const CamDrawTab t = {b->seed, (unsigned int)b->count, b->env_offset};
+  const bool fresh_tab = !e->cam_tab;
+  if (fresh_tab) HIP_TRY(e->cam_tab.alloc(1));
+  if (fresh_tab || memcmp(&t, &e->cam_host, sizeof(t)) != 0) {
+    // (in place: a graph captured earlier keeps reading this table; the copy waits for launches that may still read it.
+    // A call that only changes pointers -- kernel arguments -- has nothing to wait for.)
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(e->cam_tab, &t, sizeof(t), hipMemcpyHostToDevice));
+    e->cam_host = t;
+  }
+  e->k.cam_E = b->E;
+  e->k.cam_K = b->K;
+  e->cb.index = b->index;
+  e->cb.episode = b->episode;
+  e->cb.tab = e->cam_tab;
+  e->cb.rows = b->index_rows;
+  e->cam_count = b->count;
+  e->cam_rows = b->index_rows ? b->n_rows : 0;
+  cover_cull(e);  // (a bank: the cull is off, as with per-env cameras)
   return TC_OK;
 }
 
@@ -5262,10 +5403,12 @@ static StepArgs step_args_at(const tc_env* e, int mode, const void* cc, int cdty
   sa.ct = e->ct;  // (the per-step rows belong to K-step calls only, like the episode rows: tc_step reads and writes none)
   sa.ct.noise = ep_rows && e->ct.noise ? e->ct.noise + r0 : nullptr;
   sa.ct.rows = ep_rows && e->ct.rows ? e->ct.rows + r0 : nullptr;
+  sa.cb = e->cb;  // (the index rows likewise)
+  sa.cb.rows = ep_rows && e->cb.index && e->cb.rows ? e->cb.rows + r0 : nullptr;
   if (roll) sa.ma.roll = rollout_at(*roll, r0, (size_t)e->obs_bytes, (size_t)e->k.m.C);
   sa.mode = mode;
   sa.cdtype = cdtype;
-  sa.flags = flags;
+  sa.flags = (flags & ~TC_FI_CAM_BANK) | (e->cb.index ? TC_FI_CAM_BANK : 0u);
   sa.car_control = cc ? (const char*)cc + r0 * 2 * (cdtype == TC_F32 ? 4 : 8) : nullptr;  // (NULL: a controller acts)
   sa.maneuver = man + r0;
   sa.spawn_nodes = spawn;
@@ -5294,6 +5437,7 @@ static FrameArgs frame_args_of(const tc_env* e, uint32_t flags, const RArgs& r, 
     fa.gate_ticks = e->tune.gate_ticks;
     fa.gate_test = e->tune.gate_test;
   }
+  fa.bank = e->cb.index ? e->cam_count : 0;
   return fa;
 }
 
@@ -5618,6 +5762,10 @@ extern "C" int tc_step_multi(tc_env* e, const void* car_control, int32_t control
   }
   if (e->ct.tab && (e->ct.noise || e->ct.rows) && n_steps > e->ctrl_rows) {
     set_err("tc_step_multi: more steps than the controller's rows hold (tc_env_set_controller)");
+    return TC_E_INVALID;
+  }
+  if (e->cb.index && e->cb.rows && n_steps > e->cam_rows) {
+    set_err("tc_step_multi: more steps than the camera index rows hold (tc_env_set_camera_bank)");
     return TC_E_INVALID;
   }
   if ((e->ep.len_rows || e->ep.ret_rows) && n_steps > e->ep_rows) {

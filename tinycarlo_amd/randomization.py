@@ -1,4 +1,4 @@
-"""Per-env car constants and their per-episode draw, restated on the host.
+"""Per-env car constants and per-episode cameras: the device's draws restated on the host.
 
 The device draws the row of an env's next episode at every re-spawn (``tc_env_set_car_randomization``,
 ``csrc/tc_rng.h``: ``tc_car_stream`` / ``tc_car_draw``).  ``draw_car_params`` is the same arithmetic in numpy uint64 /
@@ -6,10 +6,15 @@ float64, so the constants of any past episode can be recomputed on the host -- a
 
 The other two helpers turn the user-facing arguments of ``TinyCarloVecEnv.set_env_cars`` / ``randomize_cars`` into
 the library's [N, 8] rows and (lo, hi, mask) tables, with the validation both need (no GPU involved).
+
+Cameras (``TinyCarloVecEnv.randomize_cameras``, ``tc_env_set_camera_bank``): ``camera_bank`` builds the bank -- every
+combination of the candidate values, each camera computed by ``Camera`` exactly as ``update_params`` does -- and
+``draw_camera_index`` is ``tc_camera_index`` of ``csrc/tc_rng.h``: which camera of the bank an env's episode uses.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence, Tuple
+import itertools
+from typing import Any, Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -17,6 +22,8 @@ CAR_COLUMNS = ("wheelbase", "track_width", "max_velocity", "max_steering_angle",
                "max_deceleration", "steering_shift")
 CAR_NP = len(CAR_COLUMNS)
 CAR_STREAM = 0x636172  # "car": the sub-stream of the seed the draws come from (apart from the device spawn stream)
+CAM_STREAM = 0x63616D  # "cam": likewise for the camera index of an episode
+CAMERA_COLUMNS = ("pitch", "roll", "yaw", "fov", "x", "y", "z")  # columns of a camera bank's parameter table
 _GOLDEN, _M1, _M2 = np.uint64(0x9E3779B97F4A7C15), np.uint64(0xBF58476D1CE4E5B9), np.uint64(0x94D049BB133111EB)
 
 
@@ -114,3 +121,79 @@ def car_ranges(p, ranges: Optional[Dict[str, Sequence[float]]]) -> Tuple[np.ndar
         mask |= 1 << j
     return lo, hi, mask
 
+
+
+# ---------------------------------------------------------------------------------------------- camera bank
+def draw_camera_index(seed: int, env_index, episode, count: int):
+    """The index into a bank of `count` cameras that env `env_index` (global index: env_offset + index in the batch) draws
+    for episode `episode` (its value of the camera episode counter at the re-spawn): tc_rng.h's tc_camera_index.
+    env_index / episode may be arrays (broadcast; an int32 counter that wrapped gives the draw of its unsigned value);
+    returns int64 of the broadcast shape."""
+    count = int(count)
+    if not 1 <= count <= 2 ** 31:
+        raise ValueError(f"count must be in [1, 2^31], got {count}")
+    env = np.asarray(env_index, dtype=np.int64).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    ep = np.asarray(episode, dtype=np.int64).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    env, ep = np.broadcast_arrays(env, ep)
+    s2 = splitmix64_at(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), np.uint64(CAM_STREAM))
+    z = splitmix64_at(s2, (env << np.uint64(32)) | ep)
+    return (((z >> np.uint64(32)) * np.uint64(count)) >> np.uint64(32)).astype(np.int64)
+
+
+def _values(name: str, v, width: int) -> np.ndarray:
+    """candidate values of one camera component as float64 [n, width] (width 1: scalars)"""
+    a = np.asarray(list(v) if not hasattr(v, "shape") else v, dtype=np.float64)
+    if a.size == 0:
+        raise ValueError(f"{name}: the list of candidate values is empty")
+    a = a.reshape(-1, 1) if (width == 1 and a.ndim == 1) else a
+    if a.ndim != 2 or a.shape[1] != width:
+        raise ValueError(f"{name}: expected a list of " + ("numbers" if width == 1 else f"{width}-vectors") + f", got shape {a.shape}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{name}: values must be finite")
+    return a
+
+
+def bank_camera_config(camera_cfg: Dict[str, Any], row) -> Dict[str, Any]:
+    """the camera config of one row (CAMERA_COLUMNS) of a bank's parameter table"""
+    r = [float(x) for x in np.asarray(row, dtype=np.float64).reshape(len(CAMERA_COLUMNS))]
+    cfg = dict(camera_cfg)
+    cfg.update(orientation=r[0:3], fov=r[3], position=r[4:7])
+    return cfg
+
+
+def camera_bank(camera_cfg: Dict[str, Any], orientation=None, fov=None, position=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(E [M, 12], K [M, 9], params [M, 7]) of the bank made of every combination of the candidate values.
+
+    orientation: a list of (pitch, roll, yaw) triples in degrees, or a dict {"pitch": [...], "roll": [...], "yaw": [...]}
+    of per-angle candidates (a missing angle keeps the config's value); fov: a list of degrees; position: a list of
+    (x, y, z) triples in metres.  None keeps the config's value.  Rows are ordered orientation-major (pitch, roll, yaw),
+    then fov, then position; row m is ``Camera(bank_camera_config(camera_cfg, params[m])).E / .K`` bit for bit.
+    Raises ValueError on an empty list, a non-finite value or an unknown angle name."""
+    from .camera import Camera
+    base = Camera(camera_cfg)
+    if isinstance(orientation, dict):
+        names = ("pitch", "roll", "yaw")
+        for k in orientation:
+            if k not in names:
+                raise ValueError(f"unknown orientation component {k!r}; choose from {names}")
+        comps = [_values(f"orientation[{n!r}]", orientation[n], 1)[:, 0] if orientation.get(n) is not None
+                 else np.array([float(base.orientation[i])]) for i, n in enumerate(names)]
+        ori = np.array(list(itertools.product(*comps)), dtype=np.float64).reshape(-1, 3)
+    elif orientation is None:
+        ori = np.array([base.orientation], dtype=np.float64)
+    else:
+        ori = _values("orientation", orientation, 3)
+    fv = np.array([[float(base.fov)]]) if fov is None else _values("fov", fov, 1)
+    pos = np.array([base.position], dtype=np.float64) if position is None else _values("position", position, 3)
+    if np.any(fv <= 0) or np.any(fv >= 180):
+        raise ValueError("fov: values must be in (0, 180) degrees")
+    M = ori.shape[0] * fv.shape[0] * pos.shape[0]
+    if M > 2 ** 31:
+        raise ValueError(f"a bank of {M} cameras is too large")
+    params = np.empty((M, len(CAMERA_COLUMNS)), dtype=np.float64)
+    E, K = np.empty((M, 12), dtype=np.float64), np.empty((M, 9), dtype=np.float64)
+    for m, (o, f, p) in enumerate(itertools.product(ori, fv[:, 0], pos)):
+        params[m, 0:3], params[m, 3], params[m, 4:7] = o, f, p
+        c = Camera(bank_camera_config(camera_cfg, params[m]))
+        E[m], K[m] = c.E.reshape(-1), c.K.reshape(-1)
+    return E, K, params

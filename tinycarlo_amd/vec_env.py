@@ -249,6 +249,10 @@ class TinyCarloVecEnv(gym.Env):
         self._ctrl: Optional[Dict[str, float]] = None
         self._ctrl_rows: Tuple[int, int, int] = (0, 0, 0)      # data pointers of the noise / steer rows installed last, rows
         self.steer_last: Optional[torch.Tensor] = None         # [N] f64: the controller's command of the last step
+        # per-episode cameras (randomize_cameras): the bank's device tensors, settings and live index / episode, or None
+        self._cam_bank: Optional[Dict[str, Any]] = None
+        self._cam_rows: Tuple[int, int] = (0, 0)               # data pointer and rows of the index rows installed last
+        self._env_cams: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # static per-env E / K (set_env_cameras)
         self._setup_device()
         self._rngs: List[Optional[np.random.Generator]] = [None] * self.num_envs
         self._was_reset = False
@@ -335,7 +339,8 @@ class TinyCarloVecEnv(gym.Env):
 
         orientation: [N,3] degrees (pitch, roll, yaw), fov: [N] degrees, position: [N,3] metres; any of them may
         be None (keep the shared camera's value).  ``set_env_cameras()`` with no argument returns to the single
-        shared camera.  E and K are computed per env on the host with the same code as ``Camera.update_params``."""
+        shared camera.  E and K are computed per env on the host with the same code as ``Camera.update_params``.
+        Static rows and the per-episode bank of ``randomize_cameras`` exclude each other: this removes a bank."""
         if orientation is None and fov is None and position is None:
             self._push_env_cameras(None, None)
             return
@@ -357,6 +362,7 @@ class TinyCarloVecEnv(gym.Env):
         self._push_env_cameras(E, K)
 
     def _push_env_cameras(self, E, K) -> None:
+        self._cam_bank, self._cam_rows = None, (0, 0)  # (tc_env_set_camera_per_env removes a bank, whatever its arguments)
         if E is None:
             self._env_cams = None
             nat.check(nat.lib().tc_env_set_camera_per_env(self._h, None, None), "tc_env_set_camera_per_env")
@@ -365,6 +371,85 @@ class TinyCarloVecEnv(gym.Env):
         Kt = torch.as_tensor(K, dtype=torch.float64).to(self.device).contiguous()
         self._env_cams = (Et, Kt)  # keep the device copies alive: the library reads them on every launch
         nat.check(nat.lib().tc_env_set_camera_per_env(self._h, Et.data_ptr(), Kt.data_ptr()), "tc_env_set_camera_per_env")
+
+    # ------------------------------------------------------------------ per-episode cameras from a bank
+    CAMERA_ROLLOUT_KEYS = ("camera",)
+
+    def randomize_cameras(self, orientation=None, fov=None, position=None, seed: int = 0, env_offset: int = 0) -> None:
+        """Per-episode cameras drawn on the device (the data collection of examples/train_stanley_il.py:53-57: a new
+        pitch and fov for every episode).  Each argument is a list of candidate values -- orientation: (pitch, roll, yaw)
+        triples in degrees, or a dict ``{"pitch": [...], "roll": [...], "yaw": [...]}`` of per-angle candidates; fov:
+        degrees; position: (x, y, z) triples -- and None keeps the shared camera's value.  The bank holds every combination
+        (``randomization.camera_bank``; E and K computed on the host with the code of ``Camera.update_params``), and every
+        re-spawn of env i (reset, or an autoreset re-spawn inside step / step_multi / drive) draws the index of its next
+        episode's camera: ``randomization.draw_camera_index(seed, env_offset + i, camera_episode[i], M)``.  A frame is
+        always projected with the camera of the episode it belongs to, however late in a K-step call it is drawn.
+        Zeroes the episode counters, so ``reset(seed=...)`` afterwards gives every env its episode-0 camera (until then
+        every env uses camera 0).  ``env_offset``: index of env 0 in a larger population (``distributed.shard_range``).
+        With no candidate list at all: back to the shared camera.  Removes the static rows of ``set_env_cameras``."""
+        from .randomization import camera_bank
+        if orientation is None and fov is None and position is None:
+            self._install_camera_bank(None)
+            return
+        if not 0 <= int(env_offset) < 2 ** 32:
+            raise ValueError("env_offset must be in [0, 2^32)")
+        cfg = dict(self.config["camera"])
+        cfg.update(orientation=list(self.camera.orientation), fov=self.camera.fov, position=list(self.camera.position))
+        E, K, params = camera_bank(cfg, orientation=orientation, fov=fov, position=position)
+        self._install_camera_bank({"E": E, "K": K, "params": params, "seed": int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                   "env_offset": int(env_offset)})
+
+    def _install_camera_bank(self, bank: Optional[Dict[str, Any]], index=None, episode=None) -> None:
+        with torch.cuda.device(self.device):
+            if bank is None:
+                if self._cam_bank is not None:
+                    nat.check(nat.lib().tc_env_set_camera_bank(self._h, None), "tc_env_set_camera_bank")
+                self._cam_bank, self._cam_rows = None, (0, 0)
+                return
+            E = torch.as_tensor(np.asarray(bank["E"], dtype=np.float64)).to(self.device).contiguous()
+            K = torch.as_tensor(np.asarray(bank["K"], dtype=np.float64)).to(self.device).contiguous()
+            M = int(E.shape[0])
+            if M < 1 or tuple(E.shape) != (M, 12) or tuple(K.shape) != (M, 9):
+                raise ValueError(f"camera bank: E must be [M, 12] and K [M, 9], got {tuple(E.shape)} and {tuple(K.shape)}")
+            i32 = dict(dtype=torch.int32, device=self.device)
+            idx = torch.zeros(self.num_envs, **i32) if index is None else self._to_dev("camera index", index, torch.int32, (self.num_envs,)).clone()
+            ep = torch.zeros(self.num_envs, **i32) if episode is None else self._to_dev("camera episode", episode, torch.int32, (self.num_envs,)).clone()
+            if index is not None and (int(idx.min()) < 0 or int(idx.max()) >= M):
+                raise ValueError(f"camera index outside the bank of {M} cameras")
+            self._cam_bank = {"E": E, "K": K, "params": np.array(bank["params"], dtype=np.float64), "seed": int(bank["seed"]),
+                              "env_offset": int(bank["env_offset"]), "index": idx, "episode": ep}
+            self._env_cams = None  # (the library drops the static rows)
+            self._push_camera_bank(0, 0)
+
+    def _push_camera_bank(self, rows_ptr: int, n_rows: int) -> None:
+        b = self._cam_bank
+        c = nat.CameraBankC(b["E"].data_ptr(), b["K"].data_ptr(), int(b["E"].shape[0]), b["env_offset"], b["seed"],
+                            b["index"].data_ptr(), b["episode"].data_ptr(), rows_ptr or None, n_rows if rows_ptr else 0)
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().tc_env_set_camera_bank(self._h, C.byref(c)), "tc_env_set_camera_bank")
+        self._cam_rows = (rows_ptr, n_rows if rows_ptr else 0)
+
+    def _install_camera_rows(self, rollout: Optional[Dict[str, torch.Tensor]], K: int) -> None:
+        """the index rows of the K-step call about to be issued (host-side bookkeeping only: the draw settings do not change)"""
+        t = rollout.get("camera") if rollout else None
+        want = (t.data_ptr(), K) if t is not None else (0, 0)
+        if want != self._cam_rows:
+            self._push_camera_bank(*want)
+
+    @property
+    def camera_index(self) -> Optional[torch.Tensor]:
+        """[N] int32 device tensor, live: the camera of the bank each env uses now (None without randomize_cameras)"""
+        return None if self._cam_bank is None else self._cam_bank["index"]
+
+    @property
+    def camera_episode(self) -> Optional[torch.Tensor]:
+        """[N] int32 device counter of the cameras each env has drawn since randomize_cameras (None without it)"""
+        return None if self._cam_bank is None else self._cam_bank["episode"]
+
+    @property
+    def camera_bank_params(self) -> Optional[np.ndarray]:
+        """[M, 7] float64 host table of the bank: pitch, roll, yaw, fov, x, y, z of camera m (None without a bank)"""
+        return None if self._cam_bank is None else self._cam_bank["params"]
 
     # ------------------------------------------------------------------ car constants: shared, per env, per episode
     def _set_shared_car(self, **values) -> None:
@@ -603,6 +688,8 @@ class TinyCarloVecEnv(gym.Env):
         r = self._check_rollout(rollout, K)
         call = PreparedStepMulti(self, None, maneuver, rollout, r, K, steer_noise)
         self._install_ctrl_rows(steer_noise, rollout, K)
+        if self._cam_bank is not None:
+            self._install_camera_rows(rollout, K)
         return call
 
     def drive_step(self, maneuver: torch.Tensor) -> None:
@@ -837,7 +924,8 @@ class TinyCarloVecEnv(gym.Env):
                 "status": ((K, N), i32), "x": ((K, N), f64), "y": ((K, N), f64), "theta": ((K, N), f64),
                 "velocity": ((K, N), f64), "laneline_distances": ((K, N, Cn), f64), "nearest_edge": ((K, N, Cn), i32),
                 "local_path": ((K, N, 8), i32), "lp_len": ((K, N), i32),
-                "episode_length": ((K, N), i32), "episode_return": ((K, N), f64), "steer": ((K, N), f64)}
+                "episode_length": ((K, N), i32), "episode_return": ((K, N), f64), "steer": ((K, N), f64),
+                "camera": ((K, N), i32)}
 
     def reserve_steps(self, n_steps: int) -> None:
         """Sizes the library's scratch ring for K-step calls that render observations (tc_env_reserve_steps): done
@@ -854,15 +942,18 @@ class TinyCarloVecEnv(gym.Env):
         shapes = self._rollout_shapes(K)
         if keys == "all":  # (the episode rows only while the accounting is on, the controller's while one is installed)
             keys = self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS + (self.EPISODE_ROLLOUT_KEYS if self._episodes is not None else ()) + \
-                (self.CTRL_ROLLOUT_KEYS if self._ctrl is not None else ())
+                (self.CTRL_ROLLOUT_KEYS if self._ctrl is not None else ()) + \
+                (self.CAMERA_ROLLOUT_KEYS if self._cam_bank is not None else ())
         for k in keys:
             if k not in shapes:
                 raise ValueError(f"unknown rollout key {k!r}; choose from "
-                                 f"{self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS + self.EPISODE_ROLLOUT_KEYS + self.CTRL_ROLLOUT_KEYS}")
+                                 f"{self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS + self.EPISODE_ROLLOUT_KEYS + self.CTRL_ROLLOUT_KEYS + self.CAMERA_ROLLOUT_KEYS}")
             if k in self.EPISODE_ROLLOUT_KEYS and self._episodes is None:
                 raise ValueError(f"rollout key {k!r} needs track_episodes() / set_time_limit() first")
             if k in self.CTRL_ROLLOUT_KEYS and self._ctrl is None:
                 raise ValueError(f"rollout key {k!r} needs set_controller() first")
+            if k in self.CAMERA_ROLLOUT_KEYS and self._cam_bank is None:
+                raise ValueError(f"rollout key {k!r} needs randomize_cameras() first")
         return {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=dev) for k in keys}
 
     def rollout_info(self, rollout: Dict[str, torch.Tensor], k: int) -> Dict[str, Any]:
@@ -909,7 +1000,10 @@ class TinyCarloVecEnv(gym.Env):
             raise ValueError("car_control must be float32|float64 and maneuver int32")
         if not (car_control.is_contiguous() and maneuver.is_contiguous()):
             raise ValueError("step_multi takes contiguous tensors")
-        return PreparedStepMulti(self, car_control, maneuver, rollout, self._check_rollout(rollout, K), K)
+        call = PreparedStepMulti(self, car_control, maneuver, rollout, self._check_rollout(rollout, K), K)
+        if self._cam_bank is not None:  # (installed at once, so the object can be captured into a HIP graph right away)
+            self._install_camera_rows(rollout, K)
+        return call
 
     def _check_rollout(self, rollout: Optional[Dict[str, torch.Tensor]], K: int) -> "nat.Rollout":
         """the tc_rollout of a K-step call from its checked tensors; sizes the library's scratch for the call"""
@@ -931,6 +1025,10 @@ class TinyCarloVecEnv(gym.Env):
                 if k in self.CTRL_ROLLOUT_KEYS:  # likewise: installed per call (tc_env_set_controller)
                     if self._ctrl is None:
                         raise ValueError(f"rollout[{k!r}] needs set_controller() first")
+                    continue
+                if k in self.CAMERA_ROLLOUT_KEYS:  # likewise: installed per call (tc_env_set_camera_bank)
+                    if self._cam_bank is None:
+                        raise ValueError(f"rollout[{k!r}] needs randomize_cameras() first")
                     continue
                 setattr(r, k, t.data_ptr())
         if K > 1 and not (self.no_observation and self.render_mode is None):
@@ -958,7 +1056,13 @@ class TinyCarloVecEnv(gym.Env):
         bookkeeping, term counters and the host spawn generators (the reference has no env checkpoint; its whole state
         is `car.*`, car.py:25-32).  Tensors are cloned to the host."""
         torch.cuda.synchronize(self.device) if self.device.type == "cuda" else None
-        return {"num_envs": self.num_envs,
+        cb = self._cam_bank
+        # per-episode cameras: the bank, its draw settings, the index in force and the episode counters (only with a bank)
+        bank = {} if cb is None else {"camera_bank": {
+            "E": cb["E"].detach().cpu().clone(), "K": cb["K"].detach().cpu().clone(), "params": cb["params"].copy(),
+            "seed": cb["seed"], "env_offset": cb["env_offset"], "index": cb["index"].detach().cpu().clone(),
+            "episode": cb["episode"].detach().cpu().clone()}}
+        return {**bank, "num_envs": self.num_envs,
                 "state": {k: v.detach().cpu().clone() for k, v in self.state.items()},
                 "out": {k: v.detach().cpu().clone() for k, v in self.out.items()},
                 "aux": {k: v.detach().cpu().clone() for k, v in self._aux.items()},
@@ -1024,6 +1128,14 @@ class TinyCarloVecEnv(gym.Env):
             self.set_controller(None)
         else:
             self.set_controller(k=ctl["k"], speed=ctl["speed"])
+        bank = sd.get("camera_bank")  # (present only when a bank was installed)
+        if bank is None:
+            if self._cam_bank is not None:
+                self._install_camera_bank(None)
+        else:
+            self._install_camera_bank({"E": bank["E"].numpy(), "K": bank["K"].numpy(), "params": bank["params"],
+                                       "seed": bank["seed"], "env_offset": bank["env_offset"]},
+                                      index=bank["index"], episode=bank["episode"])
         self._step_serial += 1
 
     def request_reset(self, mask: torch.Tensor) -> None:
@@ -1143,6 +1255,8 @@ class PreparedStepMulti:
             env._install_ctrl_rows(self._noise, self._keep[2], self.K)
         elif a[0] is None:
             raise RuntimeError("a drive() call needs the controller it was prepared with (set_controller)")
+        if env._cam_bank is not None:
+            env._install_camera_rows(self._keep[2], self.K)
         if torch.cuda.current_device() == env.device.index:
             rc = nat.lib().tc_step_multi(env._h, a[0], a[1], a[2], a[3], env._flags(), a[4], env._stream())
         else:
