@@ -5557,14 +5557,18 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
         if (prof && c0 + cn >= nsteps) HIP_TRY(hipEventRecord(e->ev[1][slot], main));
         HIP_TRY(hipEventRecord(e->sim_ev, main));
         // ---- the frame stream
-        // heaviest frames first, by the last row of the call before (see the chunked form below).  Depends on nothing but
-        // this stream's own past, so it runs while the simulate launch starts
+        HIP_TRY(hipStreamWaitEvent(fs, e->start_ev, 0));
+        // heaviest frames first, by the last row of the call before (see the chunked form below).  Behind the wait: the
+        // call before may have drawn on the CALLER's stream (a call that keeps only its last frame runs its frame kernel
+        // there, reading this very permutation, behind the simulate launch that wrote the costs), so the sort that rewrites
+        // the permutation in place is ordered behind everything the caller's stream did before this call -- and it belongs
+        // to the capture when the call is captured into a graph.  start_ev is recorded ahead of the simulate launch, so the
+        // sort still runs while that launch starts
         if (e->frame_order[0] && e->cost_row[0]) {
           hipLaunchKernelGGL(tc_order_kernel, dim3(1), dim3(TC_ORDER_NT), (size_t)(N + 15) / 16 * 16, fs, e->cost_row[0], N, N, e->frame_order[0]);
           HIP_TRY(hipGetLastError());
           e->frame_order_valid[0] = true;
         }
-        HIP_TRY(hipStreamWaitEvent(fs, e->start_ev, 0));
         RArgs r = make_rargs(e, e->streamed.seg_g, e->streamed.seg_n, e->k.seg_cap, nullptr, flags, 0, sa.ma.roll.obs, mode == MODE_STEP);
         r.seg_row0 = 0;
         r.noise_row0 = c0;
@@ -5688,6 +5692,16 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     return TC_OK;
   }
   if (prof) HIP_TRY(hipEventRecord(e->ev[0][slot], main));
+  // a K-step call that is not split (no observations, one fused launch, two launches) keeps the promise of the split form:
+  // on another stream than the handle's previous K-step call it waits for that call, and it is the next call's predecessor
+  if (nsteps > 1 && e->have_call && e->last_stream != main) HIP_TRY(hipStreamWaitEvent(main, e->call_ev, 0));
+  auto end_call = [&](int rc) -> int {
+    if (rc != TC_OK || nsteps < 2) return rc;
+    HIP_TRY(hipEventRecord(e->call_ev, main));
+    e->last_stream = main;
+    e->have_call = true;
+    return TC_OK;
+  };
   StepArgs sa = args_at(0);
   sa.ma.nsteps = nsteps;
   if (plan.fused) {  // one launch: simulate + raster by the same wavefront
@@ -5719,7 +5733,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
       HIP_TRY(hipEventRecord(e->ev[2][slot], main));
       e->prof_n++;
     }
-    return noise_advance(e, mode, true, nsteps, stream);
+    return end_call(noise_advance(e, mode, true, nsteps, stream));
   }
   sa.ma.cam_here = do_raster ? 1 : 0;
   // (K steps without observations run on the one-wavefront-per-env kernel: with nothing to share the chip with, its
@@ -5737,7 +5751,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     HIP_TRY(hipEventRecord(e->ev[2][slot], main));
     e->prof_n++;
   }
-  return noise_advance(e, mode, do_raster, nsteps, stream);
+  return end_call(noise_advance(e, mode, do_raster, nsteps, stream));
 }
 
 extern "C" int tc_reset(tc_env* e, const int32_t* spawn_nodes, const uint8_t* mask, uint32_t flags, void* stream) {
