@@ -73,7 +73,31 @@ extern "C" void cam_lds(int cap_n, int cap_e, int total_nodes, int* out) {
   const int v[5] = {L.off_p, L.off_flg, L.off_list, L.off_cnt, L.total};
   std::copy(v, v + 5, out);
 }
+// in: n rows of 16 ints, the fields of CallInputs in their order; out: n rows of 8, the fields of CallPlan in theirs
+extern "C" void plan_calls(const int* in, int n, int* out) {
+  for (int i = 0; i < n; i++, in += 16, out += 8) {
+    CallInputs c;
+    c.fuse = in[0], c.multi_split = in[1], c.env_grouped = in[2], c.pipe = in[3], c.stream = in[4], c.chunk = in[5];
+    c.kvar = in[6], c.packed = in[7] != 0, c.ring_rows = in[8], c.streamed_rows = in[9], c.st_words = in[10] != 0;
+    c.flags = (unsigned)in[11], c.no_frame_flags = (unsigned)in[12], c.nsteps = in[13], c.obs = in[14] != 0, c.all = in[15] != 0;
+    const CallPlan p = plan_call(c);
+    const int v[8] = {p.do_raster, p.fused, p.split, p.frames, p.grouped, p.piped, p.streamed, p.steps};
+    std::copy(v, v + 8, out);
+  }
+}
 """
+CALL_INPUTS = ("fuse", "multi_split", "env_grouped", "pipe", "stream", "chunk", "kvar", "packed", "ring_rows", "streamed_rows",
+               "st_words", "flags", "no_frame_flags", "nsteps", "obs", "all")
+CALL_PLAN = ("do_raster", "fused", "split", "frames", "grouped", "piped", "streamed", "steps")
+
+
+def plan_calls(lib, rows):
+    """plan_call through the shim over many inputs: rows [n, len(CALL_INPUTS)] int32 -> [n, len(CALL_PLAN)] int32"""
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    assert rows.ndim == 2 and rows.shape[1] == len(CALL_INPUTS)
+    out = np.zeros((len(rows), len(CALL_PLAN)), dtype=np.int32)
+    lib.plan_calls(_ptr(rows), len(rows), _ptr(out))
+    return out
 
 
 def build_plan_shim(d):

@@ -414,6 +414,37 @@ def test_two_launch_and_fused_paths_agree_with_oracle(fuse, monkeypatch):
     env.close()
 
 
+def test_profile_of_fused_steps_after_piped_calls():
+    """The profile ring's slots are reused across forms: eight streamed 2-step calls flag every slot in use as piped (their
+    second interval starts at the first frame launch's own event), then eight fused single steps take the same slots.  A
+    fused step is one kernel with two events recorded back to back behind it, so its second interval cannot exceed its
+    first -- unless a slot kept the flag and the read measured from an event of the old call."""
+    N, K = 4, 2
+    env = make_env("simple_layout", "r64", "classes", N)
+    env.reset(seed=5)
+    rng = np.random.default_rng(8)
+    cck = torch.from_numpy(np.stack([rng.uniform(0.3, 1, (K, N)), rng.uniform(-1, 1, (K, N))], axis=2).astype(np.float32)).cuda()
+    mank = torch.from_numpy(rng.integers(0, 4, (K, N)).astype(np.int32)).cuda()
+    roll = env.alloc_rollout(K, keys="all")
+    call = env.prepare_step_multi(cck, mank, roll)
+    info = env.launch_info(K)
+    assert not info["fused"] and info["kernel"] == "tc_envg_kernel+tc_frame_kernel" and info["steps_per_dispatch"] == K, info
+    assert env.launch_info(1)["fused"]
+    env.profile(1)
+    for _ in range(8):
+        call()
+    p = env.profile_read()
+    assert p["launches"] == 8 and p["simulate_us"] > 0, p
+    env.profile(1)
+    for _ in range(8):
+        env.step_device(cck[0], mank[0])
+    p = env.profile_read()
+    print("profile of the fused steps:", p)
+    assert p["launches"] == 8 and p["simulate_us"] > 0, p
+    assert p["raster_us"] <= p["simulate_us"], p
+    env.close()
+
+
 def test_abi_error_paths_on_device():
     """status codes instead of crashes: step before bind / before reset, bad spawn nodes, bad dtypes"""
     import ctypes as C

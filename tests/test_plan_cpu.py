@@ -5,6 +5,9 @@ duplicate edges, self-loops, isolated nodes; "<case>/<k>" below is map k of a ca
 
 A plan that reports success is held to the properties the camera stage relies on ("Host structure"); whether
 it must report failure is worked out here, independently, from the component sizes of the map.
+
+plan_call, the planner of a call's route through launch(), runs over the full product of its inputs against a restatement
+of CallPlan's field comments, its invariants, and the two restatements other tests already hold (at the end of this file).
 """
 import ctypes as C
 
@@ -171,3 +174,123 @@ def test_layer_groups_on_generated_maps(plan, graphs, name):
     gn, ge = np.diff(node_off[layer]), np.diff(edge_off[layer])
     assert gn.max() <= largest and ge.max() <= largest
     assert caps[0] == gn.max() and caps[1] == ge.max()
+
+
+# ---------------------------------------------------------------------------------------------- plan_call
+NO_OBSERVATION = 1       # TC_F_NO_OBSERVATION
+NO_FRAME_FLAGS = 0x401   # ... | DBG_SKIP_CAMERA: what the host side passes as no_frame_flags
+CHUNKS = (2, 16)
+KVARS = (5, 8, 9, 13)
+NSTEPS = (1, 2, 3, 5, 9, 20, 64, 200)
+RING_ROWS = (0, 2, 16)
+STREAMED_ROWS = (0, 1, 2, 9, 128)
+
+
+@pytest.fixture(scope="module")
+def calls(plan):
+    """the full product of plan_call's inputs -> (inputs by name, plan_call's answers by name), one array per field"""
+    axes = {"fuse": (0, 1), "multi_split": (0, 1), "env_grouped": (0, 1), "pipe": (0, 1), "stream": (0, 1), "chunk": CHUNKS,
+            "kvar": KVARS, "packed": (0, 1), "ring_rows": RING_ROWS, "streamed_rows": STREAMED_ROWS, "st_words": (0, 1),
+            "flags": (0, NO_OBSERVATION), "no_frame_flags": (NO_FRAME_FLAGS,), "nsteps": NSTEPS, "obs": (0, 1), "all": (0, 1)}
+    assert tuple(axes) == big_maps.CALL_INPUTS
+    grid = np.meshgrid(*[np.asarray(v, dtype=np.int32) for v in axes.values()], indexing="ij")
+    rows = np.stack([g.ravel() for g in grid], axis=1)
+    out = big_maps.plan_calls(plan, rows)
+    i = dict(zip(big_maps.CALL_INPUTS, rows.T))
+    p = dict(zip(big_maps.CALL_PLAN, out.T))
+    for k in big_maps.CALL_PLAN[:-1]:
+        assert np.isin(p[k], (0, 1)).all()
+        p[k] = p[k].astype(bool)
+    return i, p
+
+
+def restated_plan(i):
+    """CallPlan restated from its field comments (tc_plan.h), by the form a call takes rather than bit by bit.
+
+    Frames are drawn when there is a tensor and no flag forbids it.  A handle has the frame kernel unless its simulate
+    stage is the K = 13 one or TC_FUSE=0; it has the fused step kernel when it has the frame kernel and the format is not
+    the packed one.  A call that draws is then one of:
+      fused      a single step with the step kernel; K steps with it under TC_MULTI_SPLIT=0
+      split      every other K-step call: with the frame kernel (`frames`) or with camera-in-simulate + raster launches
+      two        a single step without the step kernel
+    A split call with the frame kernel simulates with the grouped kernel under TC_ENV_GROUPED; such a call is piped when
+    TC_CHUNK > 0 and every frame is wanted, and a piped call is streamed under TC_STREAM once the scratch of streamed calls
+    (two rows at least) and its two device words exist.
+    Steps per dispatch: a streamed call, all of them or as many as its scratch has rows; a fused call, all of them;
+    a piped chunked call, TC_CHUNK or a quarter of the call (rounded up, two at least), whichever is less; any other
+    call, all of them -- and whatever is neither fused nor streamed never more than a slot of the ring holds, when there
+    is a ring (tc_env_launch_info reports the two-launch forms so, too)."""
+    b = {k: v.astype(bool) for k, v in i.items() if k not in ("chunk", "kvar", "ring_rows", "streamed_rows", "flags", "no_frame_flags", "nsteps")}
+    draws = b["obs"] & ((i["flags"] & i["no_frame_flags"]) == 0)
+    has_frame_kernel = b["fuse"] & (i["kvar"] != 13)
+    has_step_kernel = has_frame_kernel & ~b["packed"]
+    k_steps = i["nsteps"] > 1
+    form = np.select([~draws, ~k_steps & has_step_kernel, ~k_steps, has_step_kernel & ~b["multi_split"]],
+                     ["none", "fused", "two", "fused"], default="split")
+    p = {"do_raster": draws, "fused": form == "fused", "split": form == "split"}
+    p["frames"] = p["split"] & has_frame_kernel
+    p["grouped"] = p["frames"] & b["env_grouped"]
+    p["piped"] = p["grouped"] & b["pipe"] & b["all"]
+    p["streamed"] = p["piped"] & b["stream"] & (i["streamed_rows"] >= 2) & b["st_words"]
+    quarter = np.maximum(2, -(-i["nsteps"] // 4))
+    steps = np.where(p["streamed"], np.minimum(i["nsteps"], i["streamed_rows"]),
+                     np.where(p["piped"], np.minimum(i["chunk"], quarter), i["nsteps"]))
+    ring_caps = ~p["fused"] & ~p["streamed"] & (i["ring_rows"] > 0)
+    p["steps"] = np.where(ring_caps, np.minimum(steps, i["ring_rows"]), steps)
+    return p
+
+
+def test_plan_call_equals_its_restatement(calls):
+    i, p = calls
+    assert len(p["steps"]) == 2 ** 10 * len(CHUNKS) * len(KVARS) * len(NSTEPS) * len(RING_ROWS) * len(STREAMED_ROWS)
+    want = restated_plan(i)
+    for k in big_maps.CALL_PLAN:
+        bad = np.flatnonzero(p[k] != want[k])
+        assert not len(bad), (k, len(bad), {f: int(v[bad[0]]) for f, v in i.items()}, int(p[k][bad[0]]), int(want[k][bad[0]]))
+    for k in big_maps.CALL_PLAN[:-1]:  # (every form occurs in the product)
+        assert p[k].any() and not p[k].all(), k
+
+
+def test_plan_call_invariants(calls):
+    i, p = calls
+    implies = lambda a, b: (~a | b).all()
+    assert not (p["fused"] & p["split"]).any()
+    assert implies(p["fused"] | p["split"], p["do_raster"])
+    assert implies(p["streamed"], p["piped"]) and implies(p["piped"], p["frames"]) and implies(p["frames"], p["split"])
+    assert implies(p["grouped"], p["frames"]) and implies(p["piped"], p["grouped"])
+    assert implies(p["piped"], i["all"] != 0)
+    packed = i["packed"] != 0
+    assert not (packed & p["fused"]).any()
+    assert implies(packed & (i["nsteps"] > 1) & p["do_raster"], p["split"])
+    assert (p["steps"] >= 1).all() and (p["steps"] <= i["nsteps"]).all()
+    assert implies(p["streamed"], p["steps"] <= i["streamed_rows"])
+    assert implies(~p["fused"] & ~p["streamed"] & (i["ring_rows"] > 0), p["steps"] <= i["ring_rows"])
+
+
+def kernel_name(p):
+    """tc_env_launch_info's kernel names (no controller) from the plan's bits"""
+    return np.select([p["fused"], p["grouped"], p["frames"], p["do_raster"]],
+                     ["tc_step_kernel", "tc_envg_kernel+tc_frame_kernel", "tc_env_kernel+tc_frame_kernel", "tc_env_kernel+tc_raster_kernel"],
+                     default="tc_env_kernel")
+
+
+def test_plan_call_restatements_agree(calls):
+    """the restatement above against the two the tests already had, on the inputs those cover: big_maps.expected_launch (a
+    byte format that draws frames, TC_MULTI_SPLIT at its default: the kernel names by kvar, TC_FUSE and TC_ENV_GROUPED) and
+    the chunk formula of test_gpu_call_sequences.check_launches (a piped chunked call whose ring holds a chunk)"""
+    i, _ = calls
+    want = restated_plan(i)
+    names = kernel_name(want)
+    covered = (i["multi_split"] == 1) & (i["packed"] == 0) & want["do_raster"]
+    assert covered.any()
+    for kvar in KVARS:
+        for fuse in (0, 1):
+            for grouped in (0, 1):
+                for n in NSTEPS:
+                    sel = covered & (i["kvar"] == kvar) & (i["fuse"] == fuse) & (i["env_grouped"] == grouped) & (i["nsteps"] == n)
+                    _, name = big_maps.expected_launch({"kvar": kvar, "kframe": kvar}, n, fuse=bool(fuse), env_grouped=bool(grouped))
+                    assert sel.any() and (names[sel] == name).all(), (kvar, fuse, grouped, n, name, set(names[sel]))
+    chunked = want["piped"] & ~want["streamed"] & (i["ring_rows"] >= i["chunk"])
+    assert chunked.any() and set(i["nsteps"][chunked]) == set(NSTEPS) - {1}
+    k, chunk = i["nsteps"][chunked], i["chunk"][chunked]
+    assert np.array_equal(want["steps"][chunked], np.minimum(chunk, np.maximum(2, (k + 3) // 4)))

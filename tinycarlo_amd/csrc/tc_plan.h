@@ -1,7 +1,7 @@
-// Host-only planners of tc_env_create: how the camera stage's work is cut into groups and where its buffers sit in
-// LDS.  Pure arithmetic on host arrays -- no HIP header, no device call -- so the host compiler builds it alone
-// (tests/test_plan_cpu.py does).  The limits that belong to the kernels (group count, register-cache sizes) come in as
-// arguments.
+// Host-only planners: of tc_env_create, how the camera stage's work is cut into groups and where its buffers sit in
+// LDS; of a call, which route it takes through launch() (plan_call, at the end).  Pure arithmetic on host values -- no
+// HIP header, no device call -- so the host compiler builds it alone (tests/test_plan_cpu.py does).  The limits that
+// belong to the kernels (group count, register-cache sizes) come in as arguments.
 #pragma once
 #include <vector>
 
@@ -180,4 +180,65 @@ static inline void plan_cam_lds(Layout& L, int cap_n, int cap_e, int total_nodes
   L.off_cnt = off;
   off += 64;
   L.total = off;
+}
+
+// Which way a call of nsteps steps goes through launch() on a handle: decided here for launch(), which dispatches on
+// it, and for tc_env_launch_info, which reports it.  What the decision reads of the handle and of the call comes in as
+// plain values (the host side fills them in one place, plan_of()).
+struct CallInputs {
+  // the switches, in this order: TC_FUSE, TC_MULTI_SPLIT, TC_ENV_GROUPED, TC_CHUNK > 0 (pipe), TC_STREAM, and the value
+  // of TC_CHUNK (chunk)
+  int fuse, multi_split, env_grouped, pipe, stream, chunk;
+  int kvar;            // register-cache slots of the handle's simulate stage: 5, 8, 9, 13
+  bool packed;         // the observation format is the packed class masks (TC_FMT_CLASSES_BITS)
+  int ring_rows;       // steps a slot of the scratch ring of chunked calls holds (0: no ring)
+  int streamed_rows;   // steps the scratch of streamed calls holds (0: none)
+  bool st_words;       // the two device words of a streamed call exist
+  unsigned flags;      // the call's flags ...
+  unsigned no_frame_flags;  // ... and the bits of them that leave the frames out (they belong to the kernels' header)
+  int nsteps;
+  bool obs;            // there is a tensor to draw into (the bound one or the rollout's)
+  bool all;            // every step's frame is wanted (a rollout with observations), else only the last one survives
+};
+struct CallPlan {
+  bool do_raster;  // frames are drawn at all
+  bool fused;      // one tc_step_kernel launch: simulate + raster by the same wavefront
+  bool split;      // K steps with frames: per chunk ONE simulate launch over its steps and ONE launch over the frames
+                   // wanted (neither: one tc_env_kernel launch, and a tc_raster_kernel launch behind it when frames are
+                   // drawn)
+  bool frames;     // split: camera + raster per frame (tc_frame_kernel); else camera in the simulate launch (the
+                   // register-hungry K = 13 stage, TC_FUSE=0) and a raster launch
+  bool grouped;    // frames: the simulate launches are the grouped kernel (tc_envg_kernel), else one wavefront per env
+  bool piped;      // split: the frames of a chunk are produced on an internal stream, beside the next simulate launch
+  bool streamed;   // piped: the whole call (or st_rows steps of it) is one simulate launch and one gated frame launch
+  int steps;       // steps per simulate / frame dispatch
+};
+static inline CallPlan plan_call(const CallInputs& in) {
+  CallPlan p;
+  // (the register-hungry K = 13 simulate stage spills when fused, so it stays two launches)
+  const bool can_frames = in.fuse && in.kvar != 13;
+  // packed class masks have tc_frame_kernel and tc_raster_kernel variants only: a single step is the two-launch form,
+  // K steps are always split (TC_MULTI_SPLIT=0 is ignored)
+  const bool can_fuse = can_frames && !in.packed;
+  p.do_raster = !(in.flags & in.no_frame_flags) && in.obs;
+  p.split = p.do_raster && in.nsteps > 1 && (in.multi_split || !can_fuse);
+  p.fused = p.do_raster && can_fuse && !p.split;
+  p.frames = p.split && can_frames;
+  p.grouped = p.frames && in.env_grouped;
+  p.piped = p.grouped && in.pipe && in.all;
+  p.streamed = p.piped && in.stream && in.streamed_rows >= 2 && in.st_words;
+  p.steps = in.nsteps;
+  if (p.streamed) {
+    if (p.steps > in.streamed_rows) p.steps = in.streamed_rows;
+  } else if (!p.fused) {
+    // a chunk of a pipelined call: TC_CHUNK (16) steps, or a quarter of the call when that is less, so that a short
+    // call (the 20 steps of a smoke benchmark) still has several chunks in flight; never more than a ring slot holds.
+    // Calls that are not pipelined run in chunks as large as the ring allows.
+    if (p.piped) {
+      const int q = (in.nsteps + 3) / 4;
+      p.steps = in.chunk < q ? in.chunk : (q < 2 ? 2 : q);
+    }
+    if (in.ring_rows > 0 && p.steps > in.ring_rows) p.steps = in.ring_rows;
+  }
+  return p;
 }

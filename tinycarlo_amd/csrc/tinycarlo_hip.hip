@@ -4101,7 +4101,7 @@ struct tc_env {
   int draw_n = 0;
   const int* draw_base = nullptr;  // the [rows][N] array the pairs index: the ring's, or the streamed call's
   // Streamed K-step calls (tune.stream = 0: chunked): ONE simulate launch for all steps of the call and ONE frame launch
-  // beside it whose workgroups wait for their pose row -- see launch().  Scratch for streamed.rows steps
+  // beside it whose workgroups wait for their pose row -- see launch_streamed().  Scratch for streamed.rows steps
   // (tc_env_reserve_steps), every pose entry TC_POSE_EMPTY between calls; longer calls run as segments of that many steps.
   ScratchRows streamed;
   DevPtr<unsigned int> st_words;  // [0] simulate workgroups resident, [1] "a frame workgroup gave up waiting"
@@ -4567,7 +4567,7 @@ static int raise_lds_limits(const tc_env* e) {
             raise((const void*)step_kernel_of(kcode, t, fmt, feat), lds, (feat & TC_FEAT_CTRL) ? "tc_drive_step_kernel" : "tc_step_kernel");
           raise((const void*)frame_kernel_of(kcode, t, fmt, false), lds, "tc_frame_kernel");
         }
-  // tc_envg_kernel's LDS copies of the map (edge records + fat lanepath nodes, see launch()) can exceed the 48 KB default
+  // tc_envg_kernel's LDS copies of the map (edge records + fat lanepath nodes, see launch_envg()) can exceed the 48 KB default
   const size_t envg_lds = ((size_t)m.total_edges * 48 + 15) / 16 * 16 + (size_t)m.lpN * sizeof(LpNode);
   if (envg_lds > 40 * 1024)
     for (unsigned feat = 0; feat <= (TC_FEAT_CTRL | TC_FEAT_ALL); feat++)
@@ -5230,14 +5230,20 @@ static RArgs make_rargs(tc_env* e, const int* seg_g, const int* seg_n, int seg_c
   return r;
 }
 
-static int launch_raster(tc_env* e, const int* seg_g, const int* seg_n, int seg_cap, const uint8_t* mask, uint32_t flags,
-                         void* stream, int env0 = 0, int count = -1, uint8_t* obs = nullptr, bool with_noise = false) {
+static int check_stamp_buffer(const tc_env* e) {
 #ifdef TC_TIMING
   if (g_tstamp && e->k.N > g_tstamp_n) {
     set_err("timing build: the installed stamp buffer is smaller than this env batch");
     return TC_E_INVALID;
   }
 #endif
+  return TC_OK;
+}
+
+static int launch_raster(tc_env* e, const int* seg_g, const int* seg_n, int seg_cap, const uint8_t* mask, uint32_t flags,
+                         void* stream, int env0 = 0, int count = -1, uint8_t* obs = nullptr, bool with_noise = false) {
+  int rc = check_stamp_buffer(e);
+  if (rc != TC_OK) return rc;
   RArgs r = make_rargs(e, seg_g, seg_n, seg_cap, mask, flags, env0, obs, with_noise);
   if (count < 0) count = e->k.N;
   hipLaunchKernelGGL(raster_kernel_of(r.cam.thickness > 1, r.cam.format), dim3(count), dim3(TC_NT), e->r_lds, (hipStream_t)stream, r);
@@ -5254,47 +5260,19 @@ static int noise_advance(tc_env* e, int mode, bool rendered, int nsteps, void* s
   return TC_OK;
 }
 
-// Which way a call of nsteps steps goes through launch() on this handle: decided here for launch(), which branches on
-// it, and for tc_env_launch_info, which reports it.  obs: there is a tensor to draw into (the bound one or the rollout's);
-// all: every step's frame is wanted (a rollout with observations), else only the last one survives.
-struct CallPlan {
-  bool do_raster;  // frames are drawn at all
-  bool fused;      // one tc_step_kernel launch: simulate + raster by the same wavefront
-  bool split;      // K steps with frames: per chunk ONE simulate launch over its steps and ONE launch over the frames wanted
-                   // (neither: one tc_env_kernel launch, and a tc_raster_kernel launch behind it when frames are drawn)
-  bool frames;     // split: camera + raster per frame (tc_frame_kernel); else camera in the simulate launch (the
-                   // register-hungry K = 13 stage, TC_FUSE=0) and a raster launch
-  bool piped;      // split: the frames of a chunk are produced on an internal stream, beside the next simulate launch
-  bool streamed;   // piped: the whole call (or st_rows steps of it) is one simulate launch and one gated frame launch
-  int steps;       // steps per simulate / frame dispatch
-};
-static CallPlan plan_call(const tc_env* e, uint32_t flags, int nsteps, bool obs, bool all) {
-  CallPlan p;
-  // (the register-hungry K = 13 simulate stage spills when fused, so it stays two launches)
-  const bool can_frames = e->tune.fuse && e->kvar != 13;
-  // packed class masks have tc_frame_kernel and tc_raster_kernel variants only: a single step is the two-launch form, K steps
-  // are always split (TC_MULTI_SPLIT=0 is ignored)
-  const bool can_fuse = can_frames && e->k.cam.format != TC_FMT_CLASSES_BITS;
-  p.do_raster = !(flags & (TC_F_NO_OBSERVATION | DBG_SKIP_CAMERA)) && obs;
-  p.split = p.do_raster && nsteps > 1 && (e->tune.multi_split || !can_fuse);
-  p.fused = p.do_raster && can_fuse && !p.split;
-  p.frames = p.split && can_frames;
-  p.piped = p.frames && e->tune.env_grouped && e->tune.pipe && all;
-  p.streamed = p.piped && e->tune.stream && e->streamed.rows >= 2 && e->st_words;
-  p.steps = nsteps;
-  if (p.streamed) {
-    if (p.steps > e->streamed.rows) p.steps = e->streamed.rows;
-  } else if (!p.fused) {
-    // a chunk of a pipelined call: TC_CHUNK (16) steps, or a quarter of the call when that is less, so that a short call
-    // (the 20 steps of a smoke benchmark) still has several chunks in flight; never more than a ring slot holds.  Calls
-    // that are not pipelined run in chunks as large as the ring allows.
-    if (p.piped) {
-      const int q = (nsteps + 3) / 4;
-      p.steps = e->tune.chunk < q ? e->tune.chunk : (q < 2 ? 2 : q);
-    }
-    if (e->ring.rows > 0 && p.steps > e->ring.rows) p.steps = e->ring.rows;
-  }
-  return p;
+// What plan_call (tc_plan.h) reads, filled from the handle and the call: for launch(), which dispatches on the plan, and for
+// tc_env_launch_info, which reports it.  obs: there is a tensor to draw into (the bound one or the rollout's); all: every
+// step's frame is wanted (a rollout with observations), else only the last one survives.
+static CallPlan plan_of(const tc_env* e, uint32_t flags, int nsteps, bool obs, bool all) {
+  const Tuning& t = e->tune;
+  CallInputs in;
+  in.fuse = t.fuse; in.multi_split = t.multi_split; in.env_grouped = t.env_grouped; in.pipe = t.pipe; in.stream = t.stream; in.chunk = t.chunk;
+  in.kvar = e->kvar;
+  in.packed = e->k.cam.format == TC_FMT_CLASSES_BITS;
+  in.ring_rows = e->ring.rows; in.streamed_rows = e->streamed.rows; in.st_words = e->st_words != nullptr;
+  in.flags = flags; in.no_frame_flags = TC_F_NO_OBSERVATION | DBG_SKIP_CAMERA;
+  in.nsteps = nsteps; in.obs = obs; in.all = all;
+  return plan_call(in);
 }
 
 #define TC_STREAM_MAX_ROWS 128
@@ -5385,13 +5363,36 @@ static tc_rollout rollout_at(const tc_rollout& r, size_t r0, size_t obs_bytes, s
   return q;
 }
 
+// One call of launch(): its arguments and what every route needs of them.
+struct Call {
+  int mode;
+  const void* cc;
+  int cdtype;
+  const int32_t *man, *spawn;
+  const uint8_t* mask;
+  uint32_t flags;
+  hipStream_t main;  // the caller's stream
+  int nsteps;
+  const tc_rollout* roll;
+  bool ep_rows;
+  // per-env cars (tc_env_set_car_per_env) and episodes (tc_env_set_episodes): the instantiations of the simulate stages
+  // with those bits, the same launches otherwise
+  unsigned feat;
+  bool all;  // with a rollout every step's frame is wanted; else only the last survives
+  bool thick;
+  int fmt;
+  CallPlan plan;
+  bool prof;  // the call is recorded in slot `slot` of the profile ring
+  int slot;
+};
+
 // What a simulate launch is given of the CALL, for the launch whose first step is step c0 of it: the handle's arguments
 // and feature rows, mode / dtype / flags, and the control, maneuver, rollout and episode rows from [step][env] row c0 * N
 // on.  What belongs to the path is left to the caller: ma.nsteps and the members of ma behind it, the scratch a.seg_g /
 // a.seg_n point to, r, env_order.
-static StepArgs step_args_at(const tc_env* e, int mode, const void* cc, int cdtype, const int32_t* man, const int32_t* spawn,
-                             const uint8_t* mask, uint32_t flags, const tc_rollout* roll, bool ep_rows, int c0) {
+static StepArgs step_args_at(const tc_env* e, const Call& c, int c0) {
   const size_t r0 = (size_t)c0 * e->k.N;
+  const bool ep_rows = c.ep_rows;
   StepArgs sa;
   memset(&sa, 0, sizeof(sa));
   sa.a = e->k;
@@ -5405,18 +5406,18 @@ static StepArgs step_args_at(const tc_env* e, int mode, const void* cc, int cdty
   sa.ct.rows = ep_rows && e->ct.rows ? e->ct.rows + r0 : nullptr;
   sa.cb = e->cb;  // (the index rows likewise)
   sa.cb.rows = ep_rows && e->cb.index && e->cb.rows ? e->cb.rows + r0 : nullptr;
-  if (roll) sa.ma.roll = rollout_at(*roll, r0, (size_t)e->obs_bytes, (size_t)e->k.m.C);
-  sa.mode = mode;
-  sa.cdtype = cdtype;
-  sa.flags = (flags & ~TC_FI_CAM_BANK) | (e->cb.index ? TC_FI_CAM_BANK : 0u);
-  sa.car_control = cc ? (const char*)cc + r0 * 2 * (cdtype == TC_F32 ? 4 : 8) : nullptr;  // (NULL: a controller acts)
-  sa.maneuver = man + r0;
-  sa.spawn_nodes = spawn;
-  sa.mask = mask;
+  if (c.roll) sa.ma.roll = rollout_at(*c.roll, r0, (size_t)e->obs_bytes, (size_t)e->k.m.C);
+  sa.mode = c.mode;
+  sa.cdtype = c.cdtype;
+  sa.flags = (c.flags & ~TC_FI_CAM_BANK) | (e->cb.index ? TC_FI_CAM_BANK : 0u);
+  sa.car_control = c.cc ? (const char*)c.cc + r0 * 2 * (c.cdtype == TC_F32 ? 4 : 8) : nullptr;  // (NULL: a controller acts)
+  sa.maneuver = c.man + r0;
+  sa.spawn_nodes = c.spawn;
+  sa.mask = c.mask;
   return sa;
 }
 
-// The argument block of a frame launch over scratch rows: of the streamed form (gated: see launch()) or of the ring.
+// The argument block of a frame launch over scratch rows: of the streamed form (gated: see launch_streamed()) or of the ring.
 // `gate` and `order` are the launch's own.
 static FrameArgs frame_args_of(const tc_env* e, uint32_t flags, const RArgs& r, bool streamed) {
   FrameArgs fa;
@@ -5456,6 +5457,256 @@ static int launch_envg(const tc_env* e, unsigned feat, StepArgs& sa, hipStream_t
   return TC_OK;
 }
 
+// Heaviest frames first on frame stream fsi (0: frame_stream, also the caller's stream of a call that is not piped; 1:
+// frame_stream2).  With `sort` the permutation is rewritten on `fs` from the draw-list lengths of the last frame row
+// launched on that stream, when there are a buffer and such a row.  *order: what goes into FrameArgs -- the buffer once a
+// sort has run on it, else NULL (env order).
+static int frame_order_of(tc_env* e, int fsi, hipStream_t fs, bool sort, const int** order) {
+  const int N = e->k.N;
+  if (sort && e->frame_order[fsi] && e->cost_row[fsi]) {
+    hipLaunchKernelGGL(tc_order_kernel, dim3(1), dim3(TC_ORDER_NT), (size_t)(N + 15) / 16 * 16, fs, e->cost_row[fsi], N, N, e->frame_order[fsi]);
+    HIP_TRY(hipGetLastError());
+    e->frame_order_valid[fsi] = true;
+  }
+  *order = e->frame_order[fsi] && e->frame_order_valid[fsi] ? (const int*)e->frame_order[fsi] : nullptr;
+  return TC_OK;
+}
+
+// Streamed form (default when every step's frame is wanted).  The chunked pipeline of launch_chunked pays for its structure: the
+// first chunk's simulate launch overlaps with nothing, and every frame dispatch ends in a tail with the chip half empty
+// -- a quarter of a 20-step call.  Here the whole call (or a segment of st_rows steps) is ONE simulate launch on the
+// caller's stream and ONE frame launch of steps x N workgroups on the internal stream that starts right away, beside
+// it: a frame workgroup polls its pose row until the simulate launch has written it (device-scope loads; every entry
+// validates itself, tc_frame_kernel).  Only the first step is exposed, and there is one tail per call.
+//   frame stream: [order kernel] [tc_gate_kernel: until the simulate workgroups are resident] [tc_frame_kernel, gate 1]
+//                 (wait: simulate launch done) [tc_frame_recover_kernel: whatever a gate-1 workgroup gave up on]
+// Every wait on the device is bounded (gate_ticks), and what a bound cuts short the recover pass completes: the
+// result never depends on how the two launches were scheduled.
+static int launch_streamed(tc_env* e, const Call& c) {
+  const int N = e->k.N, nsteps = c.nsteps;
+  const hipStream_t main = c.main, fs = e->frame_stream;
+  e->draw_n = 0;
+  e->draw_base = e->streamed.seg_n;
+  int si = 0;
+  for (int c0 = 0, cn = 0; c0 < nsteps; c0 += cn, si++) {
+    cn = nsteps - c0 < c.plan.steps ? nsteps - c0 : c.plan.steps;
+    // a later segment reuses the scratch rows: the frames of the one before must be drawn (and its rows cleared)
+    if (si > 0) HIP_TRY(hipStreamWaitEvent(main, e->slot_ev[0], 0));
+    HIP_TRY(hipEventRecord(e->start_ev, main));
+    StepArgs sa = step_args_at(e, c, c0);
+    sa.a.seg_g = e->streamed.seg_g;
+    sa.a.seg_n = e->streamed.seg_n;
+    sa.ma.nsteps = cn;
+    sa.ma.seg_rows = cn > 1 ? cn : 2;
+    sa.ma.pose_rows = e->streamed.pose;
+    sa.ma.resident = e->st_words;
+    int rc = launch_envg(e, c.feat, sa, main);
+    if (rc != TC_OK) return rc;
+    if (c.prof && c0 + cn >= nsteps) HIP_TRY(hipEventRecord(e->ev[1][c.slot], main));
+    HIP_TRY(hipEventRecord(e->sim_ev, main));
+    // ---- the frame stream
+    HIP_TRY(hipStreamWaitEvent(fs, e->start_ev, 0));
+    // heaviest frames first, by the last row of the call before (see the chunked form below).  Behind the wait: the
+    // call before may have drawn on the CALLER's stream (a call that keeps only its last frame runs its frame kernel
+    // there, reading this very permutation, behind the simulate launch that wrote the costs), so the sort that rewrites
+    // the permutation in place is ordered behind everything the caller's stream did before this call -- and it belongs
+    // to the capture when the call is captured into a graph.  start_ev is recorded ahead of the simulate launch, so the
+    // sort still runs while that launch starts
+    const int* order;
+    rc = frame_order_of(e, 0, fs, true, &order);
+    if (rc != TC_OK) return rc;
+    RArgs r = make_rargs(e, e->streamed.seg_g, e->streamed.seg_n, e->k.seg_cap, nullptr, c.flags, 0, sa.ma.roll.obs, c.mode == MODE_STEP);
+    r.seg_row0 = 0;
+    r.noise_row0 = c0;
+    r.obs_row_stride = (long long)N * (long long)e->obs_bytes;
+    FrameArgs fa = frame_args_of(e, c.flags, r, true);
+    fa.order = order;
+    // (ten times the patience of a frame workgroup: one idle wavefront costs nothing, and when another env's frame
+    // launch has the chip -- two handles stepping on one GPU -- the simulate workgroups only get on as that launch drains)
+    hipLaunchKernelGGL(tc_gate_kernel, dim3(1), dim3(64), 0, fs, (const unsigned int*)e->st_words, envg_grid(N), 10 * e->tune.gate_ticks);
+    HIP_TRY(hipGetLastError());
+    if (c.prof && si == 0) HIP_TRY(hipEventRecord(e->ev[3][c.slot], fs));
+    fa.gate = 1;
+    hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, false), dim3(N, cn), dim3(TC_NT), e->frame_lds, fs, fa);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamWaitEvent(fs, e->sim_ev, 0));
+    fa.gate = 2;
+    fa.recover_rows = cn;
+    fa.order = nullptr;
+    hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, true), dim3(N), dim3(TC_NT), e->frame_lds, fs, fa);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e->slot_ev[0], fs));
+    if (e->frame_order[0]) e->cost_row[0] = e->streamed.seg_n + (size_t)(cn - 1) * N;
+    const int keep = cn < 3 * 16 ? cn : 3 * 16;  // the statistics cover the same span as a chunked call's ring
+    e->draw_rows[0][0] = cn - keep;
+    e->draw_rows[0][1] = keep;
+    e->draw_n = 1;
+  }
+  // join the frame stream back; the end-of-frames probe then sits on the caller's stream behind the join
+  HIP_TRY(hipEventRecord(e->frames_ev, fs));
+  HIP_TRY(hipStreamWaitEvent(main, e->frames_ev, 0));
+  return TC_OK;
+}
+
+// K steps, split form: per chunk ONE simulate launch over its steps and ONE launch over the frames wanted.  The pose
+// rows / draw lists of a chunk live in slot (chunk index mod TC_RING_SLOTS) of the scratch ring.
+static int launch_chunked(tc_env* e, const Call& c) {
+  const int N = e->k.N, nsteps = c.nsteps;
+  const hipStream_t main = c.main;
+  const bool frames = c.plan.frames, all = c.all;
+  // Pipelining inside the call.  The steps are issued in chunks: the simulate launch of chunk c+1 runs on the caller's
+  // stream while the frames of chunk c are produced on an internal stream (joined back before the call's work ends
+  // on the caller's stream, so the caller still sees everything complete in stream order).  The two kernels suit
+  // each other: the frame kernel is bound by vector issue, the grouped simulate kernel by latency (512 wavefronts
+  // for 4096 envs), so the second hides in the first's shadow instead of adding its 21 us per step.
+  // (Measured and dropped, DESIGN.md section 4: chunk sizes ramping up 1, 2, 4, ...; a short or half first chunk; other
+  // divisors than 4 for short calls.)
+  const bool piped = c.plan.piped;
+  const int chunk = c.plan.steps;
+  hipStream_t fs = piped ? (hipStream_t)e->frame_stream : main;
+  // Short calls (chunks of fewer than 8 steps): a frame launch of 5 x N workgroups spends a good part of its life
+  // ramping up and draining (5 rows: 34.6 us per row alone, 16 rows: 30.8), and a 20-step call is four of them.  There
+  // the frame launches of consecutive chunks go to two streams alternately -- each still behind its own chunk's
+  // simulate launch -- so that chunk c+1's workgroups fill the slots chunk c's tail leaves empty (cfg3: 8-step call
+  // 66.2 -> 58.3 us per step, 20-step call 46.9 -> 44.0; with chunks of 10 steps it costs 7 %, so longer calls keep one
+  // stream and their frame launches follow one another, as a kernel trace of the default command shows them).
+  const bool two_fs = piped && e->tune.frame_streams == 2 && chunk < 8;
+  bool first_frames = true;
+  bool used_fs[2] = {false, false};
+  e->draw_n = 0;
+  e->draw_base = e->ring.seg_n;
+  int ci = 0;
+  for (int c0 = 0, cn = 0; c0 < nsteps; c0 += cn, ci++) {
+    cn = nsteps - c0 < chunk ? nsteps - c0 : chunk;
+    const int rslot = ci % TC_RING_SLOTS;
+    const size_t rb = (size_t)rslot * e->ring.rows;   // first row of this chunk in the scratch ring
+    // the frames that read this ring slot TC_RING_SLOTS chunks ago must be done before it is rewritten
+    if (piped && ci >= TC_RING_SLOTS) HIP_TRY(hipStreamWaitEvent(main, e->slot_ev[rslot], 0));
+    StepArgs sa = step_args_at(e, c, c0);
+    sa.a.seg_g = e->ring.seg_g + rb * N * e->k.seg_cap * 5;
+    sa.a.seg_n = e->ring.seg_n + rb * N;
+    sa.ma.nsteps = cn;
+    sa.ma.seg_rows = cn > 1 ? cn : 2;  // (> 1: row k of the chunk's lists; a one-step chunk still writes row 0 of them)
+    sa.ma.cam_here = frames ? 0 : 1;
+    sa.ma.pose_rows = frames ? e->ring.pose + rb * N * TC_POSE_ROW : nullptr;
+    // The first chunk's simulate launch overlaps with nothing, so it should be SHORT rather than cheap: it goes through
+    // the one-wavefront-per-env kernel (4096 wavefronts, bound by throughput: ~15 us per step) instead of the grouped
+    // one (512 wavefronts, a latency chain: 13-23 us per step).  20-step call 48.4 -> 47.2 us per step, 128-step calls
+    // 38.2 -> 37.6.  Both kernels read and leave the env's state in the caller's buffers, bit for bit the same.
+    if (c.plan.grouped && !(e->tune.first_per_env && c0 == 0 && piped && nsteps > chunk)) {  // (a one-chunk call: grouped)
+      int rc = launch_envg(e, c.feat, sa, main);
+      if (rc != TC_OK) return rc;
+    } else {
+      hipLaunchKernelGGL(env_kernel_of(e->kvar, !frames, c.feat), dim3(N), dim3(TC_NT), e->k.lds.total, main, sa);
+      HIP_TRY(hipGetLastError());
+    }
+    const bool last_chunk = c0 + cn >= nsteps;
+    if (c.prof && last_chunk) HIP_TRY(hipEventRecord(e->ev[1][c.slot], main));
+    if (!all && !last_chunk) continue;  // only the last step's frame is wanted
+    if (two_fs) fs = (ci & 1) ? e->frame_stream2 : e->frame_stream;
+    const int fsi = fs == e->frame_stream2 ? 1 : 0;
+    if (piped) {
+      HIP_TRY(hipEventRecord(e->sim_ev, main));
+      HIP_TRY(hipStreamWaitEvent(fs, e->sim_ev, 0));
+      used_fs[fsi] = true;
+    }
+    if (c.prof && first_frames && piped) HIP_TRY(hipEventRecord(e->ev[3][c.slot], fs));
+    first_frames = false;
+    RArgs r = make_rargs(e, e->ring.seg_g, e->ring.seg_n, e->k.seg_cap, nullptr, c.flags, 0, all ? sa.ma.roll.obs : nullptr, c.mode == MODE_STEP);
+    // scratch row of the first frame drawn / its step index in the call (position in the blob stream)
+    r.seg_row0 = (int)rb + (all ? 0 : cn - 1);
+    r.noise_row0 = all ? c0 : nsteps - 1;
+    r.obs_row_stride = all ? (long long)N * (long long)e->obs_bytes : 0;
+    const int rows = all ? cn : 1;  // (<= ring_rows <= 16: one grid)
+    if (frames) {
+      FrameArgs fa = frame_args_of(e, c.flags, r, false);
+      // Heaviest frames first.  A dispatch ends with a tail -- the chip half empty while the last workgroups finish, ~36 us
+      // of a 16-step dispatch, a fifth of a 5-step one -- and the dispatcher hands workgroups out in index order, so the
+      // envs are sorted by the draw-list lengths of the last frame row drawn on this stream (tc_order_kernel with one
+      // group: plain descending order): the last workgroups to start are then the cheap, mostly empty frames.
+      // (a re-sort costs ~5 us of the frame stream -- kernel + launch -- so short dispatches, whose tails already overlap on
+      // two streams, re-sort only once per call and otherwise keep the stream's last order)
+      int rc = frame_order_of(e, fsi, fs, rows >= 8 || ci < 2, &fa.order);
+      if (rc != TC_OK) return rc;
+      hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, false), dim3(N, rows), dim3(TC_NT), e->frame_lds, fs, fa);
+      if (e->frame_order[fsi]) e->cost_row[fsi] = e->ring.seg_n + ((size_t)r.seg_row0 + (size_t)rows - 1) * N;
+    } else {
+      hipLaunchKernelGGL(raster_kernel_of(c.thick, c.fmt), dim3(N, rows), dim3(TC_NT), e->r_lds, fs, r);
+    }
+    HIP_TRY(hipGetLastError());
+    if (piped) HIP_TRY(hipEventRecord(e->slot_ev[rslot], fs));
+    {  // (the ring keeps the last TC_RING_SLOTS chunks: remember where their draw-list lengths are)
+      const int w = e->draw_n < TC_RING_SLOTS ? e->draw_n++ : (memmove(e->draw_rows[0], e->draw_rows[1], sizeof(int) * 2 * (TC_RING_SLOTS - 1)), TC_RING_SLOTS - 1);
+      e->draw_rows[w][0] = r.seg_row0;
+      e->draw_rows[w][1] = rows;
+    }
+  }
+  // join the frame stream(s) back; the end-of-frames probe then sits on the caller's stream behind the join
+  if (used_fs[0]) {
+    HIP_TRY(hipEventRecord(e->frames_ev, e->frame_stream));
+    HIP_TRY(hipStreamWaitEvent(main, e->frames_ev, 0));
+  }
+  if (used_fs[1]) {
+    HIP_TRY(hipEventRecord(e->frames_ev2, e->frame_stream2));
+    HIP_TRY(hipStreamWaitEvent(main, e->frames_ev2, 0));
+  }
+  return TC_OK;
+}
+
+// one launch: simulate + raster by the same wavefront
+static int launch_fused(tc_env* e, const Call& c) {
+  const int N = e->k.N;
+  StepArgs sa = step_args_at(e, c, 0);
+  sa.ma.nsteps = c.nsteps;
+  // (component groups that fit the K = 5 register cache: the K = 5 kernel with 16-segment batches, as for the frame kernel --
+  // its simulate stage then walks the map's lane-line nodes in windows of 320 instead of 576)
+  assert(c.fmt != TC_FMT_CLASSES_BITS);  // (plan_call)
+  step_kern_t fk = step_kernel_of(e->kframe == 516 ? 516 : e->kvar, c.thick, c.fmt, c.feat);
+  sa.r = make_rargs(e, e->k.seg_g, e->k.seg_n, e->k.seg_cap, nullptr, c.flags, 0, nullptr, c.mode == MODE_STEP);
+  // covers both stages and the parked state; behind it, up to the size that costs the CU no workgroup, the head of the
+  // frame's draw list (see tc_env_create)
+  const int lds = e->step_lds;
+  sa.a.seg_lds_off = sa.r.seg_lds_off = e->k.lds.total;
+  sa.a.seg_lds_cap = sa.r.seg_lds_cap = e->seg_lds_cap ? (e->step_lds - e->k.lds.total) / 20 : 0;
+  if (sa.a.seg_lds_cap > e->tune.seg_lds_limit) sa.a.seg_lds_cap = sa.r.seg_lds_cap = e->tune.seg_lds_limit;
+  if (e->env_order && c.nsteps == 1) {
+    // every order_every-th step the envs are re-dealt to the workgroups by the draw-list lengths of the step before
+    // (tc_order_kernel: a 1-workgroup launch of a few microseconds on the caller's stream)
+    if (c.mode == MODE_STEP && e->order_calls++ % e->tune.order_every == 0 && e->order_calls > 1) {
+      hipLaunchKernelGGL(tc_order_kernel, dim3(1), dim3(TC_ORDER_NT), (size_t)(N + 15) / 16 * 16, c.main, (const int*)e->k.seg_n, N, e->order_g, e->env_order);
+      HIP_TRY(hipGetLastError());
+    }
+    sa.env_order = e->env_order;
+  }
+  hipLaunchKernelGGL(fk, dim3(N), dim3(TC_NT), lds, c.main, sa);
+  HIP_TRY(hipGetLastError());
+  e->draw_n = -1;
+  // one kernel: its whole duration is reported as the first interval, the second is empty
+  if (c.prof) HIP_TRY(hipEventRecord(e->ev[1][c.slot], c.main));
+  return TC_OK;
+}
+
+// one tc_env_kernel launch, and a tc_raster_kernel launch behind it when frames are drawn
+static int launch_two(tc_env* e, const Call& c) {
+  const int N = e->k.N;
+  const bool do_raster = c.plan.do_raster;
+  StepArgs sa = step_args_at(e, c, 0);
+  sa.ma.nsteps = c.nsteps;
+  sa.ma.cam_here = do_raster ? 1 : 0;
+  // (K steps without observations run on the one-wavefront-per-env kernel: with nothing to share the chip with, its
+  // shorter serial chain wins -- cfg2: 16.5 us per step against 20.7 for the grouped kernel)
+  hipLaunchKernelGGL(env_kernel_of(e->kvar, do_raster, c.feat), dim3(N), dim3(TC_NT), e->k.lds.total, c.main, sa);
+  HIP_TRY(hipGetLastError());
+  if (c.prof) HIP_TRY(hipEventRecord(e->ev[1][c.slot], c.main));
+  if (do_raster) {
+    int rc = launch_raster(e, e->k.seg_g, e->k.seg_n, e->k.seg_cap, c.mode == MODE_RESET ? c.mask : nullptr, c.flags, c.main, 0, N,
+                           c.roll ? c.roll->obs : nullptr, c.mode == MODE_STEP);
+    if (rc != TC_OK) return rc;
+    e->draw_n = -1;
+  }
+  return TC_OK;
+}
+
 static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t* man, const int32_t* spawn,
                   const uint8_t* mask, uint32_t flags, void* stream, int nsteps = 1, const tc_rollout* roll = nullptr,
                   bool ep_rows = false) {
@@ -5472,286 +5723,43 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
     set_err("TC_F_DEVICE_SPAWN needs a table (tc_env_set_spawn_table)");
     return TC_E_INVALID;
   }
-#ifdef TC_TIMING
-  if (g_tstamp && e->k.N > g_tstamp_n) {
-    set_err("timing build: the installed stamp buffer is smaller than this env batch");
-    return TC_E_INVALID;
-  }
-#endif
-  const bool prof = e->prof > 0 && mode == MODE_STEP && (e->prof_calls++ % e->prof) == 0;
-  const int slot = e->prof_n % TC_PROF_RING;
-  const int kv = e->kvar;
-  // per-env cars (tc_env_set_car_per_env) and episodes (tc_env_set_episodes): the instantiations of the simulate stages
-  // with those bits, the same launches otherwise
+  int rc = check_stamp_buffer(e);
+  if (rc != TC_OK) return rc;
   const unsigned feat = (e->cr.rows ? TC_FEAT_CAR : 0u) | (e->ep.length && mode != MODE_RENDER ? TC_FEAT_EP : 0u) |
                         (e->ct.tab && mode == MODE_STEP ? TC_FEAT_CTRL : 0u);  // (the controller: the tc_drive_* entry points)
-  const bool all = roll && roll->obs;  // with a rollout every step's frame is wanted; else only the last survives
-  const CallPlan plan = plan_call(e, flags, nsteps, e->k.b.obs || all, all);
-  const bool do_raster = plan.do_raster;
-  const bool thick = e->k.cam.thickness > 1;
-  const int fmt = e->k.cam.format;
-  const int N = e->k.N;
-  auto args_at = [&](int c0) { return step_args_at(e, mode, cc, cdtype, man, spawn, mask, flags, roll, ep_rows, c0); };
-  hipStream_t main = (hipStream_t)stream;
-  if (plan.split) {
-    // K steps, split form: per chunk ONE simulate launch over its steps and ONE launch over the frames wanted.  The pose
-    // rows / draw lists of a chunk live in slot (chunk index mod TC_RING_SLOTS) of the scratch ring.
-    if (e->ring.rows < 1) {
-      set_err("tc_step_multi with observations needs the scratch ring: call tc_env_reserve_steps(env, n) once before "
-              "(tc_step_multi itself never allocates)");
-      return TC_E_INVALID;
-    }
-    if (prof) HIP_TRY(hipEventRecord(e->ev[0][slot], main));
-    // one stream at a time per handle: a call on another stream than the previous K-step call waits for that call
-    if (e->have_call && e->last_stream != main) HIP_TRY(hipStreamWaitEvent(main, e->call_ev, 0));
-    const bool frames = plan.frames;
-    // Pipelining inside the call.  The steps are issued in chunks: the simulate launch of chunk c+1 runs on the caller's
-    // stream while the frames of chunk c are produced on an internal stream (joined back before the call's work ends
-    // on the caller's stream, so the caller still sees everything complete in stream order).  The two kernels suit
-    // each other: the frame kernel is bound by vector issue, the grouped simulate kernel by latency (512 wavefronts
-    // for 4096 envs), so the second hides in the first's shadow instead of adding its 21 us per step.
-    // (Measured and dropped, DESIGN.md section 4: chunk sizes ramping up 1, 2, 4, ...; a short or half first chunk; other
-    // divisors than 4 for short calls.)
-    const bool piped = plan.piped;
-    const int chunk = plan.steps;
-    hipStream_t fs = piped ? e->frame_stream : main;
-    // Short calls (chunks of fewer than 8 steps): a frame launch of 5 x N workgroups spends a good part of its life
-    // ramping up and draining (5 rows: 34.6 us per row alone, 16 rows: 30.8), and a 20-step call is four of them.  There
-    // the frame launches of consecutive chunks go to two streams alternately -- each still behind its own chunk's
-    // simulate launch -- so that chunk c+1's workgroups fill the slots chunk c's tail leaves empty (cfg3: 8-step call
-    // 66.2 -> 58.3 us per step, 20-step call 46.9 -> 44.0; with chunks of 10 steps it costs 7 %, so longer calls keep one
-    // stream and their frame launches follow one another, as a kernel trace of the default command shows them).
-    const bool two_fs = piped && e->tune.frame_streams == 2 && chunk < 8;
-    bool first_frames = true;
-    bool used_fs[2] = {false, false};
-    e->draw_n = 0;
-    e->draw_base = e->ring.seg_n;
-    // Streamed form (default when every step's frame is wanted).  The chunked pipeline below pays for its structure: the
-    // first chunk's simulate launch overlaps with nothing, and every frame dispatch ends in a tail with the chip half empty
-    // -- a quarter of a 20-step call.  Here the whole call (or a segment of st_rows steps) is ONE simulate launch on the
-    // caller's stream and ONE frame launch of steps x N workgroups on the internal stream that starts right away, beside
-    // it: a frame workgroup polls its pose row until the simulate launch has written it (device-scope loads; every entry
-    // validates itself, tc_frame_kernel).  Only the first step is exposed, and there is one tail per call.
-    //   frame stream: [order kernel] [tc_gate_kernel: until the simulate workgroups are resident] [tc_frame_kernel, gate 1]
-    //                 (wait: simulate launch done) [tc_frame_recover_kernel: whatever a gate-1 workgroup gave up on]
-    // Every wait on the device is bounded (gate_ticks), and what a bound cuts short the recover pass completes: the
-    // result never depends on how the two launches were scheduled.
-    const bool streamed = plan.streamed;
-    if (streamed) {
-      e->draw_base = e->streamed.seg_n;
-      int si = 0;
-      for (int c0 = 0, cn = 0; c0 < nsteps; c0 += cn, si++) {
-        cn = nsteps - c0 < plan.steps ? nsteps - c0 : plan.steps;
-        // a later segment reuses the scratch rows: the frames of the one before must be drawn (and its rows cleared)
-        if (si > 0) HIP_TRY(hipStreamWaitEvent(main, e->slot_ev[0], 0));
-        HIP_TRY(hipEventRecord(e->start_ev, main));
-        StepArgs sa = args_at(c0);
-        sa.a.seg_g = e->streamed.seg_g;
-        sa.a.seg_n = e->streamed.seg_n;
-        sa.ma.nsteps = cn;
-        sa.ma.seg_rows = cn > 1 ? cn : 2;
-        sa.ma.pose_rows = e->streamed.pose;
-        sa.ma.resident = e->st_words;
-        int rc = launch_envg(e, feat, sa, main);
-        if (rc != TC_OK) return rc;
-        if (prof && c0 + cn >= nsteps) HIP_TRY(hipEventRecord(e->ev[1][slot], main));
-        HIP_TRY(hipEventRecord(e->sim_ev, main));
-        // ---- the frame stream
-        HIP_TRY(hipStreamWaitEvent(fs, e->start_ev, 0));
-        // heaviest frames first, by the last row of the call before (see the chunked form below).  Behind the wait: the
-        // call before may have drawn on the CALLER's stream (a call that keeps only its last frame runs its frame kernel
-        // there, reading this very permutation, behind the simulate launch that wrote the costs), so the sort that rewrites
-        // the permutation in place is ordered behind everything the caller's stream did before this call -- and it belongs
-        // to the capture when the call is captured into a graph.  start_ev is recorded ahead of the simulate launch, so the
-        // sort still runs while that launch starts
-        if (e->frame_order[0] && e->cost_row[0]) {
-          hipLaunchKernelGGL(tc_order_kernel, dim3(1), dim3(TC_ORDER_NT), (size_t)(N + 15) / 16 * 16, fs, e->cost_row[0], N, N, e->frame_order[0]);
-          HIP_TRY(hipGetLastError());
-          e->frame_order_valid[0] = true;
-        }
-        RArgs r = make_rargs(e, e->streamed.seg_g, e->streamed.seg_n, e->k.seg_cap, nullptr, flags, 0, sa.ma.roll.obs, mode == MODE_STEP);
-        r.seg_row0 = 0;
-        r.noise_row0 = c0;
-        r.obs_row_stride = (long long)N * (long long)e->obs_bytes;
-        FrameArgs fa = frame_args_of(e, flags, r, true);
-        if (e->frame_order[0] && e->frame_order_valid[0]) fa.order = e->frame_order[0];
-        // (ten times the patience of a frame workgroup: one idle wavefront costs nothing, and when another env's frame
-        // launch has the chip -- two handles stepping on one GPU -- the simulate workgroups only get on as that launch drains)
-        hipLaunchKernelGGL(tc_gate_kernel, dim3(1), dim3(64), 0, fs, (const unsigned int*)e->st_words, envg_grid(N), 10 * e->tune.gate_ticks);
-        HIP_TRY(hipGetLastError());
-        if (prof && si == 0) HIP_TRY(hipEventRecord(e->ev[3][slot], fs));
-        fa.gate = 1;
-        hipLaunchKernelGGL(frame_kernel_of(e->kframe, thick, fmt, false), dim3(N, cn), dim3(TC_NT), e->frame_lds, fs, fa);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamWaitEvent(fs, e->sim_ev, 0));
-        fa.gate = 2;
-        fa.recover_rows = cn;
-        fa.order = nullptr;
-        hipLaunchKernelGGL(frame_kernel_of(e->kframe, thick, fmt, true), dim3(N), dim3(TC_NT), e->frame_lds, fs, fa);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(e->slot_ev[0], fs));
-        if (e->frame_order[0]) e->cost_row[0] = e->streamed.seg_n + (size_t)(cn - 1) * N;
-        used_fs[0] = true;
-        const int keep = cn < 3 * 16 ? cn : 3 * 16;  // the statistics cover the same span as a chunked call's ring
-        e->draw_rows[0][0] = cn - keep;
-        e->draw_rows[0][1] = keep;
-        e->draw_n = 1;
-      }
-    }
-    int ci = 0;
-    for (int c0 = 0, cn = 0; !streamed && c0 < nsteps; c0 += cn, ci++) {
-      cn = nsteps - c0 < chunk ? nsteps - c0 : chunk;
-      const int rslot = ci % TC_RING_SLOTS;
-      const size_t rb = (size_t)rslot * e->ring.rows;   // first row of this chunk in the scratch ring
-      // the frames that read this ring slot TC_RING_SLOTS chunks ago must be done before it is rewritten
-      if (piped && ci >= TC_RING_SLOTS) HIP_TRY(hipStreamWaitEvent(main, e->slot_ev[rslot], 0));
-      StepArgs sa = args_at(c0);
-      sa.a.seg_g = e->ring.seg_g + rb * N * e->k.seg_cap * 5;
-      sa.a.seg_n = e->ring.seg_n + rb * N;
-      sa.ma.nsteps = cn;
-      sa.ma.seg_rows = cn > 1 ? cn : 2;  // (> 1: row k of the chunk's lists; a one-step chunk still writes row 0 of them)
-      sa.ma.cam_here = frames ? 0 : 1;
-      sa.ma.pose_rows = frames ? e->ring.pose + rb * N * TC_POSE_ROW : nullptr;
-      // The first chunk's simulate launch overlaps with nothing, so it should be SHORT rather than cheap: it goes through
-      // the one-wavefront-per-env kernel (4096 wavefronts, bound by throughput: ~15 us per step) instead of the grouped
-      // one (512 wavefronts, a latency chain: 13-23 us per step).  20-step call 48.4 -> 47.2 us per step, 128-step calls
-      // 38.2 -> 37.6.  Both kernels read and leave the env's state in the caller's buffers, bit for bit the same.
-      if (frames && e->tune.env_grouped && !(e->tune.first_per_env && c0 == 0 && piped && nsteps > chunk)) {  // (a one-chunk call: grouped)
-        int rc = launch_envg(e, feat, sa, main);
-        if (rc != TC_OK) return rc;
-      } else {
-        hipLaunchKernelGGL(env_kernel_of(kv, !frames, feat), dim3(N), dim3(TC_NT), e->k.lds.total, main, sa);
-        HIP_TRY(hipGetLastError());
-      }
-      const bool last_chunk = c0 + cn >= nsteps;
-      if (prof && last_chunk) HIP_TRY(hipEventRecord(e->ev[1][slot], main));
-      if (!all && !last_chunk) continue;  // only the last step's frame is wanted
-      if (two_fs) fs = (ci & 1) ? e->frame_stream2 : e->frame_stream;
-      if (piped) {
-        HIP_TRY(hipEventRecord(e->sim_ev, main));
-        HIP_TRY(hipStreamWaitEvent(fs, e->sim_ev, 0));
-        used_fs[fs == e->frame_stream2 ? 1 : 0] = true;
-      }
-      if (prof && first_frames && piped) HIP_TRY(hipEventRecord(e->ev[3][slot], fs));
-      first_frames = false;
-      RArgs r = make_rargs(e, e->ring.seg_g, e->ring.seg_n, e->k.seg_cap, nullptr, flags, 0, all ? sa.ma.roll.obs : nullptr, mode == MODE_STEP);
-      // scratch row of the first frame drawn / its step index in the call (position in the blob stream)
-      r.seg_row0 = (int)rb + (all ? 0 : cn - 1);
-      r.noise_row0 = all ? c0 : nsteps - 1;
-      r.obs_row_stride = all ? (long long)N * (long long)e->obs_bytes : 0;
-      const int rows = all ? cn : 1;  // (<= ring_rows <= 16: one grid)
-      if (frames) {
-        FrameArgs fa = frame_args_of(e, flags, r, false);
-        // Heaviest frames first.  A dispatch ends with a tail -- the chip half empty while the last workgroups finish, ~36 us
-        // of a 16-step dispatch, a fifth of a 5-step one -- and the dispatcher hands workgroups out in index order, so the
-        // envs are sorted by the draw-list lengths of the last frame row drawn on this stream (tc_order_kernel with one
-        // group: plain descending order): the last workgroups to start are then the cheap, mostly empty frames.
-        const int fsi = fs == e->frame_stream2 ? 1 : 0;
-        // (a re-sort costs ~5 us of the frame stream -- kernel + launch -- so short dispatches, whose tails already overlap on
-        // two streams, re-sort only once per call and otherwise keep the stream's last order)
-        if (e->frame_order[fsi] && e->cost_row[fsi] && (rows >= 8 || ci < 2)) {
-          hipLaunchKernelGGL(tc_order_kernel, dim3(1), dim3(TC_ORDER_NT), (size_t)(N + 15) / 16 * 16, fs, e->cost_row[fsi], N, N, e->frame_order[fsi]);
-          HIP_TRY(hipGetLastError());
-          e->frame_order_valid[fsi] = true;
-        }
-        if (e->frame_order[fsi] && e->frame_order_valid[fsi]) fa.order = e->frame_order[fsi];
-        hipLaunchKernelGGL(frame_kernel_of(e->kframe, thick, fmt, false), dim3(N, rows), dim3(TC_NT), e->frame_lds, fs, fa);
-        if (e->frame_order[fsi]) e->cost_row[fsi] = e->ring.seg_n + ((size_t)r.seg_row0 + (size_t)rows - 1) * N;
-      } else {
-        hipLaunchKernelGGL(raster_kernel_of(thick, fmt), dim3(N, rows), dim3(TC_NT), e->r_lds, fs, r);
-      }
-      HIP_TRY(hipGetLastError());
-      if (piped) HIP_TRY(hipEventRecord(e->slot_ev[rslot], fs));
-      {  // (the ring keeps the last TC_RING_SLOTS chunks: remember where their draw-list lengths are)
-        const int w = e->draw_n < TC_RING_SLOTS ? e->draw_n++ : (memmove(e->draw_rows[0], e->draw_rows[1], sizeof(int) * 2 * (TC_RING_SLOTS - 1)), TC_RING_SLOTS - 1);
-        e->draw_rows[w][0] = r.seg_row0;
-        e->draw_rows[w][1] = rows;
-      }
-    }
-    // join the frame stream(s) back; the end-of-frames probe then sits on the caller's stream behind the join
-    if (piped) {
-      if (used_fs[0]) {
-        HIP_TRY(hipEventRecord(e->frames_ev, e->frame_stream));
-        HIP_TRY(hipStreamWaitEvent(main, e->frames_ev, 0));
-      }
-      if (used_fs[1]) {
-        HIP_TRY(hipEventRecord(e->frames_ev2, e->frame_stream2));
-        HIP_TRY(hipStreamWaitEvent(main, e->frames_ev2, 0));
-      }
-    }
-    if (prof) {
-      HIP_TRY(hipEventRecord(e->ev[2][slot], main));
-      e->prof_piped[slot] = piped ? 1 : 0;
-      e->prof_n++;
-    }
-    int rc = noise_advance(e, mode, true, nsteps, stream);
-    if (rc != TC_OK) return rc;
-    HIP_TRY(hipEventRecord(e->call_ev, main));
-    e->last_stream = main;
-    e->have_call = true;
-    return TC_OK;
+  Call c;  // (filled by name: the order of the fields is free to change)
+  c.mode = mode; c.cc = cc; c.cdtype = cdtype; c.man = man; c.spawn = spawn; c.mask = mask; c.flags = flags;
+  c.main = (hipStream_t)stream; c.nsteps = nsteps; c.roll = roll; c.ep_rows = ep_rows; c.feat = feat;
+  c.all = roll && roll->obs;
+  c.thick = e->k.cam.thickness > 1; c.fmt = e->k.cam.format;
+  c.plan = plan_of(e, flags, nsteps, e->k.b.obs || c.all, c.all);
+  c.prof = e->prof > 0 && mode == MODE_STEP && (e->prof_calls++ % e->prof) == 0;
+  c.slot = e->prof_n % TC_PROF_RING;
+  if (c.plan.split && e->ring.rows < 1) {
+    set_err("tc_step_multi with observations needs the scratch ring: call tc_env_reserve_steps(env, n) once before "
+            "(tc_step_multi itself never allocates)");
+    return TC_E_INVALID;
   }
-  if (prof) HIP_TRY(hipEventRecord(e->ev[0][slot], main));
-  // a K-step call that is not split (no observations, one fused launch, two launches) keeps the promise of the split form:
+  // ---- begin
+  if (c.prof) HIP_TRY(hipEventRecord(e->ev[0][c.slot], c.main));
+  // one stream at a time per handle: a K-step call on another stream than the previous K-step call waits for that call.
+  // A K-step call that is not split (no observations, one fused launch, two launches) keeps the promise of the split form:
   // on another stream than the handle's previous K-step call it waits for that call, and it is the next call's predecessor
-  if (nsteps > 1 && e->have_call && e->last_stream != main) HIP_TRY(hipStreamWaitEvent(main, e->call_ev, 0));
-  auto end_call = [&](int rc) -> int {
-    if (rc != TC_OK || nsteps < 2) return rc;
-    HIP_TRY(hipEventRecord(e->call_ev, main));
-    e->last_stream = main;
-    e->have_call = true;
-    return TC_OK;
-  };
-  StepArgs sa = args_at(0);
-  sa.ma.nsteps = nsteps;
-  if (plan.fused) {  // one launch: simulate + raster by the same wavefront
-    // (component groups that fit the K = 5 register cache: the K = 5 kernel with 16-segment batches, as for the frame kernel --
-    // its simulate stage then walks the map's lane-line nodes in windows of 320 instead of 576)
-    assert(fmt != TC_FMT_CLASSES_BITS);  // (plan_call)
-    step_kern_t fk = step_kernel_of(e->kframe == 516 ? 516 : kv, thick, fmt, feat);
-    sa.r = make_rargs(e, e->k.seg_g, e->k.seg_n, e->k.seg_cap, nullptr, flags, 0, nullptr, mode == MODE_STEP);
-    // covers both stages and the parked state; behind it, up to the size that costs the CU no workgroup, the head of the
-    // frame's draw list (see tc_env_create)
-    const int lds = e->step_lds;
-    sa.a.seg_lds_off = sa.r.seg_lds_off = e->k.lds.total;
-    sa.a.seg_lds_cap = sa.r.seg_lds_cap = e->seg_lds_cap ? (e->step_lds - e->k.lds.total) / 20 : 0;
-    if (sa.a.seg_lds_cap > e->tune.seg_lds_limit) sa.a.seg_lds_cap = sa.r.seg_lds_cap = e->tune.seg_lds_limit;
-    if (e->env_order && nsteps == 1) {
-      // every order_every-th step the envs are re-dealt to the workgroups by the draw-list lengths of the step before
-      // (tc_order_kernel: a 1-workgroup launch of a few microseconds on the caller's stream)
-      if (mode == MODE_STEP && e->order_calls++ % e->tune.order_every == 0 && e->order_calls > 1) {
-        hipLaunchKernelGGL(tc_order_kernel, dim3(1), dim3(TC_ORDER_NT), (size_t)(N + 15) / 16 * 16, main, (const int*)e->k.seg_n, N, e->order_g, e->env_order);
-        HIP_TRY(hipGetLastError());
-      }
-      sa.env_order = e->env_order;
-    }
-    hipLaunchKernelGGL(fk, dim3(N), dim3(TC_NT), lds, main, sa);
-    HIP_TRY(hipGetLastError());
-    e->draw_n = -1;
-    if (prof) {  // one kernel: its whole duration is reported as the first interval, the second is empty
-      HIP_TRY(hipEventRecord(e->ev[1][slot], main));
-      HIP_TRY(hipEventRecord(e->ev[2][slot], main));
-      e->prof_n++;
-    }
-    return end_call(noise_advance(e, mode, true, nsteps, stream));
-  }
-  sa.ma.cam_here = do_raster ? 1 : 0;
-  // (K steps without observations run on the one-wavefront-per-env kernel: with nothing to share the chip with, its
-  // shorter serial chain wins -- cfg2: 16.5 us per step against 20.7 for the grouped kernel)
-  hipLaunchKernelGGL(env_kernel_of(kv, do_raster, feat), dim3(N), dim3(TC_NT), e->k.lds.total, main, sa);
-  HIP_TRY(hipGetLastError());
-  if (prof) HIP_TRY(hipEventRecord(e->ev[1][slot], main));
-  if (do_raster) {
-    int rc = launch_raster(e, e->k.seg_g, e->k.seg_n, e->k.seg_cap, mode == MODE_RESET ? mask : nullptr, flags, main, 0, N,
-                           roll ? roll->obs : nullptr, mode == MODE_STEP);
-    if (rc != TC_OK) return rc;
-    e->draw_n = -1;
-  }
-  if (prof) {
-    HIP_TRY(hipEventRecord(e->ev[2][slot], main));
+  if (nsteps > 1 && e->have_call && e->last_stream != c.main) HIP_TRY(hipStreamWaitEvent(c.main, e->call_ev, 0));
+  rc = c.plan.streamed ? launch_streamed(e, c) : c.plan.split ? launch_chunked(e, c) : c.plan.fused ? launch_fused(e, c) : launch_two(e, c);
+  if (rc != TC_OK) return rc;
+  // ---- end
+  if (c.prof) {
+    HIP_TRY(hipEventRecord(e->ev[2][c.slot], c.main));
+    e->prof_piped[c.slot] = c.plan.piped ? 1 : 0;  // (every route: a slot reused by another form must not keep the old flag)
     e->prof_n++;
   }
-  return end_call(noise_advance(e, mode, do_raster, nsteps, stream));
+  rc = noise_advance(e, mode, c.plan.do_raster, nsteps, stream);
+  if (rc != TC_OK || nsteps < 2) return rc;
+  HIP_TRY(hipEventRecord(e->call_ev, c.main));
+  e->last_stream = c.main;
+  e->have_call = true;
+  return TC_OK;
 }
 
 extern "C" int tc_reset(tc_env* e, const int32_t* spawn_nodes, const uint8_t* mask, uint32_t flags, void* stream) {
@@ -5770,6 +5778,7 @@ extern "C" int tc_step_multi(tc_env* e, const void* car_control, int32_t control
                              int32_t n_steps, uint32_t flags, const tc_rollout* rollout, void* stream) {
   if (!e || !maneuver || (control_dtype != TC_F32 && control_dtype != TC_F64) || n_steps < 1) return TC_E_INVALID;
   if (!car_control && !e->ct.tab) return TC_E_INVALID;  // (a built-in controller replaces the action)
+  // (not left to launch(): the row checks below would answer first for an unbound handle whose rows are too short)
   if (!e->bound) {
     set_err("tc_env_bind has not been called");
     return TC_E_UNBOUND;
@@ -5834,7 +5843,7 @@ extern "C" int tc_env_draw_list_stats(tc_env* e, double* mean_segments, double* 
 extern "C" int tc_env_launch_info(const tc_env* e, uint32_t flags, int32_t n_steps, int32_t* fused, int32_t* kvar,
                                   int32_t* steps_per_dispatch, char* name, int32_t name_cap) {
   if (!e) return TC_E_INVALID;
-  const CallPlan p = plan_call(e, flags, n_steps, e->k.b.obs != nullptr, true);  // (every frame wanted)
+  const CallPlan p = plan_of(e, flags, n_steps, e->k.b.obs != nullptr, true);  // (every frame wanted)
   if (fused) *fused = p.fused ? 1 : 0;
   if (kvar) *kvar = (p.fused && e->kframe == 516) ? 5 : e->kvar;  // (the fused kernel of a map with component groups: K = 5)
   if (steps_per_dispatch) *steps_per_dispatch = p.steps;
@@ -5842,8 +5851,8 @@ extern "C" int tc_env_launch_info(const tc_env* e, uint32_t flags, int32_t n_ste
   if (name && name_cap > 0)
     snprintf(name, (size_t)name_cap, "%s",
              p.fused ? (drive ? "tc_drive_step_kernel" : "tc_step_kernel")
-             : p.frames ? (e->tune.env_grouped ? (drive ? "tc_drive_envg_kernel+tc_frame_kernel" : "tc_envg_kernel+tc_frame_kernel")
-                                               : (drive ? "tc_drive_env_kernel+tc_frame_kernel" : "tc_env_kernel+tc_frame_kernel"))
+             : p.grouped ? (drive ? "tc_drive_envg_kernel+tc_frame_kernel" : "tc_envg_kernel+tc_frame_kernel")
+             : p.frames  ? (drive ? "tc_drive_env_kernel+tc_frame_kernel" : "tc_env_kernel+tc_frame_kernel")
              : p.do_raster ? (drive ? "tc_drive_env_kernel+tc_raster_kernel" : "tc_env_kernel+tc_raster_kernel")
                            : (drive ? "tc_drive_env_kernel" : "tc_env_kernel"));
   return TC_OK;
