@@ -21,18 +21,19 @@ _cache = {}
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
-TC_FEAT_CAR, TC_FEAT_EP = 1, 2  # tinycarlo_hip.hip: the feature mask of the kernels that simulate
+TC_FEAT_CAR, TC_FEAT_EP = 1, 2  # k_feat.h: the feature mask of the kernels that simulate
 
 
 @functools.lru_cache(maxsize=None)
-def dev_kernel_resources():
+def dev_kernel_resources(extra=()):
     """The compiler's own figures of every kernel of the -DTC_DEV_FAST build (cfg3's K = 5 variants), cross-compiled to
-    gfx950 assembly once per test run (no GPU needed): {mangled name: (vgpr_count, vgpr_spill_count, scratch bytes)}."""
+    gfx950 assembly once per test run (no GPU needed): {mangled name: (vgpr_count, vgpr_spill_count, scratch bytes)}.
+    extra: a tuple of further compiler flags (("-DTC_DEV_FMTV=2",): the dev set with the packed frame / raster kernels)."""
     import tempfile
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "tc.s")
         cmd = [HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-mllvm", "-disable-machine-licm", "-std=c++17",
-               "-DTC_DEV_FAST", "-S", "--cuda-device-only", "-o", out,
+               "-DTC_DEV_FAST", *extra, "-S", "--cuda-device-only", "-o", out,
                os.path.join(ROOT, "tinycarlo_amd", "csrc", "tinycarlo_hip.hip")]
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL, timeout=600)
         with open(out) as f:

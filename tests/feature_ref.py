@@ -41,7 +41,7 @@ EP_KEYS = ("length", "ret", "count", "last_length", "last_return", "length_sum",
 CAR_COLS = ("wheelbase", "track_width", "max_velocity", "max_steering_angle", "steering_speed", "max_acceleration",
             "max_deceleration")
 S_NOT_RESET, S_TIME_LIMIT = 8, 32
-FEAT_CAR, FEAT_EP, FEAT_CTRL = 1, 2, 4  # TC_FEAT_* of tinycarlo_hip.hip
+FEAT_CAR, FEAT_EP, FEAT_CTRL = 1, 2, 4  # TC_FEAT_* of csrc/k_feat.h
 
 STANLEY_SHIM = r"""
 #include "tc_ctrl.h"

@@ -3,11 +3,8 @@ definition (tinycarlo_amd/packing.py), the argument checks of tc_unpack_bits and
 and the compiler's resource figures of the packed kernels."""
 import copy
 import ctypes as C
-import functools
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -139,27 +136,8 @@ def test_packed_env_shapes_follow(monkeypatch):
     assert plain.obs_packing is None and plain._obs_shape == (plain.n_classes, 62, 96)
 
 
-@functools.lru_cache(maxsize=None)
-def packed_dev_kernel_resources():
-    """common.dev_kernel_resources with -DTC_DEV_FMTV=2: the dev set with the packed frame / raster kernels"""
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "tc.s")
-        cmd = [common.HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-mllvm", "-disable-machine-licm", "-std=c++17",
-               "-DTC_DEV_FAST", "-DTC_DEV_FMTV=2", "-S", "--cuda-device-only", "-o", out,
-               os.path.join(common.ROOT, "tinycarlo_amd", "csrc", "tinycarlo_hip.hip")]
-        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL, timeout=600)
-        with open(out) as f:
-            s = f.read()
-    seen = {}
-    for b in s.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", b).group(1)
-        g = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", b).group(1))  # noqa: E731
-        seen[name] = (g("vgpr_count"), g("vgpr_spill_count"), g("private_segment_fixed_size"))
-    return seen
-
-
 def test_packed_kernels_do_not_spill():
-    seen = packed_dev_kernel_resources()
+    seen = common.dev_kernel_resources(("-DTC_DEV_FMTV=2",))  # the dev set with the packed frame / raster kernels
     # tc_frame_kernel<K, THICK, FMT = 2, RB> and tc_raster_kernel<THICK, FMT = 2>
     frame = [n for n in seen if re.match(r"_Z\d+tc_frame_kernelILi\d+ELb[01]ELi2ELi\d+EEv9FrameArgs$", n)]
     raster = [n for n in seen if re.match(r"_Z\d+tc_raster_kernelILb[01]ELi2EEv5RArgs$", n)]

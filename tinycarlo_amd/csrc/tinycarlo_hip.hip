@@ -2,15 +2,29 @@
 //
 // Build (csrc/Makefile): hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -shared
 //
-// One tc_step = two launches, one 64-lane wavefront (= one workgroup) per env in both:
-//   tc_env_kernel<K>      phase A  kinematics + lanepath tracking + CTE/heading   (car.py:70-148, 46-53)
-//                         phase B  nearest lane-line edge per layer + distance    (layer.py:33-44, car.py:55-64)
-//                         phase C  camera: transform -> 4 clip passes -> project -> visibility -> draw list
-//                                  (camera.py:52-110), handed over through a small global buffer
-//   tc_raster_kernel<..>  cv2.polylines of the draw list into LDS bit-planes (renderer.py:36-51), expanded to
-//                         uint8 and stored with 16-byte-per-lane coalesced stores (zeros included: a class-mask
-//                         frame is written exactly once)
-#include <hip/hip_runtime.h>
+// What the kernel stages share lives in device-only headers included below in a fixed order
+// (k_*.h; the tc_*.h beside them are plain arithmetic that the tests also build with the host compiler):
+//   k_probe.h    timing / marker probes and the ablation switches (in no shipped kernel)
+//   k_common.h   LDS layout, the env's LiveLds record, KArgs / MultiArgs, wavefront helpers
+//   k_feat.h     reward / termination terms, per-env cars, camera bank, episodes, controller (the FEAT template mask)
+// The kernel stages follow in this file, each with its own argument block (RArgs, StepArgs, FrameArgs, NArgs), then the
+// host side (from `// Host side: C ABI` down):
+//   camera       phase C  transform -> 4 clip passes -> project -> visibility -> draw list (camera.py:52-110)
+//   simulate     phase A  kinematics + lanepath tracking + CTE/heading   (car.py:70-148, 46-53)
+//                phase B  nearest lane-line edge per layer + distance    (layer.py:33-44, car.py:55-64)
+//                tc_env_kernel<K, CAM, FEAT>: one 64-lane wavefront (= one workgroup) per env;
+//                tc_envg_kernel<FEAT>: the same two phases for K-step calls, 8 lanes per env
+//   raster       tc_raster_kernel<..>: cv2.polylines of the draw list into LDS bit-planes (renderer.py:36-51), expanded to
+//                uint8 and stored with 16-byte-per-lane coalesced stores (zeros included: a class-mask frame is written
+//                exactly once)
+//   frame        tc_frame_kernel<..>: camera + raster of one (step, env) frame per workgroup, from the pose the simulate
+//                launch left; tc_step_kernel<..>: simulate + camera + raster of an env in one launch
+//   noise        tc_noise_kernel: NoiseObservationWrapper over a finished observation
+//   others       tc_order_kernel, tc_gate_kernel, tc_unpack_bits_kernel
+//   tables       the instantiation lists of the parts (TC_PART) and the *_kernel_of tables
+// Which of these kernels a call launches -- one fused tc_step_kernel, or a simulate launch with tc_frame_kernel behind or
+// beside it, or a simulate launch with the camera stage and tc_raster_kernel behind it -- is plan_call()'s choice (tc_plan.h).
+//
 // TC_PART: the default library is this file compiled as six translation units side by side (Makefile), because one
 // compiler process over every kernel takes ~25 minutes: part 0 = the host code and every kernel but those of the other
 // parts, parts 1 / 3 = the tc_drive_step_kernel family (class masks / rgb), parts 4 / 5 = the tc_step_kernel family (class
@@ -19,14 +33,8 @@
 // `extern template`, so its kernel tables (step_kernel_of, ...) take the addresses without compiling the bodies.  Every
 // kernel is compiled from the same text with the same flags as in a one-unit build (TC_PART undefined: make dev, make
 // timing).  The lists of instantiations are TC_INST_* below and follow Kcodes / Thicks / Fmts / FrameFmts / DriveFeats.
-#if defined(TC_PART) && defined(TC_DEV_FAST)
-#error "the development builds are one translation unit"
-#endif
-#if defined(TC_PART) && TC_PART > 0
-#define TC_PLAIN_KERNEL static  // (kernels that are no templates live in part 0)
-#else
-#define TC_PLAIN_KERNEL
-#endif
+// (TC_PLAIN_KERNEL, which keeps the kernels that are no templates in part 0, is defined in k_common.h.)
+#include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -43,607 +51,9 @@
 #include "tc_clip.h"
 #include "tc_cull.h"
 
-// Timing build only (make timing -> libtinycarlo_hip_timing.so, used by tools/phase_clock.py): every wavefront stores
-// the shader clock at its phase boundaries.  The shipped library is compiled without TC_TIMING and contains none of it.
-#if defined(TC_TIMING) && defined(TC_TIMING_LOOP)
-// variant of the timing build (make dev-timing-loop): no phase probes, only the period of every step of a K-step launch
-// (slot k = clocks from the top of step k-1 to the top of step k, k < 32; slot 0 = launch entry -> top of step 0)
-__device__ long long* tc_tstamp = nullptr;
-#define TSTAMP(i) \
-  do {            \
-  } while (0)
-#define TSTAMP_REAL(i) \
-  do {                 \
-  } while (0)
-#define TSTAMP_LOOP(k, nsteps, tprev)                                                      \
-  do {                                                                                     \
-    long long _t = clock64();                                                              \
-    long long* _tp = tc_tstamp;                                                            \
-    if (_tp && threadIdx.x == 0 && (k) < 31) _tp[(size_t)env * 32 + (k)] = _t - (tprev);  \
-    (tprev) = _t;                                                                          \
-  } while (0)
-#define TSTAMP_END(tprev)                                                                  \
-  do {                                                                                     \
-    long long* _tp = tc_tstamp;                                                            \
-    if (_tp && threadIdx.x == 0) {                                                         \
-      _tp[(size_t)env * 32 + 31] = clock64() - (tprev);                                    \
-      _tp[(size_t)env * 32 + 30] = (long long)(unsigned)__builtin_amdgcn_s_getreg(63492) | /* HW_REG_HW_ID */ \
-                                   ((long long)(unsigned)__builtin_amdgcn_s_getreg(63508) << 32); /* XCC_ID */ \
-    }                                                                                      \
-  } while (0)
-#elif defined(TC_TIMING) && defined(TC_TIMING_LDS)
-// Variant for the frame / step kernels (make dev-timing-lds): the stamps go to 256 bytes of LDS -- no vector-memory
-// operation, nothing drained -- and one lane copies them out when the frame is done.  A stamp written with a global store
-// (the variant below) puts that store's round trip into the NEXT s_waitcnt vmcnt(0) of the wavefront, i.e. the probes
-// themselves create the longest "phase" of a wavefront that otherwise has no store in flight; this variant shows the
-// latencies the shipped kernel has.  (s_memtime returns through the scalar-memory counter, so a stamp still waits for the
-// LDS queue: almost every probe sits behind an lds_sync anyway.)
-__device__ long long* tc_tstamp = nullptr;  // [N][32]
-__shared__ long long tc_ts_lds[32];
-#define TSTAMP(i)                                              \
-  do {                                                         \
-    if (threadIdx.x == 0) tc_ts_lds[(i)] = clock64();          \
-  } while (0)
-#define TSTAMP_REAL(i)                                         \
-  do {                                                         \
-    if (threadIdx.x == 0) tc_ts_lds[(i)] = wall_clock64();     \
-  } while (0)
-#define TSTAMP_LOOP(k, nsteps, tprev) \
-  do {                                \
-  } while (0)
-#define TSTAMP_END(tprev) \
-  do {                    \
-  } while (0)
-#define TSTAMP_DUMP(env_)                                                                  \
-  do {                                                                                     \
-    long long* _tp = tc_tstamp;                                                            \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                     \
-    if (_tp && threadIdx.x < 32) _tp[(size_t)(env_) * 32 + threadIdx.x] = tc_ts_lds[threadIdx.x]; \
-  } while (0)
-#define TSTAMP_CLEAR()                                         \
-  do {                                                         \
-    if (threadIdx.x < 32) tc_ts_lds[threadIdx.x] = 0;          \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         \
-  } while (0)
-#elif defined(TC_TIMING)
-__device__ long long* tc_tstamp = nullptr;  // [N][32]
-// (outstanding memory operations are drained first, so a phase is charged with the latencies it started)
-#define TSTAMP(i)                                                                          \
-  do {                                                                                     \
-    long long* _tp = tc_tstamp;                                                            \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                            \
-    if (_tp && threadIdx.x == 0) _tp[(size_t)env * 32 + (i)] = clock64();                  \
-  } while (0)
-// the constant 100 MHz counter next to the shader clock: (stamp 13 - stamp 0) / (stamp 31 - stamp 30) x 100 MHz is the
-// clock the chip actually holds while the kernel runs
-// loop period of the step loop: slot 28 = clocks from the top of the previous step to the top of the last one
-#define TSTAMP_LOOP(k, nsteps, tprev)                                                      \
-  do {                                                                                     \
-    long long _t = clock64();                                                              \
-    long long* _tp = tc_tstamp;                                                            \
-    if (_tp && threadIdx.x == 0 && (k) == (nsteps)-1 && (k) > 0) _tp[(size_t)env * 32 + 28] = _t - (tprev); \
-    (tprev) = _t;                                                                          \
-  } while (0)
-#define TSTAMP_REAL(i)                                                                     \
-  do {                                                                                     \
-    long long* _tp = tc_tstamp;                                                            \
-    if (_tp && threadIdx.x == 0) _tp[(size_t)env * 32 + (i)] = wall_clock64();            \
-  } while (0)
-#define TSTAMP_END(tprev) \
-  do {                    \
-  } while (0)
-#elif defined(TC_MARKERS)
-// tools/kernel_stats.py --sections: the probes become assembler comments, so that the static instruction mix between two
-// probes can be read off the compiler's output (no code is emitted for them)
-#define TC_STR2(x) #x
-#define TC_STR(x) TC_STR2(x)
-#define TSTAMP(i) asm volatile("; @@TS " TC_STR(i) ::: "memory")
-#define TSTAMP_REAL(i) \
-  do {                 \
-  } while (0)
-#define TSTAMP_LOOP(k, nsteps, tprev) \
-  do {                                \
-  } while (0)
-#define TSTAMP_END(tprev) \
-  do {                    \
-  } while (0)
-#else
-#define TSTAMP(i) \
-  do {            \
-  } while (0)
-#define TSTAMP_REAL(i) \
-  do {                 \
-  } while (0)
-#define TSTAMP_LOOP(k, nsteps, tprev) \
-  do {                                \
-  } while (0)
-#define TSTAMP_END(tprev) \
-  do {                    \
-  } while (0)
-#endif
-#ifndef TSTAMP_DUMP
-#define TSTAMP_DUMP(env_) \
-  do {                    \
-  } while (0)
-#define TSTAMP_CLEAR() \
-  do {                 \
-  } while (0)
-#endif
-// finer section marks for tools/kernel_stats.py --sections (nothing in any other build)
-#ifdef TC_MARKERS
-#define MARK(name) asm volatile("; @@MK " name ::: "memory")
-#else
-#define MARK(name) \
-  do {             \
-  } while (0)
-#endif
-
-#define TC_PROF_RING 64
-#define TC_RING_SLOTS 3  // chunks of a K-step call whose pose rows / draw lists exist at once (tc_env_reserve_steps)
-#define MODE_STEP 0
-#define MODE_RESET 1
-#define MODE_RENDER 2
-
-// ablation switches for profiling (not part of the ABI contract; results are wrong when set)
-#define DBG_SKIP_RASTER 0x100u
-#define DBG_SKIP_STORE 0x200u
-#define DBG_SKIP_CAMERA 0x400u
-#define DBG_SKIP_DIST 0x800u
-#define DBG_SKIP_R2 0x1000u
-#define DBG_SKIP_R3 0x2000u
-#define DBG_SKIP_R4 0x4000u
-#define DBG_SKIP_EVENTS 0x10000u
-#define DBG_SKIP_LINESETUP 0x20000u
-#define DBG_SKIP_SLOPE 0x40000u
-#define DBG_SKIP_QUAD 0x80000u
-#define DBG_SKIP_CLIP 0x100000u
-#define DBG_SKIP_DRAWLIST 0x200000u
-// not an ablation switch: set by make_rargs in RArgs.flags when ThickLine needs only its two long outline edges
-// (tc_short_edges_skip of tc_line.h holds for the camera and TC_SHORT_EDGES is 0); never part of a caller's flags
-#define R_F_LONG_EDGES 0x40000000u
-// the kernels test them only in the ablation build (make dev-ablate): in the shipped library every test folds to false,
-// so the switches cost no scalar registers there (they were ~25 live conditions at the head of the raster stage)
-#ifdef TC_ABLATE
-#define DBG_ON(word, f) (((word) & (f)) != 0)
-#else
-#define DBG_ON(word, f) false
-#endif
-
-// Every workgroup of the stage kernels is ONE wavefront, and the LDS executes a wavefront's operations in program order:
-// between phases that hand data from lane to lane through LDS nothing has to be waited for except the LDS queue itself
-// (and the compiler kept from moving memory operations across).  __syncthreads() would also drain the vector-memory
-// counter -- the frame's stores still in flight at the end of a band, the next batch's draw-list loads.
-// The same goes for the simulate stage: a wait for vmcnt there would sit out the round trip of the step's rollout-row /
-// pose-row stores (vector-memory operations retire in issue order).
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// A reference into the kernel-argument segment, passed through an empty asm: the compiler can no longer tell that two
-// reads go to the same block, so values loaded behind this point are not merged with (and kept alive from) earlier
-// loads, nor hoisted out of the loop the call sits in -- they are s_load'ed where they are used.
-template <class T>
-__device__ __forceinline__ const T& kernarg_again(const T& r) {
-  unsigned long long p = (unsigned long long)&r;
-  asm volatile("" : "+s"(p));
-  return *(const T*)(const __attribute__((address_space(4))) T*)p;
-}
-
-// Segments rasterised per batch: 32 (64 * 106 bytes of tables per workgroup), or 16 in the kernels of the big-map
-// variants (K >= 8: knuffingen), where the tables' 6.6 KB are what decides how many workgroups a CU holds.
-#define RB_MAX 32
-#define RB_OF_K(K) ((K) >= 8 ? 16 : 32)
-// raster-stage LDS layout (compile-time: folds into instruction offsets and frees SGPRs)
-#define R_OFF_TAB 0
-#define R_TAB_BYTES_OF(RB) (((RB) * 4 * 5 + (RB) * 4 + 5 * (RB) + 8 * (RB)) * 4 + 2 * 4 * (RB) * 8)
-#define R_OFF_BITS_OF(RB) ((R_TAB_BYTES_OF(RB) + 15) / 16 * 16)
-#define LCH 8        // outline steps per chunk
-
-#define TC_MAX_GROUPS 8
-struct LdsLayout {
-  int off_p, off_flg, off_list, off_cnt;
-  int total;
-  int off_live;  // tc_step_multi: the env's state between two steps (beyond both stages' buffers, never aliased)
-};
-
-// The env's state and step outputs live in this LDS record for the whole launch: live_in() fills it from the caller's
-// buffers, every step reads and rewrites it (one wavefront, program order), live_out() stores it back.  The step body
-// therefore has ONE form whether it is the only step of a launch (tc_step) or one of many (tc_step_multi), and the
-// raster stage keeps none of it in registers.
-struct LiveLds {
-  double d[10];  // x, y, theta, velocity, steering, radius, front_x, front_y, cos(theta), sin(theta)
-  double cte, he, reward;
-  double dist[TC_MAX_LAYERS];
-  int lp[8];
-  int lp_len, last_maneuver;
-  int have_trig;    // d[8], d[9] hold cos / sin of d[2] (set by every update of the front axle)
-  int needs_reset;  // TC_F_AUTORESET: re-spawn at the start of the next step
-  int cursor;       // spawn_cursor: re-spawns of this env so far
-  int cursor0;      // its value in the caller's buffer (stored back only when it changed)
-  int trunc, status, terminated;
-  int ep_len;  // running episode's length (tc_env_set_episodes; touched by the TC_FEAT_EP kernels only)
-  int cam_idx;  // the env's camera of the bank (tc_env_set_camera_bank; touched only while one is installed)
-  int pad;
-  int cnt[TC_MAX_TERMS];  // steps_true of the consecutive-step terms
-  int ne[TC_MAX_LAYERS];
-  double ep_ret;  // running episode's return (likewise)
-};
-#define TC_LIVE_BYTES 416
-static_assert(sizeof(LiveLds) <= TC_LIVE_BYTES, "LiveLds must fit its LDS slot");
-
-// per-step rollout outputs of tc_step_multi, already advanced to the current step (each [N] or NULL)
-struct RollStep {
-  double *reward, *cte, *heading_error;
-  unsigned char *terminated, *truncated;
-  int* status;
-  double *x, *y, *theta, *velocity;
-  double* dist;  // [N][C]
-  int* ne;       // [N][C]
-  int* lp;       // [N][8]
-  int* lp_len;
-  size_t row0;   // first row of the step in the [K][N] arrays above (k * N)
-};
-
-struct KArgs {
-  DevMap m;
-  DevCar car;
-  DevCam cam;
-  tc_buffers b;
-  LdsLayout lds;
-  int N;
-  int env0;    // first env of this launch (a step may be issued as several sub-batches)
-  // optional camera rows (NULL: cam.E / cam.K for every env): one per env ([N][12] / [N][9], tc_env_set_camera_per_env: row
-  // = env), or a bank of cameras ([count][12] / [count][9], tc_env_set_camera_bank: row = the index that travels with the
-  // (step, env), see CamBank)
-  const double* cam_E;
-  const double* cam_K;
-  int* seg_g;  // [N][seg_cap][5] draw list of the current frame (library owned)
-  int* seg_n;  // [N]
-  int seg_cap;
-  const tc_term* terms;  // device table [TC_MAX_TERMS] (library owned); reward / termination wrappers
-  int n_terms;
-  int* term_counters;    // [N][TC_MAX_TERMS] (caller owned)
-  // camera layer groups: phase C handles lane-line layers grp_layer[g] .. grp_layer[g+1]-1 together (camera.py's
-  // per-layer loop makes the layers independent); the LDS node buffer holds cap_nodes nodes, the largest group
-  // Group g = nodes grp_n0[g] .. grp_n0[g+1]-1 and edges grp_e0[g] .. grp_e0[g+1]-1, whose layers are grp_l0[g] ..
-  // grp_l1[g]-1.  Either whole layers of the map's own arrays (cam_nodes == NULL), or -- maps that need groups -- whole
-  // CONNECTED COMPONENTS of the lane-line graph in the env's camera copy of the map (cam_nodes / cam_edges_g: the same
-  // nodes and edges, every layer's edges still contiguous and in their original relative order, components side by
-  // side): camera.py moves a node only along its own edges, so components are as independent as layers are, and a
-  // group no longer has to hold the largest layer (knuffingen: 517 nodes) -- see tc_env_create.
-  int n_grp;
-  int grp_layer[TC_MAX_GROUPS + 1];
-  int grp_n0[TC_MAX_GROUPS + 1], grp_e0[TC_MAX_GROUPS + 1];
-  int grp_l0[TC_MAX_GROUPS], grp_l1[TC_MAX_GROUPS];
-  const double2* cam_nodes;
-  const int2* cam_edges_g;
-  int cap_nodes;
-  const int* spawn_tab;  // TC_F_DEVICE_SPAWN: spawnable candidate nodes (library owned), spawn_n > 0 entries
-  int spawn_n;
-  unsigned long long spawn_seed;
-  unsigned int dbg;  // DBG_* ablation switches for the camera stage of tc_frame_kernel (0 in every other launch)
-  // tc_frame_kernel: the first seg_lds_cap entries of the frame's draw list stay in LDS (byte offset seg_lds_off of the
-  // workgroup's block, behind both stages' buffers) instead of going through global memory; 0 in every other launch
-  int seg_lds_off, seg_lds_cap;
-  int clip_merge;  // TC_CLIP_MERGE: 1 = a pair of clip passes runs as one pass where tc_clip.h allows it, 0 = always four
-  // Whole-frame cull (tc_cull.h).  frame_cull: TC_FRAME_CULL, and the map has a table, and the shared camera a cover (never
-  // with per-env cameras: the cover is the shared camera's); cull_tab: header + cells (library owned, camera independent)
-  int frame_cull;
-  const unsigned char* cull_tab;
-  TcCullCover cull;
-};
-
-// ---------------------------------------------------------------------------------------------
-// Reward / termination wrappers (tinycarlo/wrapper/*.py) as an epilogue of the step.  Every lane runs the same
-// scalar code; dist_l is lane l's laneline distance (lanes >= C hold 0) and is broadcast layer by layer so that
-// the additions happen in the dict order of info["laneline_distances"] (env.py:85, reward.py:20,40).
-__device__ inline double d_linear_reward(double x, double max_x, double max_reward, double min_reward) {
-  double y = (-max_reward / max_x) * tc_fabs(x) + max_reward;  // utils.py:33
-  if (max_reward > 0) return (min_reward > y) ? min_reward : y;  // python max(y, min_reward)
-  return (min_reward < y) ? min_reward : y;                      // python min(y, min_reward)
-}
-
-// value of lane `l` (wave-uniform index): v_readlane instead of a shuffle through the LDS crossbar
-__device__ __forceinline__ double d_readlane(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-
-// wave-uniform value as something the compiler knows to be uniform (first active lane's copy, held in SGPRs)
-__device__ __forceinline__ int uni_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ double uni_d(double v) {
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Per-env features of the simulate stages: ONE template parameter (FEAT, a mask of these bits) of sim_body and of the
-// three kernels that simulate -- tc_step_kernel<.., FEAT>, tc_env_kernel<.., FEAT>, tc_envg_kernel<FEAT>; a kernel trace
-// shows the mask as a number (tc_envg_kernel<3u>: both).  launch() sets the bits of a call (`feat`).
-//   bit              compiles in                                                           reads
-//   TC_FEAT_CAR (1)  car constants from the env's row, re-drawn at every re-spawn          StepArgs::cr
-//   TC_FEAT_EP  (2)  episode length / return / time limit and the finished-episode sums    StepArgs::ep
-//   TC_FEAT_CTRL (4) the action computed on the device by the built-in controller           StepArgs::ct
-// A kernel without a bit contains none of that feature's code and compiles as if the feature did not exist.
-// The masks with TC_FEAT_CTRL are instantiations of three entry points of their own over the same bodies --
-// tc_drive_step_kernel, tc_drive_env_kernel, tc_drive_envg_kernel (masks 4-7) -- so the twelve-plus-four kernels of masks
-// 0-3 keep their names and their number, and a kernel trace tells a closed-loop call from an open-loop one by name.
-enum : unsigned { TC_FEAT_CAR = 1, TC_FEAT_EP = 2, TC_FEAT_ALL = TC_FEAT_CAR | TC_FEAT_EP, TC_FEAT_CTRL = 4 };
-
-// ---------------------------------------------------------------------------------------------
-// Per-env car constants (tc_env_set_car_per_env): row [env][TC_CAR_NP] of a caller-owned device buffer replaces the
-// shared car's wheelbase, track width and limits; T and the two presence flags stay shared.  Only the TC_FEAT_CAR kernels
-// (the PER instantiations of the simulate stages, chosen at launch) read it: the shared-car kernels compile as before.
-// With tc_env_set_car_randomization, every re-spawn draws the masked columns of the env's next episode first
-// (tc_car_stream / tc_car_draw, tc_rng.h) and writes them back to the row, so the row always holds the constants in force.
-struct CarDrawTab {  // library owned, updated in place by tc_env_set_car_randomization (a captured graph sees new ranges)
-  double lo[TC_CAR_NP], hi[TC_CAR_NP];
-  unsigned long long seed;
-  unsigned int mask, env_offset;  // mask 0: no resampling
-};
-struct CarRows {
-  double* rows;           // [N][TC_CAR_NP] (caller owned)
-  const CarDrawTab* tab;  // NULL: no resampling
-  int* episode;           // [N] episodes drawn so far (caller owned)
-};
-typedef const __attribute__((address_space(4))) CarDrawTab* CarDrawTabConst;  // never written by a kernel: scalar loads
-
-// a constant of the env's row, read where it is used (UNI: the env is wave-uniform, the value goes to SGPRs)
-template <bool UNI>
-__device__ __forceinline__ double car_ld(const double* row, int j) {
-  return UNI ? uni_d(row[j]) : row[j];
-}
-// the env's car: shared T and presence flags, the rest from its row (unused loads are dropped by the compiler)
-template <bool UNI>
-__device__ __forceinline__ DevCar car_of(const DevCar& shared, const double* row) {
-  DevCar c = shared;
-  c.wheelbase = car_ld<UNI>(row, TC_CAR_WHEELBASE);
-  c.track_width = car_ld<UNI>(row, TC_CAR_TRACK_WIDTH);
-  c.max_velocity = car_ld<UNI>(row, TC_CAR_MAX_VELOCITY);
-  c.max_steering_angle = car_ld<UNI>(row, TC_CAR_MAX_STEERING_ANGLE);
-  c.steering_speed = car_ld<UNI>(row, TC_CAR_STEERING_SPEED);
-  c.max_acceleration = car_ld<UNI>(row, TC_CAR_MAX_ACCELERATION);
-  c.max_deceleration = car_ld<UNI>(row, TC_CAR_MAX_DECELERATION);
-  return c;
-}
-// A re-spawn of env `env` (before d_reset): the masked columns of its next episode's row, and the episode counter.  The
-// writer stores them; every lane that reads the row later is of the same wavefront (stores and loads in program order).
-template <bool UNI>
-__device__ __forceinline__ void car_respawn(const CarRows& cr, int env, bool writer) {
-  if (!cr.tab) return;
-  const CarDrawTabConst t = (CarDrawTabConst)(unsigned long long)cr.tab;
-  const unsigned int mask = t->mask;
-  if (mask == 0) return;
-  const int ep = UNI ? uni_i(cr.episode[env]) : cr.episode[env];
-  const uint64_t z = tc_car_stream(t->seed, (uint32_t)(t->env_offset + (unsigned int)env), (uint32_t)ep);
-  double* row = cr.rows + (size_t)env * TC_CAR_NP;
-#pragma unroll
-  for (int j = 0; j < TC_CAR_NP; j++)
-    if ((mask >> j) & 1u) {
-      const double v = tc_car_draw(z, j, t->lo[j], t->hi[j]);
-      if (writer) row[j] = v;
-    }
-  if (writer) cr.episode[env] = ep + 1;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Camera bank (tc_env_set_camera_bank): KArgs::cam_E / cam_K hold `count` cameras, each env an index into them that every
-// re-spawn re-draws (tc_camera_index, tc_rng.h).  E is consumed where the pose row is formed, K later by the frame stage --
-// in a K-step call possibly after the env has re-spawned again -- so the index in force at a step travels with that
-// (step, env): entry 12 of its pose row (or a register, where the same wavefront draws the frame).  A run-time branch on
-// TC_FI_CAM_BANK in every simulate kernel (no instantiation of its own, as cam_E is); the frame kernels branch on FrameArgs::bank.
-// Set by the library in StepArgs::flags of every launch while a bank is installed: the kernels branch on this bit of a word
-// they hold anyway instead of fetching a pointer of their argument block per step to test it (never taken from the caller).
-#define TC_FI_CAM_BANK 0x80000000u
-struct CamDrawTab {  // library owned, updated in place by tc_env_set_camera_bank (a captured graph sees new settings)
-  unsigned long long seed;
-  unsigned int count, env_offset;
-};
-struct CamBank {
-  int* index;             // [N] the camera each env uses now (caller owned); NULL: no bank (TC_FI_CAM_BANK clear)
-  int* rows;              // [K][N] the index in force at each step of a K-step call, first row of this launch; or NULL
-  int* episode;           // [N] cameras drawn so far (caller owned)
-  const CamDrawTab* tab;
-};
-typedef const __attribute__((address_space(4))) CamDrawTab* CamDrawTabConst;  // never written by a kernel: scalar loads
-// an index as read from memory, kept inside the bank whatever the caller's buffer holds
-__device__ __forceinline__ int cam_clamp(const CamBank& cb, int idx) {
-  const unsigned int last = ((CamDrawTabConst)(unsigned long long)cb.tab)->count - 1u;
-  return (int)((unsigned int)idx < last ? (unsigned int)idx : last);
-}
-// A re-spawn of env `env`: the camera of its next episode.  The writer stores index and counter (as car_respawn does).
-template <bool UNI>
-__device__ __forceinline__ int cam_respawn(const CamBank& cb, int env, bool writer) {
-  const CamDrawTabConst t = (CamDrawTabConst)(unsigned long long)cb.tab;
-  const int ep = UNI ? uni_i(cb.episode[env]) : cb.episode[env];
-  const int idx = (int)tc_camera_index(t->seed, (uint32_t)(t->env_offset + (unsigned int)env), (uint32_t)ep, t->count);
-  if (writer) {
-    cb.index[env] = idx;
-    cb.episode[env] = ep + 1;
-  }
-  return idx;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Episode time limit and per-env episode statistics (tc_env_set_episodes).  Only the TC_FEAT_EP kernels (the EP instantiations
-// of the simulate stages, chosen at launch) touch any of this: every other kernel compiles as before.  Per env and step:
-//   re-spawned in this step (tc_reset, autoreset)  length = 0, ret = 0.0, nothing else
-//   TC_S_NOT_RESET                                 left alone
-//   else  length += 1; limit > 0 && length >= limit: truncated = 1, status |= TC_S_TIME_LIMIT   (ep_count, every lane)
-//         ret = ret + reward, with the step's FINAL reward: one double add per step, in step order
-//         terminated | truncated: last_* = (length, ret), count += 1, *_sum += (length, ret)   (ep_close, one lane)
-// length / ret stay on chip across the steps of a launch (LiveLds, or registers in the grouped kernel) and go back to the
-// caller's buffers once; the finished-episode statistics are rare and go straight to memory.
-struct EpArgs {
-  int* length;           // [N] caller owned, as are the next seven
-  double* ret;
-  int* count;            // (count .. return_sum: each may be NULL)
-  int* last_length;
-  double* last_return;
-  long long* length_sum;
-  double* return_sum;
-  const int* limit;      // [N] per-env limit, or NULL: *shared
-  const int* shared;     // library owned, updated in place by tc_env_set_episodes (a captured graph sees a new limit)
-  int* len_rows;         // [K][N] rows of a K-step call (tc_env_set_episode_rollout), first row of this launch; or NULL
-  double* ret_rows;
-};
-typedef const __attribute__((address_space(4))) int* EpIntConst;  // never written by a kernel: scalar load
-// first half, before truncated / status are stored: the length, and the time limit (gymnasium TimeLimit: whatever
-// `terminated` turns out to be).  Every lane that works on the env runs it, so truncated stays uniform among them.
-template <bool UNI>
-__device__ __forceinline__ void ep_count(const EpArgs& ep, int env, bool fresh, int& len, int& trunc, int& status) {
-  if (fresh) {
-    len = 0;
-    return;
-  }
-  if (status & TC_S_NOT_RESET) return;
-  len += 1;
-  const int lim = ep.limit ? (UNI ? uni_i(ep.limit[env]) : ep.limit[env]) : *(EpIntConst)(unsigned long long)ep.shared;
-  if (lim > 0 && len >= lim) {
-    trunc = 1;
-    status |= TC_S_TIME_LIMIT;
-  }
-}
-// second half, by the one lane that stores the env's outputs, once reward / terminated are final; row: (step, env) of
-// the launch's per-step rows
-__device__ __forceinline__ void ep_close(const EpArgs& ep, int env, size_t row, bool fresh, int status, int len, double& ret,
-                                         double reward, int done) {
-  if (fresh) {
-    ret = 0.0;
-  } else if (!(status & TC_S_NOT_RESET)) {
-    ret = ret + reward;
-    if (done) {
-      if (ep.last_length) ep.last_length[env] = len;
-      if (ep.last_return) ep.last_return[env] = ret;
-      if (ep.count) ep.count[env] += 1;
-      if (ep.length_sum) ep.length_sum[env] += (long long)len;
-      if (ep.return_sum) ep.return_sum[env] = ep.return_sum[env] + ret;
-    }
-  }
-  if (ep.len_rows) ep.len_rows[row] = len;
-  if (ep.ret_rows) ep.ret_rows[row] = ret;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Built-in controller (tc_env_set_controller, tc_ctrl.h).  Only the TC_FEAT_CTRL kernels (the tc_drive_* entry points,
-// chosen at launch) touch any of this: every other kernel compiles as before.  Per env and step the action is
-//   (speed, tc_ctrl_stanley(cte, he, k, speed, max_steering_angle) + noise[k][env])
-// with cte / he as the env reported them after its previous step (the bound buffers at the first step of a launch, 0 / 0
-// after a re-spawn), max_steering_angle the env's own (its car row under TC_FEAT_CAR), and car_control is never read.
-// The command before noise goes to rows[k][env] / last[env]; a step that applies no action (re-spawn, TC_S_NOT_RESET)
-// stores 0.0 there.
-struct CtrlTab {  // library owned, updated in place by tc_env_set_controller (a captured graph sees new gains)
-  double k, speed;
-};
-struct CtrlArgs {
-  const CtrlTab* tab;
-  const double* noise;  // [K][N] from the first step of this launch on, or NULL
-  double* rows;         // likewise, out
-  double* last;         // [N] out, or NULL
-};
-typedef const __attribute__((address_space(4))) CtrlTab* CtrlTabConst;  // never written by a kernel: scalar loads
-// the steering command of one env (before noise), and the velocity command
-__device__ __forceinline__ double ctrl_command(const CtrlArgs& ct, double cte, double he, double msa, double& speed) {
-  const CtrlTabConst t = (CtrlTabConst)(unsigned long long)ct.tab;
-  speed = t->speed;
-  return tc_ctrl_stanley(cte, he, t->k, speed, msa);
-}
-// by the one lane that stores the env's outputs; row: (step, env) of the launch's per-step rows
-__device__ __forceinline__ void ctrl_store(const CtrlArgs& ct, int env, size_t row, double steer) {
-  if (ct.rows) ct.rows[row] = steer;
-  if (ct.last) ct.last[env] = steer;
-}
-
-// (scalars by value: a reference to the kernel-argument struct would force a copy of it into scratch)
-// my_cnt: lane t < TC_MAX_TERMS holds steps_true of term slot t (loaded at kernel start, stored by the caller)
-__device__ __forceinline__ void d_apply_terms(const tc_term* terms, int n_terms, int& my_cnt, double tw, int tid, int C,
-                                              double cte, double vel, double dist_l, double& reward, int& terminated) {
-  const double half = tw / 2;
-  for (int t = 0; t < n_terms; t++) {
-    const tc_term* T = terms + t;
-    const int kind = T->kind;
-    const unsigned mask = T->layer_mask;
-    if (kind == TC_T_LANELINE_SPARSE_REWARD) {  // reward.py:20-21, utils.py:15-19
-      double local = 0.0;
-      for (int l = 0; l < C; l++) {
-        const double d = d_readlane(dist_l, l);
-        if (((mask >> l) & 1u) && d < half) local += T->per_layer[l];
-      }
-      reward = reward + local;
-    } else if (kind == TC_T_LANELINE_LINEAR_REWARD) {  // reward.py:40-41
-      for (int l = 0; l < C; l++) {
-        const double d = d_readlane(dist_l, l);
-        reward = reward + d_linear_reward(d, tw, T->per_layer[l], 0.0);
-      }
-    } else if (kind == TC_T_CTE_SPARSE_REWARD) {  // reward.py:60
-      double local = 0.0;
-      if (tc_fabs(cte) <= T->p[0]) local += T->p[1];
-      reward = reward + local;
-    } else if (kind == TC_T_CTE_LINEAR_REWARD) {  // reward.py:83
-      reward = reward + d_linear_reward(cte, T->p[0], T->p[1], T->p[2]);
-    } else if (kind == TC_T_LANELINE_CROSSING_TERMINATION) {  // termination.py:19-21
-      for (int l = 0; l < C; l++) {
-        const double d = d_readlane(dist_l, l);
-        if (((mask >> l) & 1u) && d <= half) terminated = 1;
-      }
-    } else if (kind == TC_T_CTE_TERMINATION || kind == TC_T_CRASH_TERMINATION) {  // termination.py:39-47,61-69
-      const bool cond = kind == TC_T_CTE_TERMINATION ? (tc_fabs(cte) > T->p[0]) : (tc_fabs(vel) < T->p[0]);
-      int c = __builtin_amdgcn_readlane(my_cnt, t);
-      if (cond) {
-        c += 1;
-        if (c >= T->number_of_steps) {
-          terminated = 1;
-          c = 0;
-        }
-      } else {
-        c = 0;
-      }
-      if (tid == t) my_cnt = c;
-    }
-  }
-}
-
-// The same stack for the grouped simulate kernel, where every lane of an env's group runs it: distances and counters
-// of the env sit in a small LDS record (all lanes of the group read and write the same words with the same values).
-__device__ __forceinline__ void d_apply_terms_mem(const tc_term* terms, int n_terms, int* cnt, double tw, int C, double cte,
-                                                  double vel, const double* dist, double& reward, int& terminated) {
-  const double half = tw / 2;
-  for (int t = 0; t < n_terms; t++) {
-    const tc_term* T = terms + t;
-    const int kind = T->kind;
-    const unsigned mask = T->layer_mask;
-    if (kind == TC_T_LANELINE_SPARSE_REWARD) {  // reward.py:20-21, utils.py:15-19
-      double local = 0.0;
-      for (int l = 0; l < C; l++)
-        if (((mask >> l) & 1u) && dist[l] < half) local += T->per_layer[l];
-      reward = reward + local;
-    } else if (kind == TC_T_LANELINE_LINEAR_REWARD) {  // reward.py:40-41
-      for (int l = 0; l < C; l++) reward = reward + d_linear_reward(dist[l], tw, T->per_layer[l], 0.0);
-    } else if (kind == TC_T_CTE_SPARSE_REWARD) {  // reward.py:60
-      double local = 0.0;
-      if (tc_fabs(cte) <= T->p[0]) local += T->p[1];
-      reward = reward + local;
-    } else if (kind == TC_T_CTE_LINEAR_REWARD) {  // reward.py:83
-      reward = reward + d_linear_reward(cte, T->p[0], T->p[1], T->p[2]);
-    } else if (kind == TC_T_LANELINE_CROSSING_TERMINATION) {  // termination.py:19-21
-      for (int l = 0; l < C; l++)
-        if (((mask >> l) & 1u) && dist[l] <= half) terminated = 1;
-    } else if (kind == TC_T_CTE_TERMINATION || kind == TC_T_CRASH_TERMINATION) {  // termination.py:39-47,61-69
-      const bool cond = kind == TC_T_CTE_TERMINATION ? (tc_fabs(cte) > T->p[0]) : (tc_fabs(vel) < T->p[0]);
-      int c = cnt[t];
-      if (cond) {
-        c += 1;
-        if (c >= T->number_of_steps) {
-          terminated = 1;
-          c = 0;
-        }
-      } else {
-        c = 0;
-      }
-      cnt[t] = c;
-    }
-  }
-}
+#include "k_probe.h"
+#include "k_common.h"
+#include "k_feat.h"
 
 // ---------------------------------------------------------------------------------------------
 // Per-lane register cache of the map: lane `tid` keeps nodes / edges (w*K + k)*64 + tid, k < K, of window w.
@@ -751,14 +161,6 @@ __device__ inline void cam_chain_replay(double* Px, double* Py, double* Pz, unsi
 }
 
 __device__ inline int2 cam_project(const double* K, double X, double Y, double Z, double& u, double& v);
-
-typedef __attribute__((address_space(3))) int* LdsIntPtr;  // (explicitly LDS: a select between it and a global pointer
-                                                            // cannot be folded into one flat access)
-
-// rank of this lane among the set bits of a wave ballot
-__device__ __forceinline__ int wave_rank(unsigned long long m) {
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
 
 // Phase C of one camera group whose nodes and edges sit in the wavefront's registers (one window: every bundled map).
 // camera.py:52-110 reads the whole node / edge arrays in each of its steps; here the flags of an edge's two ends are
@@ -1055,11 +457,6 @@ __device__ inline int checked_spawn(const DevMap& m, int node, int& status) {
   return m.first_spawnable;
 }
 
-__device__ inline unsigned int spread4(unsigned int x) {  // x < 16: 4 bits -> 4 bytes of 0x00/0xFF
-  const unsigned int m = (x * 0x00204081u) & 0x01010101u;  // 24-bit multiply: full rate
-  return (m << 8) - m;                                     // * 255 without v_mul_lo_u32
-}
-
 // camera.py:133-142 for one node + the np.int32 cast of renderer.py:43,50
 __device__ inline int2 cam_project(const double* K, double X, double Y, double Z, double& u, double& v) {
   double P3[3] = {X, Y, Z};
@@ -1068,20 +465,6 @@ __device__ inline int2 cam_project(const double* K, double X, double Y, double Z
   u = h[0] / h[2];
   v = h[1] / h[2];
   return make_int2(d_np_int32(u), d_np_int32(v));
-}
-
-// Inclusive prefix sum over the 64 lanes with DPP moves (register to register): Hillis-Steele inside each row of 16
-// (row_shr 1, 2, 4, 8, zeros shifted in), then lane 15 of a row added to the next row and lane 31 to the upper half
-// (row_bcast 15 / 31) -- instead of six ds_bpermute round trips through the LDS crossbar.  All 64 lanes must be active.
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-  (void)lane;
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);  // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);  // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);  // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);  // row_shr:8
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1 and 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2 and 3
-  return v;
 }
 
 // Caller's buffers -> LiveLds, one item per lane (one vector-memory round trip for the ~30 scalars of an env).
@@ -1839,45 +1222,6 @@ __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, in
   used_out = 0;
   for (int c = 0; c < m.C; c++)
     if (__ballot((my_layers >> c) & 1u)) used_out |= 1u << c;
-}
-
-// Step k of a launch reads row k of the action arrays and writes row k of the rollout arrays ([nsteps][N] each).
-struct MultiArgs {
-  int nsteps;
-  int seg_rows;  // > 1: step k writes its draw list to row k of seg_g / seg_n ([seg_rows][N] lists) for a raster launch
-                 // over all (step, env) frames behind this kernel; 1: row 0 every step (same wavefront rasterises it)
-  int cam_here;  // tc_env_kernel: 1 = the camera stage (draw list) runs in this kernel, 0 = not (no observation wanted,
-                 // or tc_frame_kernel produces the frames from pose_rows)
-  double* pose_rows;  // [nsteps][N][TC_POSE_ROW] camera.py:62 pose matrix of every (step, env) for tc_frame_kernel, or NULL
-  unsigned int* resident;  // streamed call (see launch()): every workgroup counts itself in here when it starts, and the
-                           // pose rows are written with device-scope stores (a frame kernel that runs BESIDE this launch
-                           // polls them); NULL otherwise
-  int map_lds;        // tc_envg_kernel: 1 = the lane-line edge records (end points + orientations, 48 bytes per edge) are
-                      // copied into the workgroup's LDS at kernel start and phase B reads them from there
-  int fat_lds;        // tc_envg_kernel: 1 = the lanepath's fat node records (96 bytes per node) sit in LDS too, behind the
-                      // edge records (or at offset 0 without them), and lanepath tracking reads them there
-  tc_rollout roll;
-};
-// (base pointers and the row: the address of a row is formed where it is stored, under its null test -- forming all 15 row
-// pointers at the top of every step was ~60 scalar instructions per step of every wavefront, 4 % of cfg2)
-__device__ __forceinline__ RollStep roll_at(const tc_rollout& r, size_t row0, int C) {
-  RollStep q;
-  q.reward = r.reward;
-  q.cte = r.cte;
-  q.heading_error = r.heading_error;
-  q.terminated = r.terminated;
-  q.truncated = r.truncated;
-  q.status = r.status;
-  q.x = r.x;
-  q.y = r.y;
-  q.theta = r.theta;
-  q.velocity = r.velocity;
-  q.dist = r.laneline_distances;
-  q.ne = r.nearest_edge;
-  q.lp = r.local_path;
-  q.lp_len = r.lp_len;
-  q.row0 = row0;
-  return q;
 }
 
 // ---------------------------------------------------------------------------------------------
