@@ -56,6 +56,8 @@ extern "C" {
 #define TC_HAS_PACKED_OBS 1
 /* Likewise additive within ABI 6: tc_env_set_camera_bank, tc_camera_bank. */
 #define TC_HAS_CAMERA_BANK 1
+/* Likewise additive within ABI 6: tc_env_set_drive_randomization, tc_drive_randomization, TC_MAN_*, tc_draw_normals. */
+#define TC_HAS_DRIVE_RANDOMIZATION 1
 #define TC_MAX_LAYERS 16
 
 /* error codes */
@@ -352,7 +354,61 @@ typedef struct {
   double* steer_rows;        /* device [n_rows][N] or NULL, out: the command BEFORE noise (the IL label, train_stanley_il.py:73) */
   double* steer_last;        /* device [N] or NULL, out: the same for the call's last step */
 } tc_controller;
-int tc_env_set_controller(tc_env* env, const tc_controller* c); /* NULL = off */
+int tc_env_set_controller(tc_env* env, const tc_controller* c); /* NULL = off; drops the drive randomisation too */
+/* Drive randomisation: what examples/train_stanley_il.py and examples/train_td3.py do to the action at an episode boundary,
+ * inside a call, where only the kernel knows where an episode ends.  Two parts, each optional, both need a controller:
+ *   maneuvers (n_maneuvers > 0): the maneuver is a per-episode quantity (train_stanley_il.py:105, train_td3.py:178) kept in
+ *     maneuver[i]; entries of `maneuvers` are in {0, 1, 2, 3}, repeats act as weights.
+ *   OU noise (ou_state != NULL): noise += THETA * (MEAN - noise) + SIGMA * randn (train_stanley_il.py:66, train_td3.py:143)
+ *     kept in ou_state[i], reset to 0 at every episode start when ou_reset != 0 (train_td3.py:177), else carried across.
+ * Per env i:
+ *   - a re-spawn by the library (tc_reset of an env the mask selects, or a TC_F_AUTORESET re-spawn in either spawn mode and in
+ *     every kernel form): with n_maneuvers > 0, e = episode[i] and
+ *       TC_MAN_DRAW   maneuver[i] = maneuvers[((z >> 32) * n_maneuvers) >> 32],
+ *                     z = SplitMix64(SplitMix64(seed)[0x6D616E])[(env_offset + i) << 32 | e]
+ *       TC_MAN_CYCLE  maneuver[i] = maneuvers[(env_offset + i + e) % n_maneuvers]
+ *     then episode[i] += 1; with ou_reset != 0, ou_state[i] = 0.0.  The re-spawn step applies no action: it consumes no
+ *     normal, stores 0.0 in noise_rows and the NEW episode's maneuver in maneuver_rows.
+ *   - a step that applies an action: the maneuver is maneuver[i] when n_maneuvers > 0 (the `maneuver` argument of tc_step /
+ *     tc_step_multi is then ignored and may be NULL), else the call's maneuver row as ever.  With OU noise:
+ *       eps = normal number ou_draws[i] of env (env_offset + i) of the seed; ou_draws[i] = (ou_draws[i] + 1) mod 2^31
+ *       n   = ou_state[i] + (theta * (mu - ou_state[i]) + sigma * eps); ou_state[i] = n
+ *     (tinycarlo_amd/csrc/tc_rng.h: tc_normal_at -- Box-Muller on a sub-stream of its own -- and tc_ou_step) and the applied
+ *     steering is steer + n, or (steer + steer_noise[k][i]) + n when the controller has noise rows.  steer_rows / steer_last
+ *     keep the command before any noise; noise_rows[k][i] = n, maneuver_rows[k][i] = the maneuver used.
+ *   - envs with TC_S_NOT_RESET are left alone: no draw, noise row 0.0.
+ * All state lives in the caller's arrays between calls, so a K-step call is bit-identical to K tc_step calls and to any
+ * split of the K steps.  The rows belong to tc_step_multi calls, like the steer rows.
+ * seed, env_offset, candidates, mode, theta, mu, sigma and ou_reset sit in a library-owned device table updated in place (a
+ * captured graph sees new values without re-capture; a call that changes them waits for the device); the pointers are
+ * kernel arguments of the launches enqueued afterwards, and so is which of the two parts is on.  Runs in the tc_drive_*
+ * entry points behind a run-time branch; while it is on, tc_reset takes them too.  d = NULL switches it off, and so does a
+ * struct with neither part (n_maneuvers = 0 and ou_state = NULL).
+ * TC_E_INVALID, before any device work: no controller installed, a maneuver outside 0..3, n_maneuvers outside 0..8, an
+ * unknown mode, a non-finite theta / mu / sigma, n_maneuvers > 0 with a NULL maneuver or episode, ou_state without ou_draws,
+ * n_rows < 0, rows with n_rows = 0, and from a tc_step_multi call of more than n_rows steps while a row pointer is set. */
+#define TC_MAN_DRAW 0
+#define TC_MAN_CYCLE 1
+typedef struct {
+  uint64_t seed;
+  uint32_t env_offset;    /* index of env 0 in a larger population (shards draw what one batch would) */
+  int32_t n_maneuvers;    /* 0..8; 0: the call's maneuver rows as ever */
+  int32_t maneuvers[8];   /* candidates, each 0, 1, 2 or 3 */
+  int32_t maneuver_mode;  /* TC_MAN_DRAW or TC_MAN_CYCLE */
+  int32_t ou_reset;       /* != 0: ou_state = 0.0 at every re-spawn */
+  double theta, mu, sigma;
+  int32_t* maneuver;      /* device [N], in/out, caller owned: the maneuver in force */
+  int32_t* episode;       /* device [N], in/out: episodes drawn so far */
+  double* ou_state;       /* device [N], in/out, or NULL: no OU noise */
+  int32_t* ou_draws;      /* device [N], in/out: normals consumed so far (never reset; wraps at 2^31) */
+  int32_t* maneuver_rows; /* device [n_rows][N], out, or NULL */
+  double* noise_rows;     /* device [n_rows][N], out, or NULL */
+  int32_t n_rows;         /* rows of maneuver_rows / noise_rows (0 when both are NULL) */
+} tc_drive_randomization;
+int tc_env_set_drive_randomization(tc_env* env, const tc_drive_randomization* d); /* NULL = off */
+/* Normal number first_draw + j (mod 2^31) of env `env` (tc_normal_at of tc_rng.h) for j < n into out[j], on the host (no
+ * device needed): what a restatement of the OU process in another language calls. */
+int tc_draw_normals(uint64_t seed, uint32_t env, uint32_t first_draw, int32_t n, double* out);
 /* Installs n_terms (0..TC_MAX_TERMS) reward / termination terms; they apply to every tc_step enqueued afterwards
  * (the call waits for earlier launches).  Each term starts from the reward / terminated value left by the one
  * before it, the first from the base values of env.py:136-138 (0 / false under TC_F_WRAPPED, which the reference

@@ -38,10 +38,13 @@ HAS_EPISODES = 1   # TC_HAS_EPISODES: additive within ABI 6
 HAS_CONTROLLER = 1  # TC_HAS_CONTROLLER: likewise
 CTRL_STANLEY = 1    # TC_CTRL_STANLEY
 HAS_CAMERA_BANK = 1  # TC_HAS_CAMERA_BANK: likewise
+HAS_DRIVE_RANDOMIZATION = 1  # TC_HAS_DRIVE_RANDOMIZATION: likewise
+MAN_DRAW, MAN_CYCLE = 0, 1   # TC_MAN_*: maneuver_mode of tc_drive_randomization
+MAX_MANEUVERS = 8
 
 EXPORTS = ["tc_abi_version", "tc_last_error", "tc_map_create", "tc_map_destroy", "tc_env_create", "tc_env_destroy",
            "tc_env_bind", "tc_env_set_camera", "tc_env_set_camera_per_env", "tc_env_set_camera_bank", "tc_env_set_car", "tc_env_set_car_per_env",
-           "tc_env_set_car_randomization", "tc_env_set_episodes", "tc_env_set_episode_rollout", "tc_env_set_controller", "tc_env_set_terms", "tc_env_set_spawn_table", "tc_env_set_noise", "tc_noise", "tc_env_obs_bytes", "tc_env_lds_bytes", "tc_env_profile",
+           "tc_env_set_car_randomization", "tc_env_set_episodes", "tc_env_set_episode_rollout", "tc_env_set_controller", "tc_env_set_drive_randomization", "tc_draw_normals", "tc_env_set_terms", "tc_env_set_spawn_table", "tc_env_set_noise", "tc_noise", "tc_env_obs_bytes", "tc_env_lds_bytes", "tc_env_profile",
            "tc_env_profile_read", "tc_reset", "tc_step", "tc_step_multi", "tc_env_reserve_steps", "tc_env_launch_info", "tc_env_draw_list_stats", "tc_render",
            "tc_render_segments", "tc_unpack_bits"]
 
@@ -87,6 +90,13 @@ class EpisodeBuffers(C.Structure):  # tc_episode_buffers: device arrays of N, le
 class ControllerC(C.Structure):  # tc_controller: gains by value, the rows device arrays [n_rows][N] (steer_last [N]) or NULL
     _fields_ = [("kind", C.c_int32), ("n_rows", C.c_int32), ("k", C.c_double), ("speed", C.c_double),
                 ("steer_noise", C.c_void_p), ("steer_rows", C.c_void_p), ("steer_last", C.c_void_p)]
+
+
+class DriveRandomizationC(C.Structure):  # tc_drive_randomization: settings by value; device arrays of N, rows [n_rows][N] or NULL
+    _fields_ = [("seed", C.c_uint64), ("env_offset", C.c_uint32), ("n_maneuvers", C.c_int32), ("maneuvers", C.c_int32 * 8),
+                ("maneuver_mode", C.c_int32), ("ou_reset", C.c_int32), ("theta", C.c_double), ("mu", C.c_double),
+                ("sigma", C.c_double), ("maneuver", C.c_void_p), ("episode", C.c_void_p), ("ou_state", C.c_void_p),
+                ("ou_draws", C.c_void_p), ("maneuver_rows", C.c_void_p), ("noise_rows", C.c_void_p), ("n_rows", C.c_int32)]
 
 
 class CameraBankC(C.Structure):  # tc_camera_bank: device pointers; index / episode [N], index_rows [n_rows][N] or NULL
@@ -151,6 +161,8 @@ def lib():
     L.tc_env_set_episodes.argtypes = [C.c_void_p, C.POINTER(EpisodeBuffers), C.c_int32]
     L.tc_env_set_episode_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.tc_env_set_controller.argtypes = [C.c_void_p, C.POINTER(ControllerC)]
+    L.tc_env_set_drive_randomization.argtypes = [C.c_void_p, C.POINTER(DriveRandomizationC)]
+    L.tc_draw_normals.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, _dp]
     L.tc_env_set_terms.argtypes = [C.c_void_p, C.POINTER(TermC), C.c_int32, C.c_void_p]
     L.tc_env_set_spawn_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64]
     L.tc_env_set_noise.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64]

@@ -1,6 +1,7 @@
 // k_feat.h -- the per-env feature blocks of the simulate stages: reward / termination terms (tinycarlo/wrapper/*.py, the
-// epilogue of a step), the TC_FEAT_* template mask, per-env car rows, the camera bank, episodes and the built-in controller
-// (tc_ctrl.h).  Defines no kernel: sim_body and the grouped kernel (tinycarlo_hip.hip) compile these in by mask.
+// epilogue of a step), the TC_FEAT_* template mask, per-env car rows, the camera bank, episodes, the built-in controller
+// (tc_ctrl.h) and the drive randomisation behind it.  Defines no kernel: sim_body and the grouped kernel (tinycarlo_hip.hip)
+// compile these in by mask.
 #ifndef K_FEAT_H
 #define K_FEAT_H
 
@@ -214,6 +215,75 @@ __device__ __forceinline__ double ctrl_command(const CtrlArgs& ct, double cte, d
 __device__ __forceinline__ void ctrl_store(const CtrlArgs& ct, int env, size_t row, double steer) {
   if (ct.rows) ct.rows[row] = steer;
   if (ct.last) ct.last[env] = steer;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Drive randomisation (tc_env_set_drive_randomization): the maneuver as a per-episode quantity and Ornstein-Uhlenbeck
+// steering noise, both following the episode inside a call.  Lives in the TC_FEAT_CTRL kernels only, behind two bits the
+// library sets in StepArgs::flags of every launch while the part is installed (run-time branches, as for TC_FI_CAM_BANK:
+// no instantiation of its own; never taken from the caller):
+//   TC_FI_DRIVE_MAN  candidates are installed: the maneuver of an action step is maneuver[env], re-drawn at every re-spawn
+//                    (tc_maneuver_index, or the cycle), and the call's maneuver rows are not read
+//   TC_FI_DRIVE_OU   ou_state is installed: every action step consumes one normal (tc_normal_at, evaluated right here: one
+//                    tc_log, one sqrt and one tc_cos next to the controller's tc_atan2 and the kinematics' tc_sin / tc_cos,
+//                    where few registers are live) and adds the new OU value behind the controller's own noise row
+// The grouped kernel keeps the three per-env values in a per-group LDS word across the steps of a launch and stores them
+// once; the per-env kernels read and write the caller's arrays where the step needs them (by the lane that stores the env's
+// outputs, read back by lanes of the same wavefront, as the car rows are): the LiveLds record has one spare int (`pad`) and
+// the three values need 16 bytes; 12 more would move TC_LIVE_BYTES, which the LDS budget of every kernel is laid out around.
+#define TC_FI_DRIVE_MAN 0x20000000u
+#define TC_FI_DRIVE_OU 0x10000000u
+#define TC_FI_DRIVE (TC_FI_DRIVE_MAN | TC_FI_DRIVE_OU)
+#define TC_MAX_MANEUVERS 8
+struct DriveTab {  // library owned, updated in place by tc_env_set_drive_randomization (a captured graph sees new settings)
+  unsigned long long seed;
+  double theta, mu, sigma;
+  unsigned int env_offset;
+  int n_man, mode, ou_reset;
+  int man[TC_MAX_MANEUVERS];
+};
+struct DriveArgs {
+  const DriveTab* tab;  // NULL: off
+  int* maneuver;        // [N] the maneuver in force (caller owned, as are the next three)
+  int* episode;         // [N] episodes drawn so far
+  double* ou_state;     // [N] or NULL
+  int* ou_draws;        // [N] normals consumed so far
+  int* man_rows;        // [K][N] from the first step of this launch on, out, or NULL
+  double* noise_rows;   // likewise
+};
+typedef const __attribute__((address_space(4))) DriveTab* DriveTabConst;  // never written by a kernel: scalar loads
+// the maneuver of episode `ep` of env `env` (n candidates, n > 0)
+__device__ __forceinline__ int drive_pick(const DriveTabConst t, int n, int env, int ep) {
+  const unsigned int g = t->env_offset + (unsigned int)env;
+  const unsigned int i = t->mode == TC_MAN_CYCLE ? (g + (unsigned int)ep) % (unsigned int)n
+                                                 : tc_maneuver_index(t->seed, g, (uint32_t)ep, (uint32_t)n);
+  return t->man[i < TC_MAX_MANEUVERS ? i : 0];
+}
+// A re-spawn of env `env` (TC_FI_DRIVE_MAN): the maneuver of its next episode; the writer stores the counter.  `held` is
+// returned while the table holds no candidate.
+template <bool UNI>
+__device__ __forceinline__ int drive_respawn_man(const DriveArgs& dr, int env, bool writer, int held) {
+  const DriveTabConst t = (DriveTabConst)(unsigned long long)dr.tab;
+  const int n = t->n_man;
+  if (n <= 0) return held;
+  const int ep = UNI ? uni_i(dr.episode[env]) : dr.episode[env];
+  const int m = drive_pick(t, n < TC_MAX_MANEUVERS ? n : TC_MAX_MANEUVERS, env, ep);
+  if (writer) dr.episode[env] = ep + 1;
+  return m;
+}
+// An action step of env `env` (TC_FI_DRIVE_OU): normal number `draws` of the env moves its OU value `ou`
+__device__ __forceinline__ double drive_ou(const DriveArgs& dr, int env, double ou, int draws) {
+  const DriveTabConst t = (DriveTabConst)(unsigned long long)dr.tab;
+  const double eps = tc_normal_at(t->seed, (uint32_t)(t->env_offset + (unsigned int)env), (uint32_t)draws);
+  return tc_ou_step(ou, eps, t->theta, t->mu, t->sigma);
+}
+__device__ __forceinline__ bool drive_ou_reset(const DriveArgs& dr) {
+  return ((DriveTabConst)(unsigned long long)dr.tab)->ou_reset != 0;
+}
+// by the one lane that stores the env's outputs; row: (step, env) of the launch's per-step rows
+__device__ __forceinline__ void drive_store(const DriveArgs& dr, size_t row, int man, double noise) {
+  if (dr.man_rows) dr.man_rows[row] = man;
+  if (dr.noise_rows) dr.noise_rows[row] = noise;
 }
 
 // (scalars by value: a reference to the kernel-argument struct would force a copy of it into scratch)

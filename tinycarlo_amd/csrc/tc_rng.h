@@ -10,9 +10,10 @@
 // Plain C / HIP like tc_trig.h: the CPU test oracle includes this header too (the package never includes the oracle).
 #ifndef TC_RNG_H
 #define TC_RNG_H
+#include <math.h> /* sqrt */
 #include <stdint.h>
 
-#include "tc_trig.h" /* TC_HD */
+#include "tc_trig.h" /* TC_HD, tc_log, tc_cos */
 
 TC_HD uint64_t tc_splitmix64_at(uint64_t seed, uint64_t n) {
   uint64_t z = seed + (n + 1) * 0x9E3779B97F4A7C15ull;
@@ -48,6 +49,31 @@ TC_HD double tc_car_draw(uint64_t z, int j, double lo, double hi) {
 TC_HD uint32_t tc_camera_index(uint64_t seed, uint32_t env, uint32_t episode, uint32_t count) {
   const uint64_t z = tc_splitmix64_at(tc_splitmix64_at(seed, 0x63616Dull), ((uint64_t)env << 32) | episode);
   return (uint32_t)(((z >> 32) * (uint64_t)count) >> 32);
+}
+
+// Drive randomisation (tc_env_set_drive_randomization): the maneuver of an episode and the Ornstein-Uhlenbeck steering noise
+// of examples/train_stanley_il.py:66,105 and examples/train_td3.py:143,178, each on a sub-stream of its own.
+// Episode `episode` of env `env` (global index) takes candidate number tc_maneuver_index of `count` (> 0): the high 32 bits of
+// output (env << 32 | episode) of s' = SplitMix64(seed)[0x6D616E] ("man"), scaled by count as in tc_camera_index.
+TC_HD uint32_t tc_maneuver_index(uint64_t seed, uint32_t env, uint32_t episode, uint32_t count) {
+  const uint64_t z = tc_splitmix64_at(tc_splitmix64_at(seed, 0x6D616Eull), ((uint64_t)env << 32) | episode);
+  return (uint32_t)(((z >> 32) * (uint64_t)count) >> 32);
+}
+// Standard normal number `draw` of env `env`: Box-Muller over outputs 0 and 1 of SplitMix64(z),
+// z = SplitMix64(SplitMix64(seed)[0x6F75])[env << 32 | draw] ("ou").  u1 = ((a >> 11) + 1) * 2^-53 lies in (0, 1], so the
+// logarithm is finite and <= 0; u2 = (b >> 11) * 2^-53 in [0, 1).  |result| <= sqrt(106 ln 2) = 8.58, never NaN or infinite.
+// tc_log / tc_cos are the portable ones of tc_trig.h, sqrt the correctly rounded IEEE one on both sides, every operation
+// rounded on its own (-ffp-contract=off): host and device agree bit for bit.
+TC_HD double tc_normal_at(uint64_t seed, uint32_t env, uint32_t draw) {
+  const uint64_t z = tc_splitmix64_at(tc_splitmix64_at(seed, 0x6F75ull), ((uint64_t)env << 32) | draw);
+  const uint64_t a = tc_splitmix64_at(z, 0), b = tc_splitmix64_at(z, 1);
+  const double u1 = (double)((a >> 11) + 1) * 0x1p-53;
+  const double u2 = (double)(b >> 11) * 0x1p-53;
+  return sqrt(-2.0 * tc_log(u1)) * tc_cos(6.283185307179586 * u2);
+}
+// noise += THETA * (MEAN - noise) + SIGMA * randn, in the Python expression's order
+TC_HD double tc_ou_step(double n, double eps, double theta, double mu, double sigma) {
+  return n + (theta * (mu - n) + sigma * eps);
 }
 
 // One blob of NoiseObservationWrapper (wrapper/observation.py:18-20): centre (x, y) inside the frame, radius in

@@ -1,4 +1,4 @@
-// tc_trig.h -- deterministic double-precision sin / cos / tan / atan2.
+// tc_trig.h -- deterministic double-precision sin / cos / tan / atan2 / log.
 //
 // Why this exists: the reference computes its transcendentals with the host libm (CPython
 // `math.*`, car.py:92-122, layer.py:122,140-141,181).  A GPU has no glibc; AMD's OCML versions
@@ -310,6 +310,57 @@ TC_HD double tc_atan2(double y, double x) {
     case 2: return pi - (z - pi_lo);
     default: return (z - pi_lo) - pi;
   }
+}
+
+// ---------------------------------------------------------------- natural logarithm
+// For the Box-Muller transform of tc_rng.h (arguments in (0, 1]; every positive double is handled).  The classic scheme
+// of the same libm: x = 2^k * (1 + f) with sqrt(2)/2 < 1 + f < sqrt(2), s = f / (2 + f),
+// log(1 + f) = f - f^2/2 + s * (f^2/2 + R(s^2)), R a degree-14 minimax polynomial in s, and k * ln2 added in two parts
+// (ln2_hi has 21 trailing zero bits, so k * ln2_hi is exact).  Accuracy: < 1 ulp.  log(1) = +0; zero gives -inf, a
+// negative argument NaN.
+TC_HD double tc_log(double x) {
+  const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
+  const double Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01, Lg3 = 2.857142874366239149e-01,
+               Lg4 = 2.222219843214978396e-01, Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
+               Lg7 = 1.479819860511658591e-01;
+  int32_t hx = tc_hi(x);
+  int k = 0;
+  if (hx < 0x00100000) {  // zero, subnormal or negative
+    if (((hx & 0x7fffffff) | tc_lo(x)) == 0) return tc_u2d(0xfff0000000000000ULL);
+    if (hx < 0) return tc_u2d(0x7ff8000000000000ULL);
+    k -= 54;
+    x = x * 18014398509481984.0;  // 2^54
+    hx = tc_hi(x);
+  }
+  if (hx >= 0x7ff00000) return x + x;
+  k += (hx >> 20) - 1023;
+  hx &= 0x000fffff;
+  int32_t i = (hx + 0x95f64) & 0x100000;
+  x = tc_u2d(((uint64_t)(uint32_t)(hx | (i ^ 0x3ff00000)) << 32) | tc_lo(x));  // x or x / 2, in [sqrt(2)/2, sqrt(2))
+  k += i >> 20;
+  const double f = x - 1.0, dk = (double)k;
+  if ((0x000fffff & (2 + hx)) < 3) {  // |f| < 2^-20
+    if (f == 0.0) {
+      if (k == 0) return 0.0;
+      return dk * ln2_hi + dk * ln2_lo;
+    }
+    const double R = f * f * (0.5 - 0.33333333333333333 * f);
+    if (k == 0) return f - R;
+    return dk * ln2_hi - ((R - dk * ln2_lo) - f);
+  }
+  const double s = f / (2.0 + f);
+  const double z = s * s;
+  const double w = z * z;
+  const double t1 = w * (Lg2 + w * (Lg4 + w * Lg6));
+  const double t2 = z * (Lg1 + w * (Lg3 + w * (Lg5 + w * Lg7)));
+  const double R = t2 + t1;
+  if (((hx - 0x6147a) | (0x6b851 - hx)) > 0) {
+    const double hfsq = 0.5 * f * f;
+    if (k == 0) return f - (hfsq - s * (hfsq + R));
+    return dk * ln2_hi - ((hfsq - (s * (hfsq + R) + dk * ln2_lo)) - f);
+  }
+  if (k == 0) return f - s * (f - R);
+  return dk * ln2_hi - ((s * (f - R) - dk * ln2_lo) - f);
 }
 
 #endif  // TC_TRIG_H

@@ -613,7 +613,8 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
                                 const int* maneuver, const int* spawn_nodes, const unsigned char* mask,
                                 unsigned int flags, const RollStep& roll, const int tid, MapCache<K>& mc, FramePose& fp,
                                 int& cam_row, const CarRows& cr = CarRows(), const EpArgs& ep = EpArgs(),
-                                const CtrlArgs& ct = CtrlArgs(), const CamBank& cb = CamBank()) {
+                                const CtrlArgs& ct = CtrlArgs(), const CamBank& cb = CamBank(),
+                                const DriveArgs& dr = DriveArgs()) {
   constexpr bool PER = (FEAT & TC_FEAT_CAR) != 0, EP = (FEAT & TC_FEAT_EP) != 0, CTRL = (FEAT & TC_FEAT_CTRL) != 0;
 
   TSTAMP(0);
@@ -660,9 +661,22 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
   bool fresh = false;  // env was (re)spawned in this launch: info is empty (car.py:47-51)
   const double* crow = PER ? cr.rows + (size_t)env * TC_CAR_NP : nullptr;
   double ctrl_steer = 0.0;  // CTRL: this step's command before noise (0 when no action is applied)
+  // CTRL, drive randomisation: the maneuver in force and the OU value applied (0 when no action is applied), for the rows
+  const bool drv_man = CTRL && (flags & TC_FI_DRIVE_MAN) != 0, drv_ou = CTRL && (flags & TC_FI_DRIVE_OU) != 0;
+  int drive_m = 0;
+  double drive_n = 0.0;
+  // a re-spawn: the next episode's maneuver, and the OU value back to 0 when asked for (lane 0 stores; see DriveArgs)
+  auto drive_respawn = [&]() {
+    if (drv_man) {
+      drive_m = drive_respawn_man<true>(dr, env, tid == 0, uni_i(dr.maneuver[env]));
+      if (tid == 0) dr.maneuver[env] = drive_m;
+    }
+    if (drv_ou && drive_ou_reset(dr) && tid == 0) dr.ou_state[env] = 0.0;
+  };
   if (mode == MODE_RESET) {
     if (PER) car_respawn<true>(cr, env, true);
     if (bank) cam_row = cam_respawn<true>(cb, env, tid == 0);
+    if (CTRL) drive_respawn();
     d_reset(m, PER ? car_of<true>(a.car, crow) : a.car, s, checked_spawn(m, spawn_nodes[env], status));
     fresh = true;
     have_trig = true;
@@ -678,6 +692,10 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
       }
       if (PER) car_respawn<true>(cr, env, true);
       if (bank) cam_row = cam_respawn<true>(cb, env, tid == 0);
+      if (CTRL) {
+        drive_respawn();
+        if (!drv_man && dr.man_rows) drive_m = maneuver[env];
+      }
       d_reset(m, PER ? car_of<true>(a.car, crow) : a.car, s, checked_spawn(m, node, status));
       fresh = true;
       have_trig = true;
@@ -685,12 +703,22 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
     } else if ((unsigned)s.lp[0] >= (unsigned)m.lpN || (unsigned)s.lp[1] >= (unsigned)m.lpN) {
       status |= TC_S_NOT_RESET;  // stepping an env that was never reset: no valid lanepath edge to index with
       trunc = 1;
+      if (CTRL && dr.man_rows) drive_m = drv_man ? uni_i(dr.maneuver[env]) : maneuver[env];
     } else {
       double v, st;
       if (CTRL) {  // (every input is wave-uniform; double arithmetic has no scalar form, so the lanes all compute it)
         ctrl_steer = ctrl_command(ct, uni_d(lv->cte), uni_d(lv->he),
                                   PER ? car_ld<true>(crow, TC_CAR_MAX_STEERING_ANGLE) : a.car.max_steering_angle, v);
         st = ct.noise ? ctrl_steer + uni_d(ct.noise[roll.row0 + env]) : ctrl_steer;
+        if (drv_ou) {  // (steer + row) + n
+          const int draws = uni_i(dr.ou_draws[env]);
+          drive_n = drive_ou(dr, env, uni_d(dr.ou_state[env]), draws);
+          st = st + drive_n;
+          if (tid == 0) {
+            dr.ou_state[env] = drive_n;
+            dr.ou_draws[env] = (draws + 1) & 0x7fffffff;
+          }
+        }
       } else if (cdtype == TC_F32) {
         v = (double)((const float*)car_control)[2 * env];
         st = (double)((const float*)car_control)[2 * env + 1];
@@ -701,7 +729,8 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
       v = d_np_clip(v, -1.0, 1.0);  // env.py:118
       // per-env steering shift: added before the clip (examples/train_td3.py:146-148)
       st = d_np_clip(PER ? st + car_ld<true>(crow, TC_CAR_STEERING_SHIFT) : st, -1.0, 1.0);
-      const int man = maneuver[env];
+      const int man = drv_man ? uni_i(dr.maneuver[env]) : maneuver[env];
+      if (CTRL) drive_m = man;
       d_car_kinematics(PER ? car_of<true>(a.car, crow) : a.car, s, v, st, have_trig);
       TSTAMP(23);
       const FatGlobal fg = {m.lp_fat, m.lp_nodes};
@@ -765,7 +794,10 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
       if (roll.theta) roll.theta[roll.row0 + env] = s.theta;
       if (roll.velocity) roll.velocity[roll.row0 + env] = s.velocity;
       if (roll.lp_len) roll.lp_len[roll.row0 + env] = s.lp_len;
-      if (CTRL && mode == MODE_STEP) ctrl_store(ct, env, roll.row0 + env, ctrl_steer);
+      if (CTRL && mode == MODE_STEP) {
+        ctrl_store(ct, env, roll.row0 + env, ctrl_steer);
+        drive_store(dr, roll.row0 + env, drive_m, drive_n);
+      }
       if (EP) lv->ep_len = ep_len;
       if (bank) {
         if (fresh) lv->cam_idx = cam_row;
@@ -2109,6 +2141,7 @@ struct StepArgs {
   EpArgs ep;             // episodes: read by the TC_FEAT_EP kernels only (behind it, for the same reason)
   CtrlArgs ct;           // built-in controller: read by the TC_FEAT_CTRL kernels only (likewise)
   CamBank cb;            // camera bank: index NULL = none (likewise behind the others)
+  DriveArgs dr;          // drive randomisation: read by the TC_FEAT_CTRL kernels only, behind TC_FI_DRIVE_* of flags (likewise)
 };
 
 // The launch arguments, read through a pointer the optimiser cannot see through.  Inside the step loop of tc_step_multi
@@ -2188,7 +2221,7 @@ __device__ __forceinline__ void env_kernel_body() {
     int cam_row;
     sim_body<K, FEAT>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
                          sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, cam_row, sa.cr, sa.ep,
-                         sa.ct, sa.cb);
+                         sa.ct, sa.cb, sa.dr);
     if (sa.ma.pose_rows) {
       double pose[12];
       cam_pose12(sa.a, cam_row, fp, pose);
@@ -2345,6 +2378,15 @@ __device__ __forceinline__ void envg_kernel_body() {
   // same value, and only lanes of this wavefront read it (LDS operations of a wavefront complete in order)
   __shared__ int g_cam_idx[TC_ENVG_NT / TC_EL];
   if (s0.flags & TC_FI_CAM_BANK) g_cam_idx[grp] = cam_clamp(s0.cb, s0.cb.index[env]);
+  // drive randomisation (tc_env_set_drive_randomization): the env's maneuver, OU value and draw counter, in LDS like the
+  // two above (every lane of the group computes and writes the same values) and back to the caller's arrays once per launch
+  __shared__ int g_drv_man[CTRL ? TC_ENVG_NT / TC_EL : 1], g_drv_draws[CTRL ? TC_ENVG_NT / TC_EL : 1];
+  __shared__ double g_drv_ou[CTRL ? TC_ENVG_NT / TC_EL : 1];
+  if (CTRL && (s0.flags & TC_FI_DRIVE_MAN)) g_drv_man[grp] = s0.dr.maneuver[env];
+  if (CTRL && (s0.flags & TC_FI_DRIVE_OU)) {
+    g_drv_ou[grp] = s0.dr.ou_state[env];
+    g_drv_draws[grp] = s0.dr.ou_draws[env];
+  }
   double cte = 0, he = 0, reward = 0;
   if (CTRL) {  // what the env reported after the step before this launch: the controller's input at the first step
     cte = s0.a.b.cte[env];
@@ -2369,7 +2411,7 @@ __device__ __forceinline__ void envg_kernel_body() {
       act_f = ((const float2*)sq.car_control)[r];
     else
       act_d = ((const double2*)sq.car_control)[r];
-    act_m = sq.maneuver[r];
+    if (!(CTRL && (sq.flags & TC_FI_DRIVE_MAN))) act_m = sq.maneuver[r];  // (device maneuvers: nothing to fetch)
   };
   fetch_action(0);
   for (int k = 0; k < nsteps; k++) {
@@ -2405,6 +2447,8 @@ __device__ __forceinline__ void envg_kernel_body() {
       }
       if (PER) car_respawn<false>(sa.cr, env, live && sub == 0);  // (one lane of the group writes the row and counter)
       if (flags & TC_FI_CAM_BANK) g_cam_idx[grp] = cam_respawn<false>(sa.cb, env, live && sub == 0);
+      if (CTRL && (flags & TC_FI_DRIVE_MAN)) g_drv_man[grp] = drive_respawn_man<false>(sa.dr, env, live && sub == 0, g_drv_man[grp]);
+      if (CTRL && (flags & TC_FI_DRIVE_OU) && drive_ou_reset(sa.dr)) g_drv_ou[grp] = 0.0;
       d_reset(m, PER ? car_of<false>(a.car, sa.cr.rows + (size_t)env * TC_CAR_NP) : a.car, s, checked_spawn(m, node, status));
       fresh = true;
       have_trig = true;
@@ -2418,6 +2462,13 @@ __device__ __forceinline__ void envg_kernel_body() {
       if (CTRL) {  // cte / he still hold what the step before left (0 / 0 behind a re-spawn)
         ctrl_steer = ctrl_command(sa.ct, cte, he, PER ? car_ld<false>(crow, TC_CAR_MAX_STEERING_ANGLE) : a.car.max_steering_angle, v);
         st = sa.ct.noise ? ctrl_steer + cur_d.y : ctrl_steer;
+        if (flags & TC_FI_DRIVE_OU) {  // (steer + row) + n
+          const int draws = g_drv_draws[grp];
+          const double n = drive_ou(sa.dr, env, g_drv_ou[grp], draws);
+          st = st + n;
+          g_drv_ou[grp] = n;
+          g_drv_draws[grp] = (draws + 1) & 0x7fffffff;
+        }
       } else if (sa.cdtype == TC_F32) {
         v = (double)cur_f.x;
         st = (double)cur_f.y;
@@ -2427,7 +2478,7 @@ __device__ __forceinline__ void envg_kernel_body() {
       }
       v = d_np_clip(v, -1.0, 1.0);  // env.py:118
       st = d_np_clip(PER ? st + car_ld<false>(crow, TC_CAR_STEERING_SHIFT) : st, -1.0, 1.0);  // (train_td3.py:146-148)
-      const int man = cur_m;
+      const int man = CTRL && (flags & TC_FI_DRIVE_MAN) ? g_drv_man[grp] : cur_m;
       TSTAMP(25);
       d_car_kinematics(PER ? car_of<false>(a.car, crow) : a.car, s, v, st, have_trig);
       TSTAMP(26);
@@ -2631,7 +2682,11 @@ __device__ __forceinline__ void envg_kernel_body() {
     // ---- this step's rollout rows and pose row
     if (live && sub == 0) {
       if (EP) ep_close(sa.ep, env, row0 + env, fresh, status, ep_len, g_ep_ret[grp], reward, terminated | trunc);
-      if (CTRL) ctrl_store(sa.ct, env, row0 + env, ctrl_steer);
+      if (CTRL) {
+        ctrl_store(sa.ct, env, row0 + env, ctrl_steer);
+        drive_store(sa.dr, row0 + env, (flags & TC_FI_DRIVE_MAN) ? g_drv_man[grp] : cur_m,
+                    track && (flags & TC_FI_DRIVE_OU) ? g_drv_ou[grp] : 0.0);
+      }
       if (roll.cte) roll.cte[roll.row0 + env] = cte;
       if (roll.heading_error) roll.heading_error[roll.row0 + env] = he;
       if (roll.truncated) roll.truncated[roll.row0 + env] = (unsigned char)trunc;
@@ -2679,6 +2734,11 @@ __device__ __forceinline__ void envg_kernel_body() {
       s1.ep.length[env] = g_ep_len[grp];
       s1.ep.ret[env] = g_ep_ret[grp];
     }
+    if (CTRL && (s1.flags & TC_FI_DRIVE_MAN)) s1.dr.maneuver[env] = g_drv_man[grp];
+    if (CTRL && (s1.flags & TC_FI_DRIVE_OU)) {
+      s1.dr.ou_state[env] = g_drv_ou[grp];
+      s1.dr.ou_draws[env] = g_drv_draws[grp];
+    }
   }
   if (live && s1.a.term_counters && sub < s1.a.n_terms) s1.a.term_counters[(size_t)env * TC_MAX_TERMS + sub] = gl.cnt[sub];
 }
@@ -2689,9 +2749,11 @@ template <unsigned FEAT>
 __global__ __launch_bounds__(TC_ENVG_NT, ((FEAT & TC_FEAT_EP) ? 4 : 0)) void tc_envg_kernel(StepArgs sa_unused) {
   envg_kernel_body<FEAT>();
 }
-// the same body with the built-in controller compiled in (FEAT has TC_FEAT_CTRL: masks 4-7)
+// the same body with the built-in controller compiled in (FEAT has TC_FEAT_CTRL: masks 4-7).  4 wavefronts per SIMD are
+// asked for in every mask: with the drive randomisation's normal (tc_log, sqrt, tc_cos beside the whole car state in
+// registers) the allocator left to itself takes 128 / 130 VGPRs in masks 4 / 5; held to 128 it spills nothing.
 template <unsigned FEAT>
-__global__ __launch_bounds__(TC_ENVG_NT, ((FEAT & TC_FEAT_EP) ? 4 : 0)) void tc_drive_envg_kernel(StepArgs sa_unused) {
+__global__ __launch_bounds__(TC_ENVG_NT, 4) void tc_drive_envg_kernel(StepArgs sa_unused) {
   static_assert((FEAT & TC_FEAT_CTRL) != 0, "the controller's entry point");
   envg_kernel_body<FEAT>();
 }
@@ -2913,7 +2975,7 @@ __device__ __forceinline__ void step_kernel_body() {
     int cam_row;  // (the bank index stays in a register: the same wavefront draws the frame)
     sim_body<K, FEAT>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
                          sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, cam_row, sa.cr, sa.ep,
-                         sa.ct, sa.cb);
+                         sa.ct, sa.cb, sa.dr);
     if (wants_frame(sa)) {
       int nseg;
       unsigned int used;
@@ -3425,6 +3487,11 @@ struct tc_env {
   DevPtr<CtrlTab> ctrl_tab;  // device copy of the gains (updated in place), or NULL
   CtrlTab ctrl_host{};   // what ctrl_tab holds
   int ctrl_rows = 0;     // rows of ct.noise / ct.rows
+  DriveArgs dr{};        // drive randomisation (tc_env_set_drive_randomization); tab NULL = off
+  DevPtr<DriveTab> drive_tab;  // device copy of the settings (updated in place), or NULL
+  DriveTab drive_host{};  // what drive_tab holds
+  int drive_rows = 0;    // rows of dr.man_rows / dr.noise_rows
+  unsigned drive_flags = 0;  // TC_FI_DRIVE_* of every launch while it is on
   CamBank cb{};          // camera bank (tc_env_set_camera_bank); index NULL = off.  k.cam_E / k.cam_K then point to the bank
   DevPtr<CamDrawTab> cam_tab;  // device copy of the draw settings (updated in place), or NULL
   CamDrawTab cam_host{};       // what cam_tab holds
@@ -4218,9 +4285,12 @@ extern "C" int tc_env_set_episode_rollout(tc_env* e, int32_t* length_rows, doubl
 
 extern "C" int tc_env_set_controller(tc_env* e, const tc_controller* c) {
   if (!e) return TC_E_INVALID;
-  if (!c) {  // feature off (the table stays for a graph captured earlier)
+  if (!c) {  // feature off (the table stays for a graph captured earlier); the drive randomisation goes with it
     memset(&e->ct, 0, sizeof(e->ct));
     e->ctrl_rows = 0;
+    memset(&e->dr, 0, sizeof(e->dr));
+    e->drive_rows = 0;
+    e->drive_flags = 0;
     return TC_OK;
   }
   if (c->kind != TC_CTRL_STANLEY) {
@@ -4255,6 +4325,100 @@ extern "C" int tc_env_set_controller(tc_env* e, const tc_controller* c) {
   e->ct.rows = c->steer_rows;
   e->ct.last = c->steer_last;
   e->ctrl_rows = (c->steer_noise || c->steer_rows) ? c->n_rows : 0;
+  return TC_OK;
+}
+
+extern "C" int tc_env_set_drive_randomization(tc_env* e, const tc_drive_randomization* d) {
+  if (!d) {  // feature off (the table stays for a graph captured earlier)
+    if (!e) return TC_E_INVALID;
+    memset(&e->dr, 0, sizeof(e->dr));
+    e->drive_rows = 0;
+    e->drive_flags = 0;
+    return TC_OK;
+  }
+  // (the settings first: a bad struct is refused whatever the handle is)
+  if (d->n_maneuvers < 0 || d->n_maneuvers > TC_MAX_MANEUVERS) {
+    set_err("tc_env_set_drive_randomization: n_maneuvers must be in 0..8");
+    return TC_E_INVALID;
+  }
+  for (int i = 0; i < d->n_maneuvers; i++)
+    if (d->maneuvers[i] < 0 || d->maneuvers[i] > 3) {
+      set_err("tc_env_set_drive_randomization: every maneuver must be in 0..3");
+      return TC_E_INVALID;
+    }
+  if (d->maneuver_mode != TC_MAN_DRAW && d->maneuver_mode != TC_MAN_CYCLE) {
+    set_err("tc_env_set_drive_randomization: unknown maneuver_mode");
+    return TC_E_INVALID;
+  }
+  if (!isfinite(d->theta) || !isfinite(d->mu) || !isfinite(d->sigma)) {
+    set_err("tc_env_set_drive_randomization: theta, mu and sigma must be finite");
+    return TC_E_INVALID;
+  }
+  if (d->n_maneuvers > 0 && (!d->maneuver || !d->episode)) {
+    set_err("tc_env_set_drive_randomization: candidates need the maneuver and episode arrays (n_maneuvers > 0)");
+    return TC_E_INVALID;
+  }
+  if (d->ou_state && !d->ou_draws) {
+    set_err("tc_env_set_drive_randomization: ou_state needs ou_draws");
+    return TC_E_INVALID;
+  }
+  if (d->n_rows < 0) {
+    set_err("tc_env_set_drive_randomization: n_rows must not be negative");
+    return TC_E_INVALID;
+  }
+  if ((d->maneuver_rows || d->noise_rows) && d->n_rows < 1) {
+    set_err("tc_env_set_drive_randomization: rows given with n_rows = 0");
+    return TC_E_INVALID;
+  }
+  if (!e) {
+    set_err("tc_env_set_drive_randomization: no env");
+    return TC_E_INVALID;
+  }
+  if (!e->ct.tab) {
+    set_err("tc_env_set_drive_randomization: no controller installed (tc_env_set_controller)");
+    return TC_E_INVALID;
+  }
+  if (d->n_maneuvers == 0 && !d->ou_state) {  // neither part: off (no launch takes a drive entry point for nothing)
+    memset(&e->dr, 0, sizeof(e->dr));
+    e->drive_rows = 0;
+    e->drive_flags = 0;
+    return TC_OK;
+  }
+  DriveTab want;
+  memset(&want, 0, sizeof(want));
+  want.seed = d->seed;
+  want.theta = d->theta;
+  want.mu = d->mu;
+  want.sigma = d->sigma;
+  want.env_offset = d->env_offset;
+  want.n_man = d->n_maneuvers;
+  want.mode = d->maneuver_mode;
+  want.ou_reset = d->ou_reset != 0;
+  for (int i = 0; i < d->n_maneuvers; i++) want.man[i] = d->maneuvers[i];
+  const bool fresh_tab = !e->drive_tab;
+  if (fresh_tab) HIP_TRY(e->drive_tab.alloc(1));
+  if (fresh_tab || memcmp(&want, &e->drive_host, sizeof(want)) != 0) {
+    // (in place: a graph captured earlier keeps reading this table; the copy waits for launches that may still read it.
+    // A call that only changes the pointers -- kernel arguments -- has nothing to wait for.)
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(e->drive_tab, &want, sizeof(want), hipMemcpyHostToDevice));
+    e->drive_host = want;
+  }
+  e->dr.tab = e->drive_tab;
+  e->dr.maneuver = d->n_maneuvers > 0 ? d->maneuver : nullptr;
+  e->dr.episode = d->n_maneuvers > 0 ? d->episode : nullptr;
+  e->dr.ou_state = d->ou_state;
+  e->dr.ou_draws = d->ou_state ? d->ou_draws : nullptr;
+  e->dr.man_rows = d->maneuver_rows;
+  e->dr.noise_rows = d->noise_rows;
+  e->drive_rows = (d->maneuver_rows || d->noise_rows) ? d->n_rows : 0;
+  e->drive_flags = (d->n_maneuvers > 0 ? TC_FI_DRIVE_MAN : 0u) | (d->ou_state ? TC_FI_DRIVE_OU : 0u);
+  return TC_OK;
+}
+
+extern "C" int tc_draw_normals(uint64_t seed, uint32_t env, uint32_t first_draw, int32_t n, double* out) {
+  if (n < 0 || (n > 0 && !out)) return TC_E_INVALID;
+  for (int32_t i = 0; i < n; i++) out[i] = tc_normal_at(seed, env, (first_draw + (uint32_t)i) & 0x7fffffffu);
   return TC_OK;
 }
 
@@ -4753,9 +4917,12 @@ static StepArgs step_args_at(const tc_env* e, const Call& c, int c0) {
   if (c.roll) sa.ma.roll = rollout_at(*c.roll, r0, (size_t)e->obs_bytes, (size_t)e->k.m.C);
   sa.mode = c.mode;
   sa.cdtype = c.cdtype;
-  sa.flags = (c.flags & ~TC_FI_CAM_BANK) | (e->cb.index ? TC_FI_CAM_BANK : 0u);
+  sa.dr = e->dr;  // (the rows likewise)
+  sa.dr.man_rows = ep_rows && e->dr.man_rows ? e->dr.man_rows + r0 : nullptr;
+  sa.dr.noise_rows = ep_rows && e->dr.noise_rows ? e->dr.noise_rows + r0 : nullptr;
+  sa.flags = (c.flags & ~(TC_FI_CAM_BANK | TC_FI_DRIVE)) | (e->cb.index ? TC_FI_CAM_BANK : 0u) | (e->dr.tab ? e->drive_flags : 0u);
   sa.car_control = c.cc ? (const char*)c.cc + r0 * 2 * (c.cdtype == TC_F32 ? 4 : 8) : nullptr;  // (NULL: a controller acts)
-  sa.maneuver = c.man + r0;
+  sa.maneuver = c.man ? c.man + r0 : nullptr;  // (NULL: the maneuvers are the device's, tc_env_set_drive_randomization)
   sa.spawn_nodes = c.spawn;
   sa.mask = c.mask;
   return sa;
@@ -5070,7 +5237,9 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
   int rc = check_stamp_buffer(e);
   if (rc != TC_OK) return rc;
   const unsigned feat = (e->cr.rows ? TC_FEAT_CAR : 0u) | (e->ep.length && mode != MODE_RENDER ? TC_FEAT_EP : 0u) |
-                        (e->ct.tab && mode == MODE_STEP ? TC_FEAT_CTRL : 0u);  // (the controller: the tc_drive_* entry points)
+                        (e->ct.tab && (mode == MODE_STEP || (mode == MODE_RESET && e->dr.tab)) ? TC_FEAT_CTRL : 0u);
+  // (the controller: the tc_drive_* entry points; a tc_reset takes them too while the drive randomisation is on: the
+  // re-spawn draws the episode's maneuver)
   Call c;  // (filled by name: the order of the fields is free to change)
   c.mode = mode; c.cc = cc; c.cdtype = cdtype; c.man = man; c.spawn = spawn; c.mask = mask; c.flags = flags;
   c.main = (hipStream_t)stream; c.nsteps = nsteps; c.roll = roll; c.ep_rows = ep_rows; c.feat = feat;
@@ -5113,14 +5282,16 @@ extern "C" int tc_reset(tc_env* e, const int32_t* spawn_nodes, const uint8_t* ma
 
 extern "C" int tc_step(tc_env* e, const void* car_control, int32_t control_dtype, const int32_t* maneuver,
                        uint32_t flags, void* stream) {
-  if (!maneuver || (control_dtype != TC_F32 && control_dtype != TC_F64)) return TC_E_INVALID;
+  if (control_dtype != TC_F32 && control_dtype != TC_F64) return TC_E_INVALID;
+  if (!maneuver && !(e && e->dr.tab && (e->drive_flags & TC_FI_DRIVE_MAN))) return TC_E_INVALID;  // (device maneuvers replace it)
   if (!car_control && !(e && e->ct.tab)) return TC_E_INVALID;  // (a built-in controller replaces the action)
   return launch(e, MODE_STEP, car_control, control_dtype, maneuver, nullptr, nullptr, flags, stream);
 }
 
 extern "C" int tc_step_multi(tc_env* e, const void* car_control, int32_t control_dtype, const int32_t* maneuver,
                              int32_t n_steps, uint32_t flags, const tc_rollout* rollout, void* stream) {
-  if (!e || !maneuver || (control_dtype != TC_F32 && control_dtype != TC_F64) || n_steps < 1) return TC_E_INVALID;
+  if (!e || (control_dtype != TC_F32 && control_dtype != TC_F64) || n_steps < 1) return TC_E_INVALID;
+  if (!maneuver && !(e->dr.tab && (e->drive_flags & TC_FI_DRIVE_MAN))) return TC_E_INVALID;  // (device maneuvers replace it)
   if (!car_control && !e->ct.tab) return TC_E_INVALID;  // (a built-in controller replaces the action)
   // (not left to launch(): the row checks below would answer first for an unbound handle whose rows are too short)
   if (!e->bound) {
@@ -5129,6 +5300,10 @@ extern "C" int tc_step_multi(tc_env* e, const void* car_control, int32_t control
   }
   if (e->ct.tab && (e->ct.noise || e->ct.rows) && n_steps > e->ctrl_rows) {
     set_err("tc_step_multi: more steps than the controller's rows hold (tc_env_set_controller)");
+    return TC_E_INVALID;
+  }
+  if (e->dr.tab && (e->dr.man_rows || e->dr.noise_rows) && n_steps > e->drive_rows) {
+    set_err("tc_step_multi: more steps than the drive randomisation's rows hold (tc_env_set_drive_randomization)");
     return TC_E_INVALID;
   }
   if (e->cb.index && e->cb.rows && n_steps > e->cam_rows) {

@@ -10,6 +10,11 @@ the library's [N, 8] rows and (lo, hi, mask) tables, with the validation both ne
 Cameras (``TinyCarloVecEnv.randomize_cameras``, ``tc_env_set_camera_bank``): ``camera_bank`` builds the bank -- every
 combination of the candidate values, each camera computed by ``Camera`` exactly as ``update_params`` does -- and
 ``draw_camera_index`` is ``tc_camera_index`` of ``csrc/tc_rng.h``: which camera of the bank an env's episode uses.
+
+Drive randomisation (``TinyCarloVecEnv.randomize_drive``, ``tc_env_set_drive_randomization``): ``draw_maneuver`` is the
+maneuver of an env's episode (``tc_maneuver_index``, or the cycle), ``draw_normal`` the env's normal numbers
+(``tc_normal_at``, evaluated by the library's host export ``tc_draw_normals``: its logarithm and cosine are the portable
+ones of ``csrc/tc_trig.h``, which numpy's are not bit for bit) and ``ou_step`` one step of the Ornstein-Uhlenbeck process.
 """
 from __future__ import annotations
 
@@ -23,6 +28,8 @@ CAR_COLUMNS = ("wheelbase", "track_width", "max_velocity", "max_steering_angle",
 CAR_NP = len(CAR_COLUMNS)
 CAR_STREAM = 0x636172  # "car": the sub-stream of the seed the draws come from (apart from the device spawn stream)
 CAM_STREAM = 0x63616D  # "cam": likewise for the camera index of an episode
+MAN_STREAM = 0x6D616E  # "man": likewise for the maneuver of an episode
+OU_STREAM = 0x6F75      # "ou": likewise for the normal numbers of the steering noise
 CAMERA_COLUMNS = ("pitch", "roll", "yaw", "fov", "x", "y", "z")  # columns of a camera bank's parameter table
 _GOLDEN, _M1, _M2 = np.uint64(0x9E3779B97F4A7C15), np.uint64(0xBF58476D1CE4E5B9), np.uint64(0x94D049BB133111EB)
 
@@ -197,3 +204,43 @@ def camera_bank(camera_cfg: Dict[str, Any], orientation=None, fov=None, position
         c = Camera(bank_camera_config(camera_cfg, params[m]))
         E[m], K[m] = c.E.reshape(-1), c.K.reshape(-1)
     return E, K, params
+
+
+def draw_maneuver(seed: int, env_index, episode, candidates: Sequence[int], mode: str = "draw") -> np.ndarray:
+    """The maneuver env `env_index` (global index) takes for episode `episode` (its value of the episode counter at the
+    re-spawn) from `candidates` (``tc_env_set_drive_randomization``): ``"draw"`` -- candidate number ``tc_maneuver_index`` of
+    ``csrc/tc_rng.h`` -- or ``"cycle"`` -- number (env_index + episode) mod len(candidates), the ``maneuver = (maneuver + 1) % 3``
+    of examples/train_stanley_il.py:105.  env_index / episode may be arrays (broadcast); returns int32."""
+    cand = np.asarray([int(c) for c in candidates], dtype=np.int32)
+    if cand.size < 1:
+        raise ValueError("draw_maneuver needs at least one candidate")
+    env = np.asarray(env_index, dtype=np.int64).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    ep = np.asarray(episode, dtype=np.int64).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    env, ep = np.broadcast_arrays(env, ep)
+    if mode == "cycle":
+        idx = ((env + ep) & np.uint64(0xFFFFFFFF)) % np.uint64(cand.size)
+    elif mode == "draw":
+        s2 = splitmix64_at(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), np.uint64(MAN_STREAM))
+        z = splitmix64_at(s2, (env << np.uint64(32)) | ep)
+        idx = ((z >> np.uint64(32)) * np.uint64(cand.size)) >> np.uint64(32)
+    else:
+        raise ValueError(f"mode must be 'draw' or 'cycle', got {mode!r}")
+    return cand[idx.astype(np.int64)]
+
+
+def draw_normal(seed: int, env_index: int, draw: int, n: Optional[int] = None):
+    """Normal number `draw` of env `env_index` (global index): ``tc_normal_at`` of ``csrc/tc_rng.h``, evaluated on the host by
+    the library (``tc_draw_normals``; no device needed).  With `n`: the float64 array of numbers draw .. draw + n - 1."""
+    import ctypes as C
+
+    from . import _native as nat
+    out = np.empty(1 if n is None else int(n), dtype=np.float64)
+    nat.check(nat.lib().tc_draw_normals(int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_index) & 0xFFFFFFFF, int(draw) & 0x7FFFFFFF,
+                                        out.size, out.ctypes.data_as(C.POINTER(C.c_double))), "tc_draw_normals")
+    return float(out[0]) if n is None else out
+
+
+def ou_step(n, eps, theta: float, mu: float, sigma: float):
+    """``noise += THETA * (MEAN - noise) + SIGMA * randn`` in the expression's order (``tc_ou_step``): float64, no fusing"""
+    n, eps = np.float64(n), np.float64(eps)
+    return n + (np.float64(theta) * (np.float64(mu) - n) + np.float64(sigma) * eps)

@@ -249,6 +249,9 @@ class TinyCarloVecEnv(gym.Env):
         self._ctrl: Optional[Dict[str, float]] = None
         self._ctrl_rows: Tuple[int, int, int] = (0, 0, 0)      # data pointers of the noise / steer rows installed last, rows
         self.steer_last: Optional[torch.Tensor] = None         # [N] f64: the controller's command of the last step
+        # drive randomisation (randomize_drive): settings and the four live device tensors, or None = off
+        self._drive: Optional[Dict[str, Any]] = None
+        self._drive_rows: Tuple[int, int, int] = (0, 0, 0)     # data pointers of the maneuver / noise rows installed last, rows
         # per-episode cameras (randomize_cameras): the bank's device tensors, settings and live index / episode, or None
         self._cam_bank: Optional[Dict[str, Any]] = None
         self._cam_rows: Tuple[int, int] = (0, 0)               # data pointer and rows of the index rows installed last
@@ -636,6 +639,7 @@ class TinyCarloVecEnv(gym.Env):
                 with torch.cuda.device(self.device):
                     nat.check(nat.lib().tc_env_set_controller(self._h, None), "tc_env_set_controller")
             self._ctrl, self._ctrl_rows, self.steer_last = None, (0, 0, 0), None
+            self._drive, self._drive_rows = None, (0, 0, 0)  # (the library drops the drive randomisation with the controller)
             return
         k, speed = float(k), float(speed)
         if not (np.isfinite(k) and np.isfinite(speed)):
@@ -661,50 +665,186 @@ class TinyCarloVecEnv(gym.Env):
         if want != self._ctrl_rows:
             self._push_controller(*want)
 
-    def drive(self, maneuver: torch.Tensor, rollout: Optional[Dict[str, torch.Tensor]] = None,
-              steer_noise: Optional[torch.Tensor] = None) -> None:
+    # ------------------------------------------------------------------ drive randomisation (per-episode maneuver, OU noise)
+    DRIVE_ROLLOUT_KEYS = ("maneuver", "steer_noise")
+    _MAN_MODES = {"draw": nat.MAN_DRAW, "cycle": nat.MAN_CYCLE}
+
+    def randomize_drive(self, maneuvers: Optional[Sequence[int]] = None, mode: str = "draw", ou: Optional[Dict[str, Any]] = None,
+                        seed: int = 0, env_offset: int = 0) -> None:
+        """Moves what examples/train_stanley_il.py and examples/train_td3.py do to the action at an episode boundary into the
+        simulate kernels (tc_env_set_drive_randomization), so that it follows the episodes of one ``drive`` call:
+        ``maneuvers`` -- candidates in {0, 1, 2, 3}, repeats act as weights -- makes the maneuver a per-episode quantity,
+        re-drawn (``mode="draw"``: ``randomization.draw_maneuver``) or advanced (``"cycle"``: train_stanley_il.py:105) at every
+        re-spawn, and ``drive`` / ``drive_step`` then take ``maneuver=None``; ``ou=dict(theta=0.1, mu=0.0, sigma=0.4,
+        reset=False)`` adds Ornstein-Uhlenbeck noise to the applied steering (train_stanley_il.py:66), back to 0 at every
+        re-spawn with ``reset=True`` (train_td3.py:177).  Either part may be left out; with neither the feature is off.
+        Live tensors: ``episode_maneuver``, ``drive_episode``, ``ou_state``, ``ou_draws``.  Rollout keys ``"maneuver"`` (the
+        one in force at each step: the ``Mn`` column) and ``"steer_noise"`` (the OU value applied).  Needs ``set_controller``."""
+        if maneuvers is None and ou is None:
+            if self._drive is not None:
+                with torch.cuda.device(self.device):
+                    nat.check(nat.lib().tc_env_set_drive_randomization(self._h, None), "tc_env_set_drive_randomization")
+            self._drive, self._drive_rows = None, (0, 0, 0)
+            return
+        if self._ctrl is None:
+            raise ValueError("randomize_drive() needs set_controller() first")
+        if not 0 <= int(env_offset) < 2 ** 32:
+            raise ValueError("env_offset must be in [0, 2^32)")
+        cand = [] if maneuvers is None else [int(m) for m in maneuvers]
+        if len(cand) > nat.MAX_MANEUVERS or any(m < 0 or m > 3 for m in cand) or (maneuvers is not None and not cand):
+            raise ValueError(f"maneuvers must be 1..{nat.MAX_MANEUVERS} values in 0..3, got {maneuvers!r}")
+        if mode not in self._MAN_MODES:
+            raise ValueError(f"mode must be 'draw' or 'cycle', got {mode!r}")
+        o = None
+        if ou is not None:
+            unknown = set(ou) - {"theta", "mu", "sigma", "reset"}
+            if unknown:
+                raise ValueError(f"unknown ou settings {sorted(unknown)}")
+            o = {"theta": float(ou.get("theta", 0.1)), "mu": float(ou.get("mu", 0.0)), "sigma": float(ou.get("sigma", 0.4)),
+                 "reset": bool(ou.get("reset", False))}
+            if not all(np.isfinite(o[k]) for k in ("theta", "mu", "sigma")):
+                raise ValueError(f"theta, mu and sigma must be finite, got {ou!r}")
+        old = self._drive
+        N, dev = self.num_envs, self.device
+        keep = lambda k, dt: old[k] if old is not None else torch.zeros(N, dtype=dt, device=dev)  # noqa: E731
+        self._drive = {"maneuvers": tuple(cand), "mode": mode, "ou": o, "seed": int(seed) & 0xFFFFFFFFFFFFFFFF,
+                       "env_offset": int(env_offset),
+                       "maneuver": keep("maneuver", torch.int32), "episode": keep("episode", torch.int32),
+                       "ou_state": keep("ou_state", torch.float64), "ou_draws": keep("ou_draws", torch.int32)}
+        self._push_drive(0, 0, 0)  # (the rows belong to a call: the next drive installs its own)
+
+    def set_ou(self, theta: Optional[float] = None, mu: Optional[float] = None, sigma: Optional[float] = None,
+               reset: Optional[bool] = None) -> None:
+        """New OU settings in place (``sigma``: the annealing of train_td3.py:179); they reach a captured HIP graph without
+        re-capture.  The OU state and the draw counters keep their values."""
+        if self._drive is None or self._drive["ou"] is None:
+            raise ValueError("set_ou() needs randomize_drive(ou=...) first")
+        o = dict(self._drive["ou"])
+        for k, v in (("theta", theta), ("mu", mu), ("sigma", sigma)):
+            if v is not None:
+                if not np.isfinite(float(v)):
+                    raise ValueError(f"{k} must be finite, got {v}")
+                o[k] = float(v)
+        if reset is not None:
+            o["reset"] = bool(reset)
+        self._drive["ou"] = o
+        self._push_drive(*self._drive_rows)
+
+    def _push_drive(self, man_ptr: int, noise_ptr: int, n_rows: int) -> None:
+        d, c = self._drive, nat.DriveRandomizationC()
+        c.seed, c.env_offset, c.n_maneuvers = d["seed"], d["env_offset"], len(d["maneuvers"])
+        for i, m in enumerate(d["maneuvers"]):
+            c.maneuvers[i] = m
+        c.maneuver_mode = self._MAN_MODES[d["mode"]]
+        o = d["ou"]
+        if o is not None:
+            c.theta, c.mu, c.sigma, c.ou_reset = o["theta"], o["mu"], o["sigma"], int(o["reset"])
+            c.ou_state, c.ou_draws = d["ou_state"].data_ptr(), d["ou_draws"].data_ptr()
+        if d["maneuvers"]:
+            c.maneuver, c.episode = d["maneuver"].data_ptr(), d["episode"].data_ptr()
+        c.maneuver_rows, c.noise_rows = man_ptr or None, noise_ptr or None
+        c.n_rows = n_rows if (man_ptr or noise_ptr) else 0
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().tc_env_set_drive_randomization(self._h, C.byref(c)), "tc_env_set_drive_randomization")
+        self._drive_rows = (man_ptr, noise_ptr, n_rows)
+
+    def _install_drive_rows(self, rollout: Optional[Dict[str, torch.Tensor]], K: int) -> None:
+        """the maneuver / noise rows of the call about to be issued (host-side bookkeeping only: the settings do not change)"""
+        mr = rollout.get("maneuver") if rollout else None
+        nr = rollout.get("steer_noise") if rollout else None
+        want = (mr.data_ptr() if mr is not None else 0, nr.data_ptr() if nr is not None else 0, K)
+        if not (want[0] or want[1]):
+            want = (0, 0, 0)
+        if want != self._drive_rows:
+            self._push_drive(*want)
+
+    @property
+    def _device_maneuvers(self) -> bool:
+        return self._drive is not None and len(self._drive["maneuvers"]) > 0
+
+    @property
+    def episode_maneuver(self) -> Optional[torch.Tensor]:
+        """[N] int32, live: the maneuver in force for each env (randomize_drive with maneuvers), else None"""
+        return self._drive["maneuver"] if self._device_maneuvers else None
+
+    @property
+    def drive_episode(self) -> Optional[torch.Tensor]:
+        """[N] int32, live: maneuvers drawn so far"""
+        return self._drive["episode"] if self._device_maneuvers else None
+
+    @property
+    def ou_state(self) -> Optional[torch.Tensor]:
+        """[N] float64, live and writable: the OU value each env applied last (randomize_drive with ou), else None"""
+        return self._drive["ou_state"] if self._drive is not None and self._drive["ou"] is not None else None
+
+    @property
+    def ou_draws(self) -> Optional[torch.Tensor]:
+        """[N] int32, live: normals consumed so far (never reset)"""
+        return self._drive["ou_draws"] if self._drive is not None and self._drive["ou"] is not None else None
+
+    def drive(self, maneuver: Optional[torch.Tensor], rollout: Optional[Dict[str, torch.Tensor]] = None,
+              steer_noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None) -> None:
         """K closed-loop steps in ONE call: ``step_multi`` with every step's action computed on the device by the
         controller of ``set_controller``.  maneuver [K, N] int32; steer_noise [K, N] float64 (optional) is added to the
         command of step k before it is applied (the exploration noise of examples/train_stanley_il.py's data
         collection); ``rollout["steer"]`` (``alloc_rollout(K, keys=(..., "steer"))``) receives the command BEFORE noise,
         the imitation-learning label.  Bit-identical to K ``step_device`` calls with the action computed on the host from
-        ``out["cte"]`` / ``out["heading_error"]`` before each."""
-        self.prepare_drive(maneuver, rollout, steer_noise)()
+        ``out["cte"]`` / ``out["heading_error"]`` before each.  With ``randomize_drive(maneuvers=...)`` the maneuvers are the
+        device's own: ``maneuver`` is None and the number of steps comes from ``n_steps``, the rollout or ``steer_noise``."""
+        self.prepare_drive(maneuver, rollout, steer_noise, n_steps)()
 
-    def prepare_drive(self, maneuver: torch.Tensor, rollout: Optional[Dict[str, torch.Tensor]] = None,
-                      steer_noise: Optional[torch.Tensor] = None) -> "PreparedStepMulti":
+    def prepare_drive(self, maneuver: Optional[torch.Tensor], rollout: Optional[Dict[str, torch.Tensor]] = None,
+                      steer_noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None) -> "PreparedStepMulti":
         """`drive` as a checked, reusable call object (see `prepare_step_multi`); its rows are installed at once, so the
         object can be captured into a HIP graph right away."""
         if self._ctrl is None:
             raise RuntimeError("drive() needs set_controller() first")
-        if maneuver.dim() != 2 or int(maneuver.shape[0]) < 1 or int(maneuver.shape[1]) != self.num_envs:
-            raise ValueError(f"maneuver must be [K, {self.num_envs}], got {tuple(maneuver.shape)}")
-        K = int(maneuver.shape[0])
-        if maneuver.device != self.device or maneuver.dtype != torch.int32 or not maneuver.is_contiguous():
-            raise ValueError("drive takes a contiguous int32 device tensor as maneuver")
+        if maneuver is None:
+            if not self._device_maneuvers:
+                raise ValueError("drive(maneuver=None) needs randomize_drive(maneuvers=...) first")
+            K = int(n_steps) if n_steps is not None else (int(steer_noise.shape[0]) if steer_noise is not None else
+                                                         (int(next(iter(rollout.values())).shape[0]) if rollout else 0))
+            if K < 1:
+                raise ValueError("drive(maneuver=None) takes its number of steps from n_steps, the rollout or steer_noise")
+        else:
+            if maneuver.dim() != 2 or int(maneuver.shape[0]) < 1 or int(maneuver.shape[1]) != self.num_envs:
+                raise ValueError(f"maneuver must be [K, {self.num_envs}], got {tuple(maneuver.shape)}")
+            K = int(maneuver.shape[0])
+            if maneuver.device != self.device or maneuver.dtype != torch.int32 or not maneuver.is_contiguous():
+                raise ValueError("drive takes a contiguous int32 device tensor as maneuver")
+            if n_steps is not None and int(n_steps) != K:
+                raise ValueError(f"n_steps = {n_steps} does not fit maneuver rows of {K} steps")
         if steer_noise is not None and (tuple(steer_noise.shape) != (K, self.num_envs) or steer_noise.dtype != torch.float64 or
                                         steer_noise.device != self.device or not steer_noise.is_contiguous()):
             raise ValueError(f"steer_noise must be a contiguous float64 tensor of shape ({K}, {self.num_envs}) on {self.device}")
         r = self._check_rollout(rollout, K)
         call = PreparedStepMulti(self, None, maneuver, rollout, r, K, steer_noise)
         self._install_ctrl_rows(steer_noise, rollout, K)
+        if self._drive is not None:
+            self._install_drive_rows(rollout, K)
         if self._cam_bank is not None:
             self._install_camera_rows(rollout, K)
         return call
 
-    def drive_step(self, maneuver: torch.Tensor) -> None:
+    def drive_step(self, maneuver: Optional[torch.Tensor] = None) -> None:
         """One closed-loop step (tc_step with the controller's action): `step_device` without a car_control."""
         if self._ctrl is None:
             raise RuntimeError("drive_step() needs set_controller() first")
         if not self._was_reset:
             raise RuntimeError("step() before reset()")
-        if (tuple(maneuver.shape) != (self.num_envs,) or maneuver.device != self.device or maneuver.dtype != torch.int32 or
+        if maneuver is None:
+            if not self._device_maneuvers:
+                raise ValueError("drive_step(maneuver=None) needs randomize_drive(maneuvers=...) first")
+        elif (tuple(maneuver.shape) != (self.num_envs,) or maneuver.device != self.device or maneuver.dtype != torch.int32 or
                 not maneuver.is_contiguous()):
             raise ValueError(f"drive_step takes a contiguous int32 device tensor of shape ({self.num_envs},) as maneuver")
         self._note_fresh()
         self._install_ctrl_rows(None, None, 0)
+        if self._drive is not None:
+            self._install_drive_rows(None, 0)
         with torch.cuda.device(self.device):
-            nat.check(nat.lib().tc_step(self._h, None, nat.F64, maneuver.data_ptr(), self._flags(), self._stream()), "tc_step")
+            nat.check(nat.lib().tc_step(self._h, None, nat.F64, maneuver.data_ptr() if maneuver is not None else None,
+                                        self._flags(), self._stream()), "tc_step")
         self._keep = (maneuver,)
         self._step_serial += 1
 
@@ -894,6 +1034,8 @@ class TinyCarloVecEnv(gym.Env):
         self._note_fresh()
         if self._ctrl is not None:  # (a controller acts: the rows of an earlier drive call are not this step's)
             self._install_ctrl_rows(None, None, 0)
+            if self._drive is not None:
+                self._install_drive_rows(None, 0)
         dt = nat.F64 if car_control.dtype == torch.float64 else nat.F32
         with torch.cuda.device(self.device):
             nat.check(nat.lib().tc_step(self._h, car_control.data_ptr(), dt, maneuver.data_ptr(), self._flags(),
@@ -925,7 +1067,7 @@ class TinyCarloVecEnv(gym.Env):
                 "velocity": ((K, N), f64), "laneline_distances": ((K, N, Cn), f64), "nearest_edge": ((K, N, Cn), i32),
                 "local_path": ((K, N, 8), i32), "lp_len": ((K, N), i32),
                 "episode_length": ((K, N), i32), "episode_return": ((K, N), f64), "steer": ((K, N), f64),
-                "camera": ((K, N), i32)}
+                "camera": ((K, N), i32), "maneuver": ((K, N), i32), "steer_noise": ((K, N), f64)}
 
     def reserve_steps(self, n_steps: int) -> None:
         """Sizes the library's scratch ring for K-step calls that render observations (tc_env_reserve_steps): done
@@ -943,17 +1085,20 @@ class TinyCarloVecEnv(gym.Env):
         if keys == "all":  # (the episode rows only while the accounting is on, the controller's while one is installed)
             keys = self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS + (self.EPISODE_ROLLOUT_KEYS if self._episodes is not None else ()) + \
                 (self.CTRL_ROLLOUT_KEYS if self._ctrl is not None else ()) + \
-                (self.CAMERA_ROLLOUT_KEYS if self._cam_bank is not None else ())
+                (self.CAMERA_ROLLOUT_KEYS if self._cam_bank is not None else ()) + \
+                (self.DRIVE_ROLLOUT_KEYS if self._drive is not None else ())
         for k in keys:
             if k not in shapes:
                 raise ValueError(f"unknown rollout key {k!r}; choose from "
-                                 f"{self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS + self.EPISODE_ROLLOUT_KEYS + self.CTRL_ROLLOUT_KEYS + self.CAMERA_ROLLOUT_KEYS}")
+                                 f"{self.ROLLOUT_KEYS + self.INFO_ROLLOUT_KEYS + self.EPISODE_ROLLOUT_KEYS + self.CTRL_ROLLOUT_KEYS + self.CAMERA_ROLLOUT_KEYS + self.DRIVE_ROLLOUT_KEYS}")
             if k in self.EPISODE_ROLLOUT_KEYS and self._episodes is None:
                 raise ValueError(f"rollout key {k!r} needs track_episodes() / set_time_limit() first")
             if k in self.CTRL_ROLLOUT_KEYS and self._ctrl is None:
                 raise ValueError(f"rollout key {k!r} needs set_controller() first")
             if k in self.CAMERA_ROLLOUT_KEYS and self._cam_bank is None:
                 raise ValueError(f"rollout key {k!r} needs randomize_cameras() first")
+            if k in self.DRIVE_ROLLOUT_KEYS and self._drive is None:
+                raise ValueError(f"rollout key {k!r} needs randomize_drive() first")
         return {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=dev) for k in keys}
 
     def rollout_info(self, rollout: Dict[str, torch.Tensor], k: int) -> Dict[str, Any]:
@@ -1030,6 +1175,10 @@ class TinyCarloVecEnv(gym.Env):
                     if self._cam_bank is None:
                         raise ValueError(f"rollout[{k!r}] needs randomize_cameras() first")
                     continue
+                if k in self.DRIVE_ROLLOUT_KEYS:  # likewise: installed per call (tc_env_set_drive_randomization)
+                    if self._drive is None:
+                        raise ValueError(f"rollout[{k!r}] needs randomize_drive() first")
+                    continue
                 setattr(r, k, t.data_ptr())
         if K > 1 and not (self.no_observation and self.render_mode is None):
             self.reserve_steps(K)  # (no-op once the scratch covers K: the call itself never allocates)
@@ -1080,7 +1229,11 @@ class TinyCarloVecEnv(gym.Env):
                     "per_env": None if self._time_limit_per_env is None else self._time_limit_per_env.detach().cpu().clone(),
                     "stats": {k: v.detach().cpu().clone() for k, v in self._episodes.items()}},
                 # built-in controller: its gains
-                "controller": None if self._ctrl is None else dict(self._ctrl)}
+                "controller": None if self._ctrl is None else dict(self._ctrl),
+                # drive randomisation: the settings and the four live tensors
+                "drive_randomization": None if self._drive is None else {
+                    k: (v.detach().cpu().clone() if isinstance(v, torch.Tensor) else (dict(v) if isinstance(v, dict) else v))
+                    for k, v in self._drive.items()}}
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
         if int(sd["num_envs"]) != self.num_envs:
@@ -1128,6 +1281,15 @@ class TinyCarloVecEnv(gym.Env):
             self.set_controller(None)
         else:
             self.set_controller(k=ctl["k"], speed=ctl["speed"])
+        drv = sd.get("drive_randomization")  # (absent in older checkpoints: off)
+        if drv is None or ctl is None:
+            self.randomize_drive()
+        else:
+            ou = drv["ou"]
+            self.randomize_drive(maneuvers=drv["maneuvers"] or None, mode=drv["mode"], ou=None if ou is None else dict(ou),
+                                 seed=drv["seed"], env_offset=drv["env_offset"])
+            for k in ("maneuver", "episode", "ou_state", "ou_draws"):
+                self._drive[k].copy_(drv[k])
         bank = sd.get("camera_bank")  # (present only when a bank was installed)
         if bank is None:
             if self._cam_bank is not None:
@@ -1234,7 +1396,8 @@ class PreparedStepMulti:
         self._noise = steer_noise                       # `prepare_drive`: the controller's noise rows (car_control None)
         self._rollout_ref = r
         dt = nat.F32 if car_control is not None and car_control.dtype == torch.float32 else nat.F64
-        self._args = (car_control.data_ptr() if car_control is not None else None, dt, maneuver.data_ptr(), K,
+        self._args = (car_control.data_ptr() if car_control is not None else None, dt,
+                      maneuver.data_ptr() if maneuver is not None else None, K,
                       C.byref(r) if rollout else None)
 
     def __call__(self) -> None:
@@ -1253,8 +1416,12 @@ class PreparedStepMulti:
             env._install_episode_rows(self._keep[2], self.K)
         if env._ctrl is not None:
             env._install_ctrl_rows(self._noise, self._keep[2], self.K)
+            if env._drive is not None:
+                env._install_drive_rows(self._keep[2], self.K)
         elif a[0] is None:
             raise RuntimeError("a drive() call needs the controller it was prepared with (set_controller)")
+        if a[2] is None and not env._device_maneuvers:
+            raise RuntimeError("a drive(maneuver=None) call needs the device maneuvers it was prepared with (randomize_drive)")
         if env._cam_bank is not None:
             env._install_camera_rows(self._keep[2], self.K)
         if torch.cuda.current_device() == env.device.index:
