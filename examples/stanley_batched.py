@@ -4,7 +4,7 @@
 controller reads cte / heading_error from the env's device tensors and writes the action tensor, the reference's
 wrappers (CTE sparse reward, CTE and crash termination) run inside the step kernel, finished envs re-spawn on the device.
 
-    python examples/stanley_batched.py [--envs 4096] [--steps 600] [--maneuver 3] [--randomize] [--max-episode-steps N] [--fused K [--packed] [--randomize-cameras] [--explore]]
+    python examples/stanley_batched.py [--envs 4096] [--steps 600] [--maneuver 3] [--randomize] [--max-episode-steps N] [--fused K [--packed] [--randomize-cameras] [--explore] [--collect CAP]]
 
 --randomize: every episode of every env drives its own car, drawn on the device at the re-spawn (wheelbase, track width,
 speed and steering limits within +-20 %), plus the steering shift of the reference's TD3 study (examples/train_td3.py:37,
@@ -33,6 +33,12 @@ With --max-episode-steps, so that episodes end, this is that data collection ent
 cycles through (0, 1, 3) at every re-spawn (train_stanley_il.py:105), and Ornstein-Uhlenbeck noise (theta 0.1, sigma 0.4,
 carried across episodes, train_stanley_il.py:66) is added to the applied steering; the maneuver in force at each step comes
 back in the rollout's "maneuver" rows (the Mn column), and the share of each among the collected frames is printed.
+
+--collect CAP (with --fused K): the script's dataset itself (train_stanley_il.py:61-77, 100-110) -- a device sample buffer of CAP
+samples (vec.make_sample_buffer) takes every call's rows: the frame before a step with that step's steering command and
+maneuver, every SKIP_STEPS = 2nd action step of an episode, until the buffer is full (overflow="stop").  The maneuver column
+exists only with --explore (without it the maneuver is the one constant of --maneuver and no rollout rows carry it: the buffer
+then holds obs and steer).  Samples kept and dropped and, with --explore, the maneuver shares among the samples are printed.
 """
 import argparse
 import math
@@ -49,7 +55,7 @@ from tinycarlo_amd.wrapper import CrashTerminationWrapper, CTESparseRewardWrappe
 
 
 def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0", seed=2, randomize=False,
-        max_episode_steps=None, fused=0, packed=False, randomize_cameras=False, explore=False):
+        max_episode_steps=None, fused=0, packed=False, randomize_cameras=False, explore=False, collect=0):
     config = bundled_config("config_simple_layout.yaml")
     if packed:  # packing is for class masks: the bundled config with that format
         if not fused:
@@ -69,6 +75,8 @@ def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0",
                            | {"steering_shift": (-0.01, 0.0)}, seed=seed)
     if explore and not fused:
         raise ValueError("--explore goes with --fused K (the device's maneuvers and noise belong to the built-in controller)")
+    if collect and not fused:
+        raise ValueError("--collect goes with --fused K (the samples are taken from the rows of a call)")
     if randomize_cameras:
         if not fused:
             raise ValueError("--randomize-cameras goes with --fused K (the camera of a frame comes back in the rollout rows)")
@@ -99,14 +107,20 @@ def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0",
         prepared = {}
         for n in set(calls):  # (a shorter last call has rows of its own)
             roll = vec.alloc_rollout(n, keys=("obs", "reward", "terminated", "truncated", "cte") + (("camera",) if randomize_cameras else ()) +
-                                     (("maneuver",) if explore else ()))
+                                     (("maneuver",) if explore else ()) + (("steer",) if collect else ()))
             prepared[n] = (vec.prepare_drive(None if explore else man.expand(n, num_envs).contiguous(), roll), roll)
+        if collect:  # the script's dataset: SKIP_STEPS = 2, stop at BUFFER_SIZE (without --explore the maneuver is one constant: no column)
+            buf = vec.make_sample_buffer(collect, columns=("maneuver", "steer") if explore else ("steer",), stride=2, overflow="stop",
+                                         max_rows=max(calls))
+            buf.begin(vec.out["obs"])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if fused:
         for n in calls:
             call, roll = prepared[n]
             call()                                                    # n closed-loop steps, frames into roll["obs"]
+            if collect:
+                buf.collect(roll)                                     # (obs before the step, maneuver, steer) samples, on the device
             ret += roll["reward"].sum(0)
             cte_abs += roll["cte"].abs().mean(1).sum()
             ended += (roll["terminated"] | roll["truncated"]).sum()
@@ -143,6 +157,12 @@ def run(num_envs=4096, steps=600, maneuver=3, k=4.0, speed=0.4, device="cuda:0",
         tot = max(int(man_frames.sum()), 1)
         out.update(maneuver_share={m: round(int(man_frames[m]) / tot, 4) for m in range(4) if int(man_frames[m])},
                    maneuver_episodes_drawn=int(vec.drive_episode.sum()), normals_consumed=int(vec.ou_draws.sum()))
+    if collect:
+        kept = len(buf)
+        out.update(samples_kept=kept, samples_dropped=buf.dropped, sample_buffer_full=buf.full)
+        if explore and kept:
+            share = torch.bincount(buf.cols["maneuver"][:kept].long(), minlength=4)[:4]
+            out["sample_maneuver_share"] = {m: round(int(share[m]) / kept, 4) for m in range(4) if int(share[m])}
     if max_episode_steps:
         es = vec.episode_stats
         n_ep = int(es["count"].sum())
@@ -163,6 +183,7 @@ if __name__ == "__main__":
     ap.add_argument("--packed", action="store_true", help="with --fused: bit-packed class-mask frames, unpacked in batches")
     ap.add_argument("--randomize-cameras", action="store_true", help="with --fused: per-episode pitch / fov from a 400-camera bank")
     ap.add_argument("--explore", action="store_true", help="with --fused: per-episode maneuvers (0, 1, 3) in turn and OU steering noise")
+    ap.add_argument("--collect", type=int, default=0, metavar="CAP", help="with --fused: a device sample buffer of CAP (obs, maneuver, steer) samples")
     a = ap.parse_args()
     print(run(a.envs, a.steps, a.maneuver, randomize=a.randomize, max_episode_steps=a.max_episode_steps, fused=a.fused,
-              packed=a.packed, randomize_cameras=a.randomize_cameras, explore=a.explore))
+              packed=a.packed, randomize_cameras=a.randomize_cameras, explore=a.explore, collect=a.collect))

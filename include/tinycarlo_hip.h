@@ -58,6 +58,8 @@ extern "C" {
 #define TC_HAS_CAMERA_BANK 1
 /* Likewise additive within ABI 6: tc_env_set_drive_randomization, tc_drive_randomization, TC_MAN_*, tc_draw_normals. */
 #define TC_HAS_DRIVE_RANDOMIZATION 1
+/* Likewise additive within ABI 6: tc_collect, tc_collect_scratch_bytes, tc_collect_desc, TC_COLLECT_*. */
+#define TC_HAS_COLLECT 1
 #define TC_MAX_LAYERS 16
 
 /* error codes */
@@ -585,6 +587,70 @@ int tc_render(tc_env* env, uint32_t flags, void* stream);
  * index == NULL with n_out > n_src_frames, a misaligned pointer. */
 int tc_unpack_bits(const uint8_t* packed, int64_t n_src_frames, int32_t planes, int32_t H, int32_t W, const int64_t* index,
                    int64_t n_out, void* dst, int32_t dst_dtype, void* stream);
+
+/* Sample buffer: turns the [K][N] rows of one K-step call into dataset samples on the device -- the Xn / Mn / Yn fill of
+ * examples/train_stanley_il.py:61-77,100-110 and Replaybuffer.add of examples/rl_utils.py:13-30.  Needs no env handle.
+ * The executable definition is collect_reference of tinycarlo_amd/collect.py; tinycarlo_amd/csrc/tc_collect.h holds the rules.
+ *
+ * Per env n the caller keeps pending[n] (u8: the env's next row is a re-spawn row), age[n] (i32: action steps of the
+ * running episode) and last[n] (one frame: the observation the next action is computed from).  Rows are visited k outer,
+ * n inner:
+ *   1. pending[n]: a re-spawn row (TC_F_AUTORESET applied no action): no sample, age[n] = 0.
+ *   2. else i = age[n]++; if i % stride == 0 the row is a candidate: obs = last[n], next_obs = obs_rows[k][n], env = n and
+ *      every column's value of (k, n).
+ *   3. pending[n] = terminated[k][n] | truncated[k][n] (either may be NULL), last[n] = obs_rows[k][n].
+ * Candidates take ordinals counters[TC_COLLECT_NEXT], +1, ... in visiting order.  Ordinal o < capacity goes to slot o; beyond
+ * that TC_COLLECT_STOP drops it (and counts it), TC_COLLECT_RING takes slot o % capacity, TC_COLLECT_RANDOM the counter-based
+ * draw of tc_rng.h (sub-stream "rep" of `seed`, ordinal o).  Where candidates of one call share a slot the highest ordinal
+ * wins, as in a sequential loop; ordinal[slot] records what a slot holds (-1 = empty; the caller initialises it).
+ *
+ * A frame is frame_bytes opaque bytes (packed bits, byte class masks, rgb), frame_bytes % 4 == 0; copies move 16 bytes per
+ * lane when frame_bytes % 16 == 0 and obs, next_obs, last and obs_rows are 16-byte aligned, 4 bytes otherwise.
+ * Every pointer is a device pointer.  counters: int64[4] = filled slots, next ordinal, dropped, candidates of the last call.
+ * scratch: at least tc_collect_scratch_bytes bytes for (n_rows, num_envs), 16-byte aligned, contents free between calls.
+ * Neither allocates nor synchronises: everything is enqueued on `stream` in order, every counter lives on the device, and
+ * the call can be captured into a HIP graph (a replay advances the buffer like a fresh call over the rows' contents).
+ * TC_E_INVALID with tc_last_error() text, before any HIP call: a NULL required pointer, a non-positive size, stride < 1,
+ * frame_bytes % 4 != 0, a misaligned pointer, an element size not in {1, 4, 8}, more than TC_COLLECT_MAX_COLUMNS columns, an
+ * unknown mode, capacity >= 2^32 with TC_COLLECT_RANDOM, n_rows * num_envs >= 2^26 (the copy launch
+ * runs one wavefront per (row, env)), a scratch that is too small. */
+#define TC_COLLECT_STOP 0
+#define TC_COLLECT_RING 1
+#define TC_COLLECT_RANDOM 2
+#define TC_COLLECT_MAX_COLUMNS 8
+#define TC_COLLECT_COUNT 0     /* indices into the counter block */
+#define TC_COLLECT_NEXT 1
+#define TC_COLLECT_DROPPED 2
+#define TC_COLLECT_LAST_CALL 3
+typedef struct {
+  const void* src;   /* [n_rows][num_envs] elements of this call */
+  void* dst;         /* [capacity] elements */
+  int32_t elem_size; /* 1, 4 or 8 bytes; src and dst aligned to it */
+  int32_t reserved;
+} tc_collect_column;
+typedef struct {
+  int64_t capacity;
+  int32_t num_envs;
+  int32_t stride;
+  int32_t mode; /* TC_COLLECT_* */
+  int32_t n_columns;
+  uint64_t seed;
+  int64_t frame_bytes;
+  uint8_t* obs;      /* [capacity][frame_bytes] */
+  uint8_t* next_obs; /* likewise, or NULL */
+  int64_t* ordinal;  /* [capacity] */
+  int32_t* env;      /* [capacity] */
+  tc_collect_column columns[TC_COLLECT_MAX_COLUMNS];
+  uint8_t* pending; /* [num_envs] */
+  int32_t* age;     /* [num_envs] */
+  uint8_t* last;    /* [num_envs][frame_bytes] */
+  int64_t* counters;
+  void* scratch;
+  int64_t scratch_bytes;
+} tc_collect_desc;
+int64_t tc_collect_scratch_bytes(int32_t n_rows, int32_t num_envs);
+int tc_collect(const tc_collect_desc* desc, int32_t n_rows, const uint8_t* obs_rows, const uint8_t* terminated,
+               const uint8_t* truncated, void* stream);
 
 #ifdef __cplusplus
 }

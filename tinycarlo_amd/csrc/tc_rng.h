@@ -76,6 +76,15 @@ TC_HD double tc_ou_step(double n, double eps, double theta, double mu, double si
   return n + (theta * (mu - n) + sigma * eps);
 }
 
+// Sample buffer (tc_collect, tc_collect.h), overflow mode "random": the candidate with ordinal `o` (>= capacity) replaces slot
+// tc_replace_slot of `capacity` (0 < capacity < 2^32) -- the np.random.randint(0, size) of examples/rl_utils.py:20 as a
+// counter-based draw: the high 32 bits of output `o` of s' = SplitMix64(seed)[0x726570] ("rep"), scaled by capacity as in
+// tc_camera_index.
+TC_HD uint32_t tc_replace_slot(uint64_t seed, uint64_t o, uint32_t capacity) {
+  const uint64_t z = tc_splitmix64_at(tc_splitmix64_at(seed, 0x726570ull), o);
+  return (uint32_t)(((z >> 32) * (uint64_t)capacity) >> 32);
+}
+
 // One blob of NoiseObservationWrapper (wrapper/observation.py:18-20): centre (x, y) inside the frame, radius in
 // [1, max_radius), mode 1 = "copy in" with probability 0.3 (else erase), src = the plane copied from.  Blob k of
 // (env, step) takes two outputs of the sub-stream SplitMix64(seed)[env << 32 | step].  The reference draws these

@@ -7,6 +7,7 @@
 //   k_probe.h    timing / marker probes and the ablation switches (in no shipped kernel)
 //   k_common.h   LDS layout, the env's LiveLds record, KArgs / MultiArgs, wavefront helpers
 //   k_feat.h     reward / termination terms, per-env cars, camera bank, episodes, controller (the FEAT template mask)
+//   k_collect.h  the sample buffer's kernels (tc_collect: scan, rank, claim, copy); no env handle, no template
 // The kernel stages follow in this file, each with its own argument block (RArgs, StepArgs, FrameArgs, NArgs), then the
 // host side (from `// Host side: C ABI` down):
 //   camera       phase C  transform -> 4 clip passes -> project -> visibility -> draw list (camera.py:52-110)
@@ -54,6 +55,7 @@
 #include "k_probe.h"
 #include "k_common.h"
 #include "k_feat.h"
+#include "k_collect.h"
 
 // ---------------------------------------------------------------------------------------------
 // Per-lane register cache of the map: lane `tid` keeps nodes / edges (w*K + k)*64 + tid, k < K, of window w.
@@ -5423,6 +5425,62 @@ extern "C" int tc_unpack_bits(const uint8_t* packed, int64_t n_src_frames, int32
     case TC_BF16: hipLaunchKernelGGL(tc_unpack_bits_kernel<TC_BF16>, grid, block, 0, st, src, (long long)n_src_frames, frame_words, idx, (long long)n_out, (uint4*)dst); break;
     default: hipLaunchKernelGGL(tc_unpack_bits_kernel<TC_F32>, grid, block, 0, st, src, (long long)n_src_frames, frame_words, idx, (long long)n_out, (uint4*)dst); break;
   }
+  HIP_TRY(hipGetLastError());
+  return TC_OK;
+}
+
+extern "C" int64_t tc_collect_scratch_bytes(int32_t n_rows, int32_t num_envs) { return tc_collect_scratch_size(n_rows, num_envs); }
+
+extern "C" int tc_collect(const tc_collect_desc* d, int32_t n_rows, const uint8_t* obs_rows, const uint8_t* terminated,
+                          const uint8_t* truncated, void* stream) {
+  // (every check comes before the first HIP call: a bad argument is reported on a machine without a device too)
+  auto bad = [](const char* what) {
+    set_err(std::string("tc_collect: ") + what);
+    return TC_E_INVALID;
+  };
+  auto mis = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (!d) return bad("NULL descriptor");
+  if (!obs_rows || !d->obs || !d->ordinal || !d->env || !d->pending || !d->age || !d->last || !d->counters || !d->scratch)
+    return bad("obs_rows, obs, ordinal, env, pending, age, last, counters and scratch are required");
+  if (n_rows < 1 || d->capacity < 1 || d->num_envs < 1 || d->frame_bytes < 1) return bad("n_rows, capacity, num_envs and frame_bytes must be positive");
+  // (tc_collect_copy runs one wavefront per (row, env): 2^26 pairs would be a grid of 2^32 threads, which a launch refuses --
+  // and by then the scan and rank launches would have moved the carry and the counters)
+  if ((int64_t)n_rows * d->num_envs >= (1ll << 26)) return bad("n_rows * num_envs must be below 2^26");
+  if (d->stride < 1) return bad("stride must be at least 1");
+  if (d->frame_bytes % 4 != 0) return bad("frame_bytes must be a multiple of 4");
+  if (d->mode != TC_COLLECT_STOP && d->mode != TC_COLLECT_RING && d->mode != TC_COLLECT_RANDOM) return bad("unknown mode");
+  if (d->mode == TC_COLLECT_RANDOM && d->capacity >= (1ll << 32)) return bad("TC_COLLECT_RANDOM needs capacity < 2^32");
+  if (d->n_columns < 0 || d->n_columns > TC_COLLECT_MAX_COLUMNS) return bad("at most TC_COLLECT_MAX_COLUMNS columns");
+  for (int j = 0; j < d->n_columns; j++) {
+    const tc_collect_column& c = d->columns[j];
+    if (c.elem_size != 1 && c.elem_size != 4 && c.elem_size != 8) return bad("a column's element size must be 1, 4 or 8");
+    if (!c.src || !c.dst) return bad("a column needs src and dst");
+    if (mis(c.src, (uintptr_t)c.elem_size) || mis(c.dst, (uintptr_t)c.elem_size)) return bad("a column's src and dst must be aligned to its element size");
+  }
+  if (mis(obs_rows, 4) || mis(d->obs, 4) || mis(d->last, 4) || (d->next_obs && mis(d->next_obs, 4))) return bad("frames must be 4-byte aligned");
+  if (mis(d->ordinal, 8) || mis(d->counters, 8) || mis(d->env, 4) || mis(d->age, 4) || mis(d->scratch, 16))
+    return bad("ordinal and counters must be 8-byte, env and age 4-byte, scratch 16-byte aligned");
+  if (d->scratch_bytes < tc_collect_scratch_size(n_rows, d->num_envs)) return bad("scratch is too small (tc_collect_scratch_bytes)");
+  CollectArgs a;
+  a.d = *d;
+  a.rows = n_rows;
+  a.waves = (int)tc_collect_waves(d->num_envs);
+  a.vec16 = d->frame_bytes % 16 == 0 && !mis(obs_rows, 16) && !mis(d->obs, 16) && !mis(d->last, 16) && !(d->next_obs && mis(d->next_obs, 16));
+  a.obs_rows = obs_rows;
+  a.terminated = terminated;
+  a.truncated = truncated;
+  const size_t cells = (size_t)n_rows * a.waves;
+  a.head = (long long*)d->scratch;
+  a.mask = (unsigned long long*)((char*)d->scratch + 16);
+  a.base = (int*)((char*)d->scratch + 16 + cells * 8);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 block(TC_COLLECT_NT);
+  const long long pairs = (long long)n_rows * d->num_envs;
+  hipLaunchKernelGGL(tc_collect_scan, dim3((unsigned)((d->num_envs + TC_COLLECT_NT - 1) / TC_COLLECT_NT)), block, 0, st, a);
+  hipLaunchKernelGGL(tc_collect_rank, dim3(1), block, 0, st, a);
+  if (d->mode == TC_COLLECT_RANDOM)
+    hipLaunchKernelGGL(tc_collect_claim, dim3((unsigned)((pairs + TC_COLLECT_NT - 1) / TC_COLLECT_NT)), block, 0, st, a);
+  hipLaunchKernelGGL(tc_collect_copy, dim3((unsigned)((pairs + TC_COLLECT_NT / 64 - 1) / (TC_COLLECT_NT / 64))), block, 0, st, a);  // one wavefront per (row, env)
   HIP_TRY(hipGetLastError());
   return TC_OK;
 }

@@ -30,6 +30,7 @@ CAR_STREAM = 0x636172  # "car": the sub-stream of the seed the draws come from (
 CAM_STREAM = 0x63616D  # "cam": likewise for the camera index of an episode
 MAN_STREAM = 0x6D616E  # "man": likewise for the maneuver of an episode
 OU_STREAM = 0x6F75      # "ou": likewise for the normal numbers of the steering noise
+REP_STREAM = 0x726570   # "rep": likewise for the slot a sample replaces in a full sample buffer (overflow="random")
 CAMERA_COLUMNS = ("pitch", "roll", "yaw", "fov", "x", "y", "z")  # columns of a camera bank's parameter table
 _GOLDEN, _M1, _M2 = np.uint64(0x9E3779B97F4A7C15), np.uint64(0xBF58476D1CE4E5B9), np.uint64(0x94D049BB133111EB)
 
@@ -244,3 +245,17 @@ def ou_step(n, eps, theta: float, mu: float, sigma: float):
     """``noise += THETA * (MEAN - noise) + SIGMA * randn`` in the expression's order (``tc_ou_step``): float64, no fusing"""
     n, eps = np.float64(n), np.float64(eps)
     return n + (np.float64(theta) * (np.float64(mu) - n) + np.float64(sigma) * eps)
+
+
+# ---------------------------------------------------------------------------------------------- sample buffer
+def draw_replace_slot(seed: int, ordinal, capacity: int):
+    """The slot of a full sample buffer of `capacity` slots that the candidate with ordinal `ordinal` replaces
+    (``SampleBuffer(overflow="random")``): tc_rng.h's tc_replace_slot -- Replaybuffer.add's np.random.randint(0, size) of the
+    reference's examples/rl_utils.py:20 as a counter-based draw.  ordinal may be an array; returns int64 of its shape."""
+    capacity = int(capacity)
+    if not 1 <= capacity < 2 ** 32:
+        raise ValueError(f"capacity must be in [1, 2^32), got {capacity}")
+    o = np.asarray(ordinal, dtype=np.int64).astype(np.uint64)
+    s2 = splitmix64_at(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), np.uint64(REP_STREAM))
+    z = splitmix64_at(s2, o)
+    return (((z >> np.uint64(32)) * np.uint64(capacity)) >> np.uint64(32)).astype(np.int64)

@@ -898,6 +898,32 @@ class TinyCarloVecEnv(gym.Env):
         from .packing import unpack_obs
         return unpack_obs(packed, dtype=dtype, index=index, out=out)
 
+    def make_sample_buffer(self, capacity: int, columns=("maneuver", "steer"), **kw):
+        """A `tinycarlo_amd.SampleBuffer` for this env's K-step calls: num_envs, the frame shape, its packing and the device
+        filled in.  columns: names of `[K, N]` rollout keys the env can produce now (a sequence: their rollout dtypes; a
+        mapping name -> dtype must agree with them).  Other arguments (next_obs, stride, overflow, seed, max_rows) pass
+        through.  `buf.begin(obs)` after `reset()`, `buf.collect(rollout)` after each call."""
+        from .collect import SampleBuffer
+        shapes = self._rollout_shapes(1)
+        needs = ((self.EPISODE_ROLLOUT_KEYS, self._episodes, "track_episodes() / set_time_limit()"),
+                 (self.CTRL_ROLLOUT_KEYS, self._ctrl, "set_controller()"), (self.CAMERA_ROLLOUT_KEYS, self._cam_bank, "randomize_cameras()"),
+                 (self.DRIVE_ROLLOUT_KEYS, self._drive, "randomize_drive()"))
+        cols = {}
+        for name in columns:
+            if name not in shapes or shapes[name][0] != (1, self.num_envs) or name in ("terminated", "truncated"):
+                raise ValueError(f"column {name!r} is not a [K, N] rollout key of this env")
+            for keys, have, what in needs:
+                if name in keys and have is None:
+                    raise ValueError(f"column {name!r} needs {what} first")
+            if isinstance(columns, dict) and columns[name] != shapes[name][1]:
+                raise ValueError(f"column {name!r} is {shapes[name][1]} in this env's rollouts, not {columns[name]}")
+            cols[name] = shapes[name][1]
+        for k in ("num_envs", "obs_shape", "device", "packed"):
+            if k in kw:
+                raise ValueError(f"{k} is the env's")
+        return SampleBuffer(capacity, self.num_envs, self._obs_shape, columns=cols, device=self.device,
+                            packed=self.obs_packing == "bits", **kw)
+
     def _to_dev(self, key: str, a, dtype: torch.dtype, shape: Tuple[int, ...]) -> torch.Tensor:
         if isinstance(a, torch.Tensor):
             t = a
