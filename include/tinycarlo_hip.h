@@ -522,7 +522,9 @@ int tc_step(tc_env* env, const void* car_control, int32_t control_dtype, const i
  * lists through global memory only / beyond the first n segments, TC_FRAME_ORDER=0 frame workgroups in env order (default:
  * the envs whose last frame had the longest draw list first, so that a dispatch ends with its cheapest frames),
  * TC_STEP_ORDER=n (tc_step: the envs are re-dealt to the workgroups every n-th step so that heavy and light frames share
- * a SIMD, default 8; 0 = workgroup w works on env w). */
+ * a SIMD, default 8; 0 = workgroup w works on env w).
+ * The env's laneline_distances / nearest_edge buffers hold the call's last step; per-step values come from the rollout's
+ * rows (TC_INFO_EVERY_STEP=1: every step computes them, also where neither rows nor a lane-line term read them). */
 typedef struct {
   uint8_t* obs;          /* [K][N][tc_env_obs_bytes] */
   double* reward;        /* [K][N] */

@@ -98,6 +98,10 @@ __device__ __forceinline__ void car_respawn(const CarRows& cr, int env, bool wri
 // Set by the library in StepArgs::flags of every launch while a bank is installed: the kernels branch on this bit of a word
 // they hold anyway instead of fetching a pointer of their argument block per step to test it (never taken from the caller).
 #define TC_FI_CAM_BANK 0x80000000u
+// Likewise set by the library, from the call's plan (CallPlan::info_every, tc_plan.h): every step of the launch computes
+// the lane-line distances (phase B of the simulate stages).  Clear, only the launch's last step does: nothing reads another
+// step's -- no rollout rows for them, no term that looks at distances -- and the env's buffers take the last step's.
+#define TC_FI_INFO_EVERY 0x08000000u
 struct CamDrawTab {  // library owned, updated in place by tc_env_set_camera_bank (a captured graph sees new settings)
   unsigned long long seed;
   unsigned int count, env_offset;

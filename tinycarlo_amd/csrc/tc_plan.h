@@ -5,6 +5,8 @@
 #pragma once
 #include <vector>
 
+#include "../../include/tinycarlo_hip.h" /* TC_T_* */
+
 static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 // Camera layer groups.  Up to 512 nodes / edges the whole map is one group held in the K = 5 / 8 register cache.
@@ -199,6 +201,10 @@ struct CallInputs {
   int nsteps;
   bool obs;            // there is a tensor to draw into (the bound one or the rollout's)
   bool all;            // every step's frame is wanted (a rollout with observations), else only the last one survives
+  // who reads the lane-line distances ("phase B" of the simulate kernels) of a step that is not a launch's last:
+  bool info_rows = false;   // the call's rollout has laneline_distances or nearest_edge rows
+  bool info_terms = false;  // an installed term does (term_reads_distances; kept on the handle by tc_env_set_terms)
+  int info_every = 0;       // the switch TC_INFO_EVERY_STEP
 };
 struct CallPlan {
   bool do_raster;  // frames are drawn at all
@@ -212,7 +218,13 @@ struct CallPlan {
   bool piped;      // split: the frames of a chunk are produced on an internal stream, beside the next simulate launch
   bool streamed;   // piped: the whole call (or st_rows steps of it) is one simulate launch and one gated frame launch
   int steps;       // steps per simulate / frame dispatch
+  bool info_every; // every step of every simulate launch of the call computes the lane-line distances; else only a
+                   // launch's last step does (the env's laneline_distances / nearest_edge buffers hold that step's)
 };
+// The reward / termination terms that read a step's lane-line distances (d_apply_terms): the three lane-line kinds.
+static inline bool term_reads_distances(int kind) {
+  return kind == TC_T_LANELINE_SPARSE_REWARD || kind == TC_T_LANELINE_LINEAR_REWARD || kind == TC_T_LANELINE_CROSSING_TERMINATION;
+}
 static inline CallPlan plan_call(const CallInputs& in) {
   CallPlan p;
   // (the register-hungry K = 13 simulate stage spills when fused, so it stays two launches)
@@ -227,6 +239,10 @@ static inline CallPlan plan_call(const CallInputs& in) {
   p.grouped = p.frames && in.env_grouped;
   p.piped = p.grouped && in.pipe && in.all;
   p.streamed = p.piped && in.stream && in.streamed_rows >= 2 && in.st_words;
+  // Phase B carries nothing from step to step, and its results leave a launch three ways only: the rollout's rows, the
+  // terms of the step, and -- of the launch's last step -- the env's buffers.  One bit for the whole call: every launch it is
+  // split into (chunks, 128-step segments) is given the same.
+  p.info_every = in.info_rows || in.info_terms || in.info_every != 0;
   p.steps = in.nsteps;
   if (p.streamed) {
     if (p.steps > in.streamed_rows) p.steps = in.streamed_rows;

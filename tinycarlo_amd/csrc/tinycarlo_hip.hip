@@ -609,12 +609,16 @@ struct FramePose {
 // EP: episode length / return / time limit (tc_env_set_episodes); the running pair lives in LiveLds (ep_len, ep_ret).
 // CTRL: the action comes from the built-in controller (tc_env_set_controller), computed from the cte / he the record holds
 // from the step before; car_control is not read.
+// need_b (wave-uniform): this step computes the lane-line distances -- the launch's last step, and every step when the
+// call's plan says someone reads them (TC_FI_INFO_EVERY).  need_win: the map window is fetched into `mc` behind phase A: for
+// phase B, and for the camera stage where the same wavefront runs one behind this step.
 template <int K, unsigned FEAT = 0>
 __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, int env, int mode,
                                 const void* car_control, int cdtype,
                                 const int* maneuver, const int* spawn_nodes, const unsigned char* mask,
                                 unsigned int flags, const RollStep& roll, const int tid, MapCache<K>& mc, FramePose& fp,
-                                int& cam_row, const CarRows& cr = CarRows(), const EpArgs& ep = EpArgs(),
+                                int& cam_row, const bool need_b, const bool need_win, const CarRows& cr = CarRows(),
+                                const EpArgs& ep = EpArgs(),
                                 const CtrlArgs& ct = CtrlArgs(), const CamBank& cb = CamBank(),
                                 const DriveArgs& dr = DriveArgs()) {
   constexpr bool PER = (FEAT & TC_FEAT_CAR) != 0, EP = (FEAT & TC_FEAT_EP) != 0, CTRL = (FEAT & TC_FEAT_CTRL) != 0;
@@ -826,14 +830,18 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
     // The map window is fetched here, behind phase A, and not at the top of the step: across the scalar phase its 30
     // registers per lane were what pushed the fused kernel over 128 VGPRs (the allocator answered by spilling the node
     // half to scratch and reloading it here).  The lines are L1 / L2 resident after the first step of a launch.
-    if (single) {  // (the camera stage behind this one finds the window loaded)
+    if (single && need_win) {  // (the camera stage behind this one finds the window loaded)
       cache_nodes(mc, m, 0, m.total_nodes, tid);
       cache_edges(mc, m, 0, m.total_edges, 0, tid);
     }
     // ---- phase B: lane-line distances (car.py:55-64)
     const int C = m.C;
     double dist_l = 0;  // lane l < C: distance to lane-line layer l (0 while the info is empty, car.py:47-51)
-    if (have_info && !DBG_ON(flags, DBG_SKIP_DIST)) {
+    // Without need_b neither branch runs: nobody reads this step's distances (see envg_kernel_body) -- no rollout rows for
+    // them, no term that looks at dist_l -- and lv->dist / lv->ne keep an earlier step's values until the launch's last
+    // step, which always comes through here, rewrites them for live_out.  (The condition sits in the two branches, not in
+    // a third one in front of them: that form moved the fused kernels' VGPR counts, which the tests hold to the recorded ones.)
+    if (need_b && have_info && !DBG_ON(flags, DBG_SKIP_DIST)) {
       int my_e = -1;
       const int cell = uni_i(d_grid_cell(m, s.x, s.y));  // (every lane holds the same state)
       if (cell >= 0) {
@@ -946,7 +954,7 @@ __device__ __forceinline__ void sim_body(const KArgs& a, unsigned char* smem, in
       }
       TSTAMP(16);
       lds_sync();  // dn aliases the camera's node buffer
-    } else if (tid < C) {
+    } else if (need_b && tid < C) {
       lv->dist[tid] = 0;
       lv->ne[tid] = -1;
       if (roll.dist) roll.dist[(roll.row0 + env) * C + tid] = 0;
@@ -2221,9 +2229,10 @@ __device__ __forceinline__ void env_kernel_body() {
                           // registers per lane held across the whole step body, raster stage included)
     FramePose fp;
     int cam_row;
+    const bool need_b = k == nsteps - 1 || (sa.flags & TC_FI_INFO_EVERY) != 0;
     sim_body<K, FEAT>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
-                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, cam_row, sa.cr, sa.ep,
-                         sa.ct, sa.cb, sa.dr);
+                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, cam_row, need_b,
+                         need_b || (CAM && sa.ma.cam_here), sa.cr, sa.ep, sa.ct, sa.cb, sa.dr);
     if (sa.ma.pose_rows) {
       double pose[12];
       cam_pose12(sa.a, cam_row, fp, pose);
@@ -2559,112 +2568,120 @@ __device__ __forceinline__ void envg_kernel_body() {
     }
     // ---- phase B: nearest lane-line edge and distance per layer (car.py:55-64, layer.py:33-44,126-164)
     const int C = m.C;
+    // On demand: the phase carries nothing to the next step, and what it computes leaves the launch through the rollout's
+    // rows, the terms below and -- of the last step -- the env's buffers.  The plan (CallPlan::info_every) says whether any
+    // step but the last has a reader; without one those steps skip the phase, the grid lookup included.  roll.dist / roll.ne
+    // are NULL then (they are what sets the bit), and gl.dist keeps the values of an earlier step or launch: no term of
+    // the stack reads it (that would have set the bit too).  need_b is wave-uniform: a scalar branch round the phase.
     const bool last = k == nsteps - 1;
-    const int cell = have_info ? d_grid_cell(m, s.x, s.y) : -1;
+    const bool need_b = last || (flags & TC_FI_INFO_EVERY) != 0;
     TSTAMP(0);
     static_assert(TC_EL == 8 && TC_AG <= TC_EL, "group8_argmin_multi, one lane per layer of a block");
-    if (have_info) {
-      // The cell's candidate edges (DevMap: every edge that can be the first minimum for a point of the cell, layer by
-      // layer, ascending -- a handful per layer), a block of TC_AG layers at a time.  Memory first, arithmetic after: the
-      // block's list offsets are fetched together, then each lane's first candidate of every layer together (two load
-      // latencies for the whole block, whatever the vector-memory pipeline's queue looks like beside the frame kernel),
-      // then the layers are scanned one after the other from the LDS edge records; lane g of the group finally evaluates
-      // layer g's tail, so the bounds test and the distance run once per block, not once per layer.
-      //   A car outside the grid (cell < 0) runs the SAME code with the identity list -- every edge of the layer -- so a
-      // wavefront with one such env executes longer loops, not a second copy of the phase.
-      const bool far = cell < 0;
-      for (int lb = 0; lb < C; lb += TC_AG) {
-        double bd[TC_AG];
-        int best[TC_AG], lo[TC_AG], off[TC_AG + 1], e0[TC_AG];
+    if (need_b) {
+      const int cell = have_info ? d_grid_cell(m, s.x, s.y) : -1;
+      if (have_info) {
+        // The cell's candidate edges (DevMap: every edge that can be the first minimum for a point of the cell, layer by
+        // layer, ascending -- a handful per layer), a block of TC_AG layers at a time.  Memory first, arithmetic after: the
+        // block's list offsets are fetched together, then each lane's first candidate of every layer together (two load
+        // latencies for the whole block, whatever the vector-memory pipeline's queue looks like beside the frame kernel),
+        // then the layers are scanned one after the other from the LDS edge records; lane g of the group finally evaluates
+        // layer g's tail, so the bounds test and the distance run once per block, not once per layer.
+        //   A car outside the grid (cell < 0) runs the SAME code with the identity list -- every edge of the layer -- so a
+        // wavefront with one such env executes longer loops, not a second copy of the phase.
+        const bool far = cell < 0;
+        for (int lb = 0; lb < C; lb += TC_AG) {
+          double bd[TC_AG];
+          int best[TC_AG], lo[TC_AG], off[TC_AG + 1], e0[TC_AG];
 #pragma unroll
-        for (int g = 0; g <= TC_AG; g++) {
-          const int lg = lb + g < C ? lb + g : C;
-          off[g] = far ? m.edge_off[lg] : m.cand_off[cell * C + lg];
-        }
-#pragma unroll
-        for (int g = 0; g < TC_AG; g++) {
-          lo[g] = lb + g < C ? m.edge_off[lb + g] : 0;
-          e0[g] = off[g] + sub < off[g + 1] ? (far ? off[g] + sub : m.cand_idx[off[g] + sub]) : -1;
-        }
-#pragma unroll
-        for (int g = 0; g < TC_AG; g++) {
-          double bdg = 0;
-          int bg = -1, e = e0[g];
-          for (int i = off[g] + sub; i < off[g + 1]; i += TC_EL) {
-            double4 q;
-            if (map_lds)
-              q = make_double4(l_exy[4 * e], l_exy[4 * e + 1], l_exy[4 * e + 2], l_exy[4 * e + 3]);
-            else
-              q = m.edge_xy[e];
-            const double d = tc_fabs(d_dist(s.x, s.y, q.x, q.y) + d_dist(s.x, s.y, q.z, q.w));
-            if (bg < 0 || d < bdg) {
-              bg = e - lo[g];
-              bdg = d;
-            }
-            if (i + TC_EL < off[g + 1]) e = far ? i + TC_EL : m.cand_idx[i + TC_EL];
+          for (int g = 0; g <= TC_AG; g++) {
+            const int lg = lb + g < C ? lb + g : C;
+            off[g] = far ? m.edge_off[lg] : m.cand_off[cell * C + lg];
           }
-          bd[g] = bdg;
-          best[g] = bg;
-        }
-        if (lb == 0) TSTAMP(16);
-        group8_argmin_multi(bd, best);
-        if (lb == 0) TSTAMP(1);
-        int ne = -1, eo = 0;
 #pragma unroll
-        for (int g = 0; g < TC_AG; g++) {
-          ne = sub == g ? best[g] : ne;
-          eo = sub == g ? lo[g] : eo;
-        }
-        const int l = lb + sub;
-        if (sub < TC_AG && l < C) {  // lane g: layer lb + g
-          double dist_l = 0;
-          if (ne >= 0) {
-            const int ge = eo + ne;
-            double4 q;
-            double o_fw, o_rv;
-            if (map_lds) {
-              q = make_double4(l_exy[4 * ge], l_exy[4 * ge + 1], l_exy[4 * ge + 2], l_exy[4 * ge + 3]);
-              o_fw = l_ofw[ge];
-              o_rv = l_orv[ge];
-            } else {
-              q = m.edge_xy[ge];
-              o_fw = m.ori_fwd[ge];
-              o_rv = m.ori_rev[ge];
+          for (int g = 0; g < TC_AG; g++) {
+            lo[g] = lb + g < C ? m.edge_off[lb + g] : 0;
+            e0[g] = off[g] + sub < off[g + 1] ? (far ? off[g] + sub : m.cand_idx[off[g] + sub]) : -1;
+          }
+#pragma unroll
+          for (int g = 0; g < TC_AG; g++) {
+            double bdg = 0;
+            int bg = -1, e = e0[g];
+            for (int i = off[g] + sub; i < off[g + 1]; i += TC_EL) {
+              double4 q;
+              if (map_lds)
+                q = make_double4(l_exy[4 * e], l_exy[4 * e + 1], l_exy[4 * e + 2], l_exy[4 * e + 3]);
+              else
+                q = m.edge_xy[e];
+              const double d = tc_fabs(d_dist(s.x, s.y, q.x, q.y) + d_dist(s.x, s.y, q.z, q.w));
+              if (bg < 0 || d < bdg) {
+                bg = e - lo[g];
+                bdg = d;
+              }
+              if (i + TC_EL < off[g + 1]) e = far ? i + TC_EL : m.cand_idx[i + TC_EL];
             }
-            const double2 n0 = make_double2(q.x, q.y), n1 = make_double2(q.z, q.w);
-            bool certain;
-            bool inb = d_within_bounds_filter(n0.x, n0.y, n1.x, n1.y, s.x, s.y, certain);
-            if (!certain) inb = d_within_bounds(n0.x, n0.y, n1.x, n1.y, o_fw, o_rv, s.x, s.y);
-            if (inb) {
-              dist_l = tc_fabs(d_distance_to_edge(n0.x, n0.y, n1.x, n1.y, s.x, s.y));
-            } else {
-              const double da = d_dist(s.x, s.y, n0.x, n0.y);
-              const double db = d_dist(s.front_x, s.front_y, n1.x, n1.y);  // FRONT axle for n1 (car.py:64)
-              dist_l = db < da ? db : da;
+            bd[g] = bdg;
+            best[g] = bg;
+          }
+          if (lb == 0) TSTAMP(16);
+          group8_argmin_multi(bd, best);
+          if (lb == 0) TSTAMP(1);
+          int ne = -1, eo = 0;
+#pragma unroll
+          for (int g = 0; g < TC_AG; g++) {
+            ne = sub == g ? best[g] : ne;
+            eo = sub == g ? lo[g] : eo;
+          }
+          const int l = lb + sub;
+          if (sub < TC_AG && l < C) {  // lane g: layer lb + g
+            double dist_l = 0;
+            if (ne >= 0) {
+              const int ge = eo + ne;
+              double4 q;
+              double o_fw, o_rv;
+              if (map_lds) {
+                q = make_double4(l_exy[4 * ge], l_exy[4 * ge + 1], l_exy[4 * ge + 2], l_exy[4 * ge + 3]);
+                o_fw = l_ofw[ge];
+                o_rv = l_orv[ge];
+              } else {
+                q = m.edge_xy[ge];
+                o_fw = m.ori_fwd[ge];
+                o_rv = m.ori_rev[ge];
+              }
+              const double2 n0 = make_double2(q.x, q.y), n1 = make_double2(q.z, q.w);
+              bool certain;
+              bool inb = d_within_bounds_filter(n0.x, n0.y, n1.x, n1.y, s.x, s.y, certain);
+              if (!certain) inb = d_within_bounds(n0.x, n0.y, n1.x, n1.y, o_fw, o_rv, s.x, s.y);
+              if (inb) {
+                dist_l = tc_fabs(d_distance_to_edge(n0.x, n0.y, n1.x, n1.y, s.x, s.y));
+              } else {
+                const double da = d_dist(s.x, s.y, n0.x, n0.y);
+                const double db = d_dist(s.front_x, s.front_y, n1.x, n1.y);  // FRONT axle for n1 (car.py:64)
+                dist_l = db < da ? db : da;
+              }
+            }
+            gl.dist[l] = dist_l;
+            if (live) {
+              if (roll.dist) roll.dist[(roll.row0 + env) * C + l] = dist_l;
+              if (roll.ne) roll.ne[(roll.row0 + env) * C + l] = ne;
+            }
+            if (last && live) {
+              b.laneline_distances[(size_t)env * C + l] = dist_l;
+              b.nearest_edge[(size_t)env * C + l] = ne;
             }
           }
-          gl.dist[l] = dist_l;
+          if (lb == 0) TSTAMP(2);
+        }
+      } else {
+        for (int l = sub; l < C; l += TC_EL) {  // no info this step (car.py:47-51): zero distances, no nearest edge
+          gl.dist[l] = 0;
           if (live) {
-            if (roll.dist) roll.dist[(roll.row0 + env) * C + l] = dist_l;
-            if (roll.ne) roll.ne[(roll.row0 + env) * C + l] = ne;
+            if (roll.dist) roll.dist[(roll.row0 + env) * C + l] = 0;
+            if (roll.ne) roll.ne[(roll.row0 + env) * C + l] = -1;
           }
           if (last && live) {
-            b.laneline_distances[(size_t)env * C + l] = dist_l;
-            b.nearest_edge[(size_t)env * C + l] = ne;
+            b.laneline_distances[(size_t)env * C + l] = 0;
+            b.nearest_edge[(size_t)env * C + l] = -1;
           }
-        }
-        if (lb == 0) TSTAMP(2);
-      }
-    } else {
-      for (int l = sub; l < C; l += TC_EL) {  // no info this step (car.py:47-51): zero distances, no nearest edge
-        gl.dist[l] = 0;
-        if (live) {
-          if (roll.dist) roll.dist[(roll.row0 + env) * C + l] = 0;
-          if (roll.ne) roll.ne[(roll.row0 + env) * C + l] = -1;
-        }
-        if (last && live) {
-          b.laneline_distances[(size_t)env * C + l] = 0;
-          b.nearest_edge[(size_t)env * C + l] = -1;
         }
       }
     }
@@ -2975,9 +2992,10 @@ __device__ __forceinline__ void step_kernel_body() {
                           // registers per lane held across the whole step body, raster stage included)
     FramePose fp;
     int cam_row;  // (the bank index stays in a register: the same wavefront draws the frame)
+    // (the map window is fetched every step: the camera stage below finds it loaded)
     sim_body<K, FEAT>(sa.a, smem, env, sa.mode, (const char*)sa.car_control + row0 * 2 * esz, sa.cdtype, sa.maneuver + row0,
-                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, cam_row, sa.cr, sa.ep,
-                         sa.ct, sa.cb, sa.dr);
+                         sa.spawn_nodes, sa.mask, sa.flags, roll_at(sa.ma.roll, row0, sa.a.m.C), tid, mc, fp, cam_row,
+                         k == nsteps - 1 || (sa.flags & TC_FI_INFO_EVERY) != 0, true, sa.cr, sa.ep, sa.ct, sa.cb, sa.dr);
     if (wants_frame(sa)) {
       int nseg;
       unsigned int used;
@@ -3314,7 +3332,7 @@ extern "C" int tc_abi_version(void) { return TC_ABI_VERSION; }
 // Every switch the library reads from the environment, parsed once per tc_env_create / tc_map_create by read_tuning()
 // -- the only place that looks at the environment.  INTEGRATION.md calls the shipped ones result-neutral.
 struct Tuning {
-  int fuse, env_grouped, envg_map_lds, first_per_env, stream, groups, seg_lds, frame_order, cand_grid, clip_merge, frame_cull, short_edges;  // on / off
+  int fuse, env_grouped, envg_map_lds, first_per_env, stream, groups, seg_lds, frame_order, cand_grid, clip_merge, frame_cull, short_edges, info_every;  // on / off
   // tc_step_multi with observations, split form (default; 0 selects the fused K-step kernel): ONE
   // simulate launch loops over the K steps and leaves K draw lists per env, ONE raster launch of K x N workgroups
   // draws them.  Why: a frame costs between ~10 k clocks (nothing in view) and ~80 k (60 segments) to rasterise and an
@@ -3364,6 +3382,7 @@ static Tuning read_tuning() {
       {"TC_CLIP_MERGE", "1", "0: the camera stage always runs its four clip passes one by one"},
       {"TC_FRAME_CULL", "1", "0: the camera stage never culls a whole frame from its pose (tc_cull.h)"},
       {"TC_SHORT_EDGES", "0", "1: thickness 2 draws the quad's two short outline edges too (tc_line.h)"},
+      {"TC_INFO_EVERY_STEP", "0", "1: every step computes the lane-line distances, also where nothing reads them (tc_plan.h)"},
 #ifdef TC_ABLATE
       {"TC_PRINT_LDS", "", "set: tc_env_create prints its LDS layout"},
 #endif
@@ -3399,6 +3418,7 @@ static Tuning read_tuning() {
   t.clip_merge = on("TC_CLIP_MERGE");
   t.frame_cull = on("TC_FRAME_CULL");
   t.short_edges = on("TC_SHORT_EDGES");
+  t.info_every = on("TC_INFO_EVERY_STEP");
   t.pipe = positive("TC_CHUNK") > 0;
   t.chunk = t.pipe ? positive("TC_CHUNK") : 16;
   t.frame_streams = atoi(sw("TC_FRAME_STREAMS")) == 1 ? 1 : 2;
@@ -3494,6 +3514,7 @@ struct tc_env {
   DriveTab drive_host{};  // what drive_tab holds
   int drive_rows = 0;    // rows of dr.man_rows / dr.noise_rows
   unsigned drive_flags = 0;  // TC_FI_DRIVE_* of every launch while it is on
+  bool terms_read_dist = false;  // an installed term reads lane-line distances (term_reads_distances; tc_env_set_terms)
   CamBank cb{};          // camera bank (tc_env_set_camera_bank); index NULL = off.  k.cam_E / k.cam_K then point to the bank
   DevPtr<CamDrawTab> cam_tab;  // device copy of the draw settings (updated in place), or NULL
   CamDrawTab cam_host{};       // what cam_tab holds
@@ -4670,6 +4691,8 @@ extern "C" int tc_env_set_terms(tc_env* e, const tc_term* terms, int32_t n_terms
   if (n_terms > 0) HIP_TRY(hipMemcpy(e->terms, terms, sizeof(tc_term) * n_terms, hipMemcpyHostToDevice));
   e->k.n_terms = n_terms;
   e->k.term_counters = counters;
+  e->terms_read_dist = false;  // (once here, not per call: plan_of)
+  for (int t = 0; t < n_terms; t++) e->terms_read_dist = e->terms_read_dist || term_reads_distances(terms[t].kind);
   return TC_OK;
 }
 
@@ -4773,7 +4796,7 @@ static int noise_advance(tc_env* e, int mode, bool rendered, int nsteps, void* s
 // What plan_call (tc_plan.h) reads, filled from the handle and the call: for launch(), which dispatches on the plan, and for
 // tc_env_launch_info, which reports it.  obs: there is a tensor to draw into (the bound one or the rollout's); all: every
 // step's frame is wanted (a rollout with observations), else only the last one survives.
-static CallPlan plan_of(const tc_env* e, uint32_t flags, int nsteps, bool obs, bool all) {
+static CallPlan plan_of(const tc_env* e, uint32_t flags, int nsteps, bool obs, bool all, const tc_rollout* roll = nullptr) {
   const Tuning& t = e->tune;
   CallInputs in;
   in.fuse = t.fuse; in.multi_split = t.multi_split; in.env_grouped = t.env_grouped; in.pipe = t.pipe; in.stream = t.stream; in.chunk = t.chunk;
@@ -4782,6 +4805,9 @@ static CallPlan plan_of(const tc_env* e, uint32_t flags, int nsteps, bool obs, b
   in.ring_rows = e->ring.rows; in.streamed_rows = e->streamed.rows; in.st_words = e->st_words != nullptr;
   in.flags = flags; in.no_frame_flags = TC_F_NO_OBSERVATION | DBG_SKIP_CAMERA;
   in.nsteps = nsteps; in.obs = obs; in.all = all;
+  in.info_rows = roll && (roll->laneline_distances || roll->nearest_edge);
+  in.info_terms = e->terms_read_dist;
+  in.info_every = t.info_every;
   return plan_call(in);
 }
 
@@ -4922,7 +4948,8 @@ static StepArgs step_args_at(const tc_env* e, const Call& c, int c0) {
   sa.dr = e->dr;  // (the rows likewise)
   sa.dr.man_rows = ep_rows && e->dr.man_rows ? e->dr.man_rows + r0 : nullptr;
   sa.dr.noise_rows = ep_rows && e->dr.noise_rows ? e->dr.noise_rows + r0 : nullptr;
-  sa.flags = (c.flags & ~(TC_FI_CAM_BANK | TC_FI_DRIVE)) | (e->cb.index ? TC_FI_CAM_BANK : 0u) | (e->dr.tab ? e->drive_flags : 0u);
+  sa.flags = (c.flags & ~(TC_FI_CAM_BANK | TC_FI_DRIVE | TC_FI_INFO_EVERY)) | (e->cb.index ? TC_FI_CAM_BANK : 0u) |
+             (e->dr.tab ? e->drive_flags : 0u) | (c.plan.info_every ? TC_FI_INFO_EVERY : 0u);
   sa.car_control = c.cc ? (const char*)c.cc + r0 * 2 * (c.cdtype == TC_F32 ? 4 : 8) : nullptr;  // (NULL: a controller acts)
   sa.maneuver = c.man ? c.man + r0 : nullptr;  // (NULL: the maneuvers are the device's, tc_env_set_drive_randomization)
   sa.spawn_nodes = c.spawn;
@@ -5247,7 +5274,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
   c.main = (hipStream_t)stream; c.nsteps = nsteps; c.roll = roll; c.ep_rows = ep_rows; c.feat = feat;
   c.all = roll && roll->obs;
   c.thick = e->k.cam.thickness > 1; c.fmt = e->k.cam.format;
-  c.plan = plan_of(e, flags, nsteps, e->k.b.obs || c.all, c.all);
+  c.plan = plan_of(e, flags, nsteps, e->k.b.obs || c.all, c.all, roll);
   c.prof = e->prof > 0 && mode == MODE_STEP && (e->prof_calls++ % e->prof) == 0;
   c.slot = e->prof_n % TC_PROF_RING;
   if (c.plan.split && e->ring.rows < 1) {
