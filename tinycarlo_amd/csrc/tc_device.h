@@ -695,7 +695,8 @@ __device__ inline void r_cap(const Ras& r, int cx, int cy, int rad, const unsign
   }
 }
 
-// clipLine, d_sdiv and Line2's set-up (r_clip_line, d_sdiv, LineP, r_line2_setup): HIP-free, shared with the host tests
+// clipLine, d_sdiv, ThickLine's quad and Line2's set-up (r_clip_line, d_sdiv, r_quad_dp, LineP, r_outline_edge): HIP-free,
+// shared with the host tests.  -DTC_LINE_LITERAL builds the literal int64 forms back in (a build switch like TC_FILL_LITERAL).
 #include "tc_line.h"
 
 // Line(): LineIterator(..., 8, leftToRight=true) -- thickness <= 1
@@ -751,16 +752,9 @@ __device__ inline void r_line2_pixels(const Ras& r, int a, int b, int step, int 
   }
 }
 
-// The four polygon vertices travel as BY-VALUE scalars.  Any aggregate (array or struct behind a
-// reference) lets LLVM fold "select of loads" into "load of selected pointer", which pins the
-// aggregate in scratch memory -- and scratch write-back shows up as HBM traffic.
-__device__ inline long long sel4(long long a0, long long a1, long long a2, long long a3, int i) {
-  long long r = a0;
-  r = i == 1 ? a1 : r;
-  r = i == 2 ? a2 : r;
-  r = i == 3 ? a3 : r;
-  return r;
-}
+// The polygon travels as BY-VALUE scalars (pixel end points and dp, or the four vertices).  Any aggregate (array or struct
+// behind a reference) lets LLVM fold "select of loads" into "load of selected pointer", which pins the aggregate in
+// scratch memory -- and scratch write-back shows up as HBM traffic.
 
 // FillConvexPoly(v[4], shift = 16, LINE_8) = 4 outline edges (Line2, above) + the scanline fill below.
 // FillConvexPoly's two edge walkers as closed-form pieces: tc_fill.h has the event part, as the literal loop nest and in
@@ -779,14 +773,17 @@ __device__ inline int r_fill_events(int W, int H, long long qx0, long long qx1, 
 #endif
 }
 
-// slope of one recorded piece (drawing.cpp: edge[i].dx = ((xe - xs)*2 + (ty - y)) / (2*(ty - y)), edge[i].x = xs)
-__device__ inline void r_fill_slope(long long qx0, long long qx1, long long qx2, long long qx3, long long qy0,
-                                    long long qy1, long long qy2, long long qy3, int y_u, int v, long long& xs,
+// slope of one recorded piece (drawing.cpp: edge[i].dx = ((xe - xs)*2 + (ty - y)) / (2*(ty - y)), edge[i].x = xs) of the
+// quad (pixel end points, dp).  Vertex i is p0 (i < 2) or p1, plus dp (i = 0, 3) or minus: its int32 parts are selected
+// and the one int64 vertex formed from them, instead of all eight vertices and 64-bit selects among them.
+__device__ inline void r_fill_slope(int x0, int y0, int x1, int y1, int dpx, int dpy, int y_u, int v, long long& xs,
                                     long long& dx) {
   const int idx0 = v & 3, idx = (v >> 2) & 3;
-  const int ty = d_wrap32((sel4(qy0, qy1, qy2, qy3, idx) + (TC_XY_ONE >> 1)) >> TC_XY_SHIFT);
-  xs = sel4(qx0, qx1, qx2, qx3, idx0);
-  const long long xe = sel4(qx0, qx1, qx2, qx3, idx);
+  const bool m0 = idx0 == 1 || idx0 == 2, m = idx == 1 || idx == 2;
+  const long long ye = (long long)(idx >= 2 ? y1 : y0) * TC_XY_ONE + (m ? -dpy : dpy);
+  const int ty = d_wrap32((ye + (TC_XY_ONE >> 1)) >> TC_XY_SHIFT);
+  xs = (long long)(idx0 >= 2 ? x1 : x0) * TC_XY_ONE + (m0 ? -dpx : dpx);
+  const long long xe = (long long)(idx >= 2 ? x1 : x0) * TC_XY_ONE + (m ? -dpx : dpx);
   dx = d_sdiv((xe - xs) * 2 + ((long long)ty - y_u), 2 * ((long long)ty - y_u));
 }
 
@@ -855,25 +852,6 @@ __device__ inline void r_circle_fill(const Ras& r, int cx, int cy, int radius) {
     dx += mask;
     minus -= mask & 2;
   }
-}
-
-// ThickLine's quad for thickness > 1: returns false when the segment is degenerate (|r| <= DBL_EPSILON)
-__device__ inline bool r_quad(int x0, int y0, int x1, int y1, int thickness, long long& qx0, long long& qx1,
-                              long long& qx2, long long& qx3, long long& qy0, long long& qy1, long long& qy2,
-                              long long& qy3) {
-  long long p0x = (long long)x0 * TC_XY_ONE, p0y = (long long)y0 * TC_XY_ONE;
-  long long p1x = (long long)x1 * TC_XY_ONE, p1y = (long long)y1 * TC_XY_ONE;
-  const double INV_XY_ONE = 1. / TC_XY_ONE;
-  double dx = (double)(p0x - p1x) * INV_XY_ONE, dy = (double)(p1y - p0y) * INV_XY_ONE;
-  double rr = dx * dx + dy * dy;
-  int odd = thickness & 1;
-  long long th = (long long)thickness << (TC_XY_SHIFT - 1);
-  if (!(tc_fabs(rr) > 2.2204460492503131e-16)) return false;
-  rr = ((double)th + odd * TC_XY_ONE * 0.5) / sqrt(rr);
-  long long dpx = __double2int_rn(dy * rr), dpy = __double2int_rn(dx * rr);
-  qx0 = p0x + dpx; qx1 = p0x - dpx; qx2 = p1x - dpx; qx3 = p1x + dpx;
-  qy0 = p0y + dpy; qy1 = p0y - dpy; qy2 = p1y - dpy; qy3 = p1y + dpy;
-  return true;
 }
 
 #endif  // TC_DEVICE_H

@@ -1571,12 +1571,10 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
               const long long ymin = (ya < yb ? ya : yb) - mg, ymax = (ya < yb ? yb : ya) + mg;
               touch = ymax >= y0 && ymin < y1;
             }
-            if (touch && !DBG_ON(a.flags, DBG_SKIP_QUAD) &&
-                r_quad(sg[1], sg[2], sg[3], sg[4], cam.thickness, qx0, qx1, qx2, qx3, qy0, qy1, qy2, qy3)) {
+            if (touch && !DBG_ON(a.flags, DBG_SKIP_QUAD) && r_quad_dp(sg[1], sg[2], sg[3], sg[4], cam.thickness, dpx, dpy)) {
               TSTAMP(21);
               okq = 1;
-              dpx = (int)(qx0 - (long long)sg[1] * TC_XY_ONE);
-              dpy = (int)(qy0 - (long long)sg[2] * TC_XY_ONE);
+              r_quad_vertices(sg[1], sg[2], sg[3], sg[4], dpx, dpy, qx0, qx1, qx2, qx3, qy0, qy1, qy2, qy3);
               int hi = -1;
               if (!DBG_ON(a.flags, DBG_SKIP_EVENTS))
               np = r_fill_events(W, H, qx0, qx1, qx2, qx3, qy0, qy1, qy2, qy3, fpy + 4 * tid, fpv + 4 * tid, wm, lo,
@@ -1610,17 +1608,9 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
           if (t < (nb << sh) && ((fm[j] >> 16) & 1)) {
             const int s0 = t & ((1 << sh) - 1), e = s0 << (2 - sh);  // item of the segment; its edge: 0 2, or 0 1 2 3
             const SegV sg = seg_get(base + j);
-            const long long p0x = (long long)sg[1] * TC_XY_ONE, p0y = (long long)sg[2] * TC_XY_ONE;
-            const long long p1x = (long long)sg[3] * TC_XY_ONE, p1y = (long long)sg[4] * TC_XY_ONE;
-            const long long dpx = fd[2 * j], dpy = fd[2 * j + 1];
-            const long long qx0 = p0x + dpx, qx1 = p0x - dpx, qx2 = p1x - dpx, qx3 = p1x + dpx;
-            const long long qy0 = p0y + dpy, qy1 = p0y - dpy, qy2 = p1y - dpy, qy3 = p1y + dpy;
-            // FillConvexPoly walks p0 = v[3]; Line2(p0, v[i]); p0 = v[i]: outline edge e runs v[e-1] -> v[e] with
-            // v0 = p0+dp, v1 = p0-dp, v2 = p1-dp, v3 = p1+dp
-            const bool a_is_p1 = e == 0 || e == 3, b_is_p1 = e >= 2;
-            const bool a_minus = e == 2 || e == 3, b_minus = e == 1 || e == 2;
-            long long ax = (a_is_p1 ? p1x : p0x) + (a_minus ? -dpx : dpx), ay = (a_is_p1 ? p1y : p0y) + (a_minus ? -dpy : dpy);
-            long long bx = (b_is_p1 ? p1x : p0x) + (b_minus ? -dpx : dpx), by = (b_is_p1 ? p1y : p0y) + (b_minus ? -dpy : dpy);
+            // the quad travels as (pixel end points, dp): the fill pieces and the outline edge each form the vertices
+            // they need from the int32 parts (r_fill_slope, r_outline_edge)
+            const int dpx = fd[2 * j], dpy = fd[2 * j + 1];
             const int np = fm[j] & 0xff;
             // fill pieces of this lane (x at the start row and slope): piece s0, and s0 + 2 in the two-edge form -- one
             // instance of the code, a loop the wavefront leaves together
@@ -1631,14 +1621,14 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
               if (want) {
                 const int s = 4 * j + s0 + h;
                 long long xs, dxs;
-                r_fill_slope(qx0, qx1, qx2, qx3, qy0, qy1, qy2, qy3, fpy[s], fpv[s], xs, dxs);
+                r_fill_slope(sg[1], sg[2], sg[3], sg[4], dpx, dpy, fpy[s], fpv[s], xs, dxs);
                 fpx[s] = xs;
                 fpd[s] = dxs;
               }
             }
             LineP L;
             L.ecount = -1;
-            if (!DBG_ON(a.flags, DBG_SKIP_LINESETUP)) L = r_line2_setup(W, H, ax, ay, bx, by);
+            if (!DBG_ON(a.flags, DBG_SKIP_LINESETUP)) L = r_outline_edge(W, H, sg[1], sg[2], sg[3], sg[4], dpx, dpy, e);
             if (L.ecount >= 0) {
               r.bits = bits + sg[0] * plane;
               r_put(r, L.ex, L.ey);
