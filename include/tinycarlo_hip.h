@@ -60,6 +60,8 @@ extern "C" {
 #define TC_HAS_DRIVE_RANDOMIZATION 1
 /* Likewise additive within ABI 6: tc_collect, tc_collect_scratch_bytes, tc_collect_desc, TC_COLLECT_*. */
 #define TC_HAS_COLLECT 1
+/* Likewise additive within ABI 6: tc_collect_link, tc_history_resolve, tc_gather_frames, TC_PAD_*. */
+#define TC_HAS_HISTORY 1
 #define TC_MAX_LAYERS 16
 
 /* error codes */
@@ -653,6 +655,52 @@ typedef struct {
 int64_t tc_collect_scratch_bytes(int32_t n_rows, int32_t num_envs);
 int tc_collect(const tc_collect_desc* desc, int32_t n_rows, const uint8_t* obs_rows, const uint8_t* terminated,
                const uint8_t* truncated, void* stream);
+
+/* Frame histories over the sample buffer (TC_HAS_HISTORY): a sample of ReplaybufferTemporal (examples/rl_utils.py:32-57) is
+ * what the env showed over the last T steps of the episode, newest first (examples/train_td3.py:164,175-176).  The buffer
+ * keeps one frame per slot plus one link: prev[slot] = ordinal of the sample that precedes the slot's in its episode (-1:
+ * none), and per env chain[n] = ordinal of the env's most recent candidate of the running episode (-1: none; the caller
+ * sets chain to -1 where it sets age to 0).  Rules: tc_collect.h (tc_collect_chain_step, tc_history_walk); definition:
+ * collect_reference / history_reference of tinycarlo_amd/collect.py.
+ *
+ * tc_collect_link: call it BEFORE tc_collect, on the same stream, with the same descriptor, n_rows and done rows.  It reads
+ * pending, age and counters[TC_COLLECT_NEXT] without changing them, repeats the scan and the rank into desc->scratch (which
+ * tc_collect overwrites afterwards) and then, one thread per env, walks the rows: a re-spawn row sets chain[n] = -1, a
+ * candidate with ordinal o gets link_rows[k][n] = chain[n] and sets chain[n] = o, written or not; every other entry of
+ * link_rows becomes -1.  Hand link_rows to tc_collect as an 8-byte column whose dst is prev: prev[slot] is then written
+ * under exactly the condition under which the slot's frame, env and ordinal are, so a buffer with links has at most
+ * TC_COLLECT_MAX_COLUMNS - 1 columns of its own.  desc->columns is not looked at here.  chain: device int64 [num_envs];
+ * link_rows: device int64 [n_rows][num_envs].  Three launches; neither allocates nor synchronises; can be captured.
+ * TC_E_INVALID before any HIP call: what tc_collect refuses about the fields used here, a NULL or misaligned chain / link_rows. */
+int tc_collect_link(const tc_collect_desc* desc, int32_t n_rows, const uint8_t* terminated, const uint8_t* truncated,
+                    int64_t* chain, int64_t* link_rows, void* stream);
+
+/* The histories of n_index slots: slots[b][0] = index[b], slots[b][t] = the slot of the sample t steps before it, as far
+ * as the links lead: the walk stops where the episode started (prev < 0) or where the predecessor was dropped or
+ * overwritten (the slot of ordinal prev is -1 or holds another ordinal).  valid[b] = entries found; the rest is -1
+ * (TC_PAD_ZERO) or the last slot found (TC_PAD_EDGE).  An index outside [0, capacity) or an empty slot gives valid = 0 and
+ * -1 throughout.  next_slots (or NULL): [b][0] = slots[b][0], [b][t] = slots[b][t-1] -- with tc_gather_frames' second
+ * source the next-history x1 = queue[:-1] against x = queue[1:].  mode, seed, capacity: the buffer's.  index, slots,
+ * next_slots: device int64 [n_index], [n_index][T]; valid: device int32 [n_index].  One launch, one thread per sample.
+ * TC_E_INVALID before any HIP call: a NULL or misaligned pointer, capacity < 1, T < 1, n_index < 0, an unknown mode or pad,
+ * capacity >= 2^32 with TC_COLLECT_RANDOM.  n_index = 0 is TC_OK without a launch. */
+#define TC_PAD_ZERO 0
+#define TC_PAD_EDGE 1
+int tc_history_resolve(const int64_t* prev, const int64_t* ordinal, int64_t capacity, int32_t mode, uint64_t seed,
+                       const int64_t* index, int64_t n_index, int32_t T, int32_t pad, int64_t* slots, int64_t* next_slots,
+                       int32_t* valid, void* stream);
+
+/* Byte frames gathered by index into the dtype the consumer wants: dst [n_out][frame_bytes] elements of dst_dtype, output
+ * frame j = frame index[j] of src -- or of src2, where src2 is given and j % group == 0.  TC_U8 copies; TC_F16, TC_BF16 and
+ * TC_F32 give float(v) * (1.0f / 255.0f) rounded once to the dtype: what torch's device kernel computes for
+ * frames.to(dtype) / 255 (a division by a scalar is a product with the float reciprocal there), bit for bit.
+ * An index outside [0, n_src_frames) yields zeros and reads nothing.  Each lane owns one 16-byte store and takes its 16 /
+ * 8 / 4 source bytes with one load when frame_bytes and src (src2) are multiples of that; otherwise lanes move 4 source
+ * bytes each (frame_bytes % 4 == 0, src 4-byte aligned).  dst is 16-byte aligned.  One launch; neither allocates nor
+ * synchronises; can be captured.  TC_E_INVALID before any HIP call: NULL src, index or dst, non-positive n_src_frames or
+ * frame_bytes, frame_bytes % 4 != 0, n_out < 0, group < 1 with src2, an unknown dtype, a misaligned pointer. */
+int tc_gather_frames(const uint8_t* src, const uint8_t* src2, int64_t n_src_frames, int64_t frame_bytes, const int64_t* index,
+                     int64_t n_out, int64_t group, void* dst, int32_t dst_dtype, void* stream);
 
 #ifdef __cplusplus
 }

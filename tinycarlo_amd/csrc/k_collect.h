@@ -6,6 +6,9 @@
 //   tc_collect_rank   one workgroup: exclusive prefix sum over the [rows][wavefronts] counts in row-major order = the rank
 //                     of each wavefront's first candidate; then the counter block moves on (tc_collect_advance)
 //   tc_collect_claim  random mode only: atomicMax(ordinal[slot(o)], o) for every candidate
+//   tc_collect_link_* frame histories only, a pass of three launches IN FRONT of the call (tc_collect_link_scan and _rank: the
+//                     scan and the rank again without moving the carry or the counters; then one thread per env links
+//                     each candidate to its env's previous one); its link_rows travel through tc_collect_copy as a column
 //   tc_collect_copy   one wavefront per (row, env): a candidate that is written (tc_collect_writes) moves its frame(s) with
 //                     up to four 16-byte loads per lane in flight before the stores, its columns, env and ordinal.  The
 //                     wavefront of (row 0, env n) reads last[n] for its sample and then stores obs[rows - 1][n] over it --
@@ -36,7 +39,9 @@ struct CollectArgs {
   int* base;                  // scratch: [rows][waves] counts, then exclusive ranks
 };
 
-TC_PLAIN_KERNEL __global__ __launch_bounds__(TC_COLLECT_NT) void tc_collect_scan(CollectArgs a) {
+// (COMMIT: the carry moves on; without it the pass only looks: the link pass in front of tc_collect)
+template <bool COMMIT>
+__device__ __forceinline__ void collect_scan(const CollectArgs& a) {
   const int n = (int)(blockIdx.x * TC_COLLECT_NT + threadIdx.x);
   const int N = a.d.num_envs;
   const bool live = n < N;  // (lanes beyond N stay in the loop: the ballot below is over whole wavefronts)
@@ -56,13 +61,16 @@ TC_PLAIN_KERNEL __global__ __launch_bounds__(TC_COLLECT_NT) void tc_collect_scan
       a.base[(size_t)k * a.waves + w] = __popcll(m);
     }
   }
-  if (live) {
+  if (COMMIT && live) {
     a.d.pending[n] = pending;
     a.d.age[n] = age;
   }
 }
+TC_PLAIN_KERNEL __global__ __launch_bounds__(TC_COLLECT_NT) void tc_collect_scan(CollectArgs a) { collect_scan<true>(a); }
+TC_PLAIN_KERNEL __global__ __launch_bounds__(TC_COLLECT_NT) void tc_collect_link_scan(CollectArgs a) { collect_scan<false>(a); }
 
-TC_PLAIN_KERNEL __global__ __launch_bounds__(TC_COLLECT_NT) void tc_collect_rank(CollectArgs a) {
+template <bool COMMIT>
+__device__ __forceinline__ void collect_rank(const CollectArgs& a) {
   __shared__ long long part[TC_COLLECT_NT];
   const int t = threadIdx.x;
   const long long cells = (long long)a.rows * a.waves;
@@ -88,11 +96,14 @@ TC_PLAIN_KERNEL __global__ __launch_bounds__(TC_COLLECT_NT) void tc_collect_rank
     const long long c = part[t];
     a.head[0] = a.d.counters[TC_COLLECT_NEXT];
     a.head[1] = c;
+    if (!COMMIT) return;
     long long ctr[4] = {a.d.counters[0], a.d.counters[1], a.d.counters[2], a.d.counters[3]};
     tc_collect_advance(a.d.mode, c, a.d.capacity, (int64_t*)ctr);
     for (int j = 0; j < 4; j++) a.d.counters[j] = ctr[j];
   }
 }
+TC_PLAIN_KERNEL __global__ __launch_bounds__(TC_COLLECT_NT) void tc_collect_rank(CollectArgs a) { collect_rank<true>(a); }
+TC_PLAIN_KERNEL __global__ __launch_bounds__(TC_COLLECT_NT) void tc_collect_link_rank(CollectArgs a) { collect_rank<false>(a); }
 
 // ordinal of candidate (k, n), or -1 where the row is no candidate
 __device__ __forceinline__ long long collect_ordinal(const CollectArgs& a, int k, int n) {
@@ -101,6 +112,28 @@ __device__ __forceinline__ long long collect_ordinal(const CollectArgs& a, int k
   const int bit = n & 63;
   if (!((m >> bit) & 1ull)) return -1;
   return a.head[0] + a.base[cell] + __popcll(m & ((1ull << bit) - 1ull));
+}
+
+// The link pass (tc_collect_link, frame histories): behind tc_collect_link_scan / _rank, which leave the masks, the ranks and
+// head[0] of the call that tc_collect is about to make without moving the carry or the counters.  One thread per env walks
+// the rows (tc_collect_chain_step beside the state machine of rules 1-3; loads and stores coalesced along n): a candidate's
+// link goes to link_rows[k][n], every other entry becomes -1, the carry chain[n] moves on.
+TC_PLAIN_KERNEL __global__ __launch_bounds__(TC_COLLECT_NT) void tc_collect_link_walk(CollectArgs a, long long* chain, long long* link_rows) {
+  const int n = (int)(blockIdx.x * TC_COLLECT_NT + threadIdx.x);
+  const int N = a.d.num_envs;
+  if (n >= N) return;
+  unsigned char pending = a.d.pending[n];
+  int age = a.d.age[n];
+  int64_t c = chain[n];
+  for (int k = 0; k < a.rows; k++) {
+    const size_t at = (size_t)k * N + n;
+    const int done = (a.terminated ? a.terminated[at] : 0) | (a.truncated ? a.truncated[at] : 0);
+    const int respawn = pending != 0;
+    const int cand = tc_collect_env_step(&pending, &age, a.d.stride, done);
+    const long long o = cand ? collect_ordinal(a, k, n) : -1;
+    link_rows[at] = tc_collect_chain_step(&c, respawn, cand, o);
+  }
+  chain[n] = c;
 }
 
 TC_PLAIN_KERNEL __global__ __launch_bounds__(TC_COLLECT_NT) void tc_collect_claim(CollectArgs a) {

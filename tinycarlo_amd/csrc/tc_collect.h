@@ -66,4 +66,47 @@ TC_HD int64_t tc_collect_scratch_size(int32_t rows, int32_t n_envs) {
   const int64_t cells = (int64_t)rows * tc_collect_waves(n_envs);
   return 16 + cells * 8 + (cells * 4 + 15) / 16 * 16;
 }
+
+// ---- frame histories (TC_HAS_HISTORY): a link per slot to the sample that precedes it in its episode, so that a sample
+// of ReplaybufferTemporal (examples/rl_utils.py:32-57: what the env showed over the last SEQ_LEN steps, newest first,
+// examples/train_td3.py:164,175-176) is gathered from single-frame slots.  chain[n] = ordinal of env n's most recent
+// candidate of the running episode (-1: none), prev[slot] = ordinal of the sample before the slot's (-1: the episode
+// started there).  Definition: collect_reference / history_reference of tinycarlo_amd/collect.py.
+
+// One row of one env, beside tc_collect_env_step: `respawn` = the env was pending BEFORE the row (rule 1), `cand` = the row
+// is a candidate with ordinal o (rule 2).  Returns the candidate's link (what prev[slot] becomes if o is written); the chain
+// moves on whether or not o is written.  A row skipped by the stride touches nothing.
+TC_HD int64_t tc_collect_chain_step(int64_t* chain, int respawn, int cand, int64_t o) {
+  if (respawn) {
+    *chain = -1;
+    return -1;
+  }
+  if (!cand) return -1;
+  const int64_t link = *chain;
+  *chain = o;
+  return link;
+}
+
+// The history of slot s, newest first, into slots[0 .. T-1]; returns the number of entries found (0: s is outside the
+// buffer or empty).  The walk stops where the episode started (prev < 0) or where the predecessor was dropped or
+// overwritten (its slot holds another ordinal); ordinals strictly decrease along a chain.  The rest is -1, or with
+// pad_edge the last slot found.
+TC_HD int32_t tc_history_walk(const int64_t* prev, const int64_t* ordinal, int mode, uint64_t seed, int64_t cap, int64_t s,
+                              int32_t T, int pad_edge, int64_t* slots) {
+  int32_t valid = 0;
+  if (s >= 0 && s < cap && ordinal[s] >= 0) {
+    slots[0] = s;
+    valid = 1;
+    while (valid < T) {
+      const int64_t p = prev[s];
+      if (p < 0) break;
+      const int64_t q = tc_collect_slot(mode, seed, p, cap);
+      if (q < 0 || ordinal[q] != p) break;
+      slots[valid++] = s = q;
+    }
+  }
+  const int64_t fill = pad_edge && valid > 0 ? s : -1;
+  for (int32_t t = valid; t < T; t++) slots[t] = fill;
+  return valid;
+}
 #endif

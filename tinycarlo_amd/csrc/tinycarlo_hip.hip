@@ -7,7 +7,8 @@
 //   k_probe.h    timing / marker probes and the ablation switches (in no shipped kernel)
 //   k_common.h   LDS layout, the env's LiveLds record, KArgs / MultiArgs, wavefront helpers
 //   k_feat.h     reward / termination terms, per-env cars, camera bank, episodes, controller (the FEAT template mask)
-//   k_collect.h  the sample buffer's kernels (tc_collect: scan, rank, claim, copy); no env handle, no template
+//   k_collect.h  the sample buffer's kernels (tc_collect: scan, rank, claim, copy; tc_collect_link); no env handle, no template
+//   k_history.h  frame histories out of the sample buffer (tc_history_resolve; tc_gather_frames, a template compiled in part 0)
 // The kernel stages follow in this file, each with its own argument block (RArgs, StepArgs, FrameArgs, NArgs), then the
 // host side (from `// Host side: C ABI` down):
 //   camera       phase C  transform -> 4 clip passes -> project -> visibility -> draw list (camera.py:52-110)
@@ -56,6 +57,7 @@
 #include "k_common.h"
 #include "k_feat.h"
 #include "k_collect.h"
+#include "k_history.h"
 
 // ---------------------------------------------------------------------------------------------
 // Per-lane register cache of the map: lane `tid` keeps nodes / edges (w*K + k)*64 + tid, k < K, of window w.
@@ -5498,6 +5500,125 @@ extern "C" int tc_collect(const tc_collect_desc* d, int32_t n_rows, const uint8_
   if (d->mode == TC_COLLECT_RANDOM)
     hipLaunchKernelGGL(tc_collect_claim, dim3((unsigned)((pairs + TC_COLLECT_NT - 1) / TC_COLLECT_NT)), block, 0, st, a);
   hipLaunchKernelGGL(tc_collect_copy, dim3((unsigned)((pairs + TC_COLLECT_NT / 64 - 1) / (TC_COLLECT_NT / 64))), block, 0, st, a);  // one wavefront per (row, env)
+  HIP_TRY(hipGetLastError());
+  return TC_OK;
+}
+
+extern "C" int tc_collect_link(const tc_collect_desc* d, int32_t n_rows, const uint8_t* terminated, const uint8_t* truncated,
+                               int64_t* chain, int64_t* link_rows, void* stream) {
+  // (every check comes before the first HIP call; the fields tc_collect alone uses are its business)
+  auto bad = [](const char* what) {
+    set_err(std::string("tc_collect_link: ") + what);
+    return TC_E_INVALID;
+  };
+  auto mis = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (!d) return bad("NULL descriptor");
+  if (!d->pending || !d->age || !d->counters || !d->scratch || !chain || !link_rows)
+    return bad("pending, age, counters, scratch, chain and link_rows are required");
+  if (n_rows < 1 || d->capacity < 1 || d->num_envs < 1) return bad("n_rows, capacity and num_envs must be positive");
+  if ((int64_t)n_rows * d->num_envs >= (1ll << 26)) return bad("n_rows * num_envs must be below 2^26");
+  if (d->stride < 1) return bad("stride must be at least 1");
+  if (mis(d->counters, 8) || mis(d->age, 4) || mis(d->scratch, 16) || mis(chain, 8) || mis(link_rows, 8))
+    return bad("counters, chain and link_rows must be 8-byte, age 4-byte, scratch 16-byte aligned");
+  if (d->scratch_bytes < tc_collect_scratch_size(n_rows, d->num_envs)) return bad("scratch is too small (tc_collect_scratch_bytes)");
+  CollectArgs a;
+  a.d = *d;
+  a.rows = n_rows;
+  a.waves = (int)tc_collect_waves(d->num_envs);
+  a.vec16 = 0;
+  a.obs_rows = nullptr;
+  a.terminated = terminated;
+  a.truncated = truncated;
+  const size_t cells = (size_t)n_rows * a.waves;
+  a.head = (long long*)d->scratch;
+  a.mask = (unsigned long long*)((char*)d->scratch + 16);
+  a.base = (int*)((char*)d->scratch + 16 + cells * 8);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 block(TC_COLLECT_NT), envs((unsigned)((d->num_envs + TC_COLLECT_NT - 1) / TC_COLLECT_NT));
+  hipLaunchKernelGGL(tc_collect_link_scan, envs, block, 0, st, a);
+  hipLaunchKernelGGL(tc_collect_link_rank, dim3(1), block, 0, st, a);
+  hipLaunchKernelGGL(tc_collect_link_walk, envs, block, 0, st, a, (long long*)chain, (long long*)link_rows);
+  HIP_TRY(hipGetLastError());
+  return TC_OK;
+}
+
+extern "C" int tc_history_resolve(const int64_t* prev, const int64_t* ordinal, int64_t capacity, int32_t mode, uint64_t seed,
+                                  const int64_t* index, int64_t n_index, int32_t T, int32_t pad, int64_t* slots,
+                                  int64_t* next_slots, int32_t* valid, void* stream) {
+  auto bad = [](const char* what) {
+    set_err(std::string("tc_history_resolve: ") + what);
+    return TC_E_INVALID;
+  };
+  auto mis = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (!prev || !ordinal || !index || !slots || !valid) return bad("prev, ordinal, index, slots and valid are required");
+  if (capacity < 1 || T < 1 || n_index < 0) return bad("capacity and T must be positive, n_index not negative");
+  if (n_index >= (1ll << 31) * TC_HISTORY_NT) return bad("n_index is too large for one launch");
+  if (mode != TC_COLLECT_STOP && mode != TC_COLLECT_RING && mode != TC_COLLECT_RANDOM) return bad("unknown mode");
+  if (mode == TC_COLLECT_RANDOM && capacity >= (1ll << 32)) return bad("TC_COLLECT_RANDOM needs capacity < 2^32");
+  if (pad != TC_PAD_ZERO && pad != TC_PAD_EDGE) return bad("pad must be TC_PAD_ZERO or TC_PAD_EDGE");
+  if (mis(prev, 8) || mis(ordinal, 8) || mis(index, 8) || mis(slots, 8) || mis(next_slots, 8) || mis(valid, 4))
+    return bad("prev, ordinal, index, slots and next_slots must be 8-byte, valid 4-byte aligned");
+  if (n_index == 0) return TC_OK;
+  ResolveArgs a;
+  a.prev = (const long long*)prev;
+  a.ordinal = (const long long*)ordinal;
+  a.capacity = capacity;
+  a.mode = mode;
+  a.T = T;
+  a.pad = pad;
+  a.seed = seed;
+  a.index = (const long long*)index;
+  a.n_index = n_index;
+  a.slots = (long long*)slots;
+  a.next_slots = (long long*)next_slots;
+  a.valid = valid;
+  hipLaunchKernelGGL(tc_history_resolve_walk, dim3((unsigned)((n_index + TC_HISTORY_NT - 1) / TC_HISTORY_NT)), dim3(TC_HISTORY_NT), 0,
+                     (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return TC_OK;
+}
+
+template <int DT>
+static void launch_gather(bool wide, dim3 grid, hipStream_t st, const uint8_t* src, const uint8_t* src2, int64_t n_src, int64_t F,
+                          const int64_t* index, int64_t n_out, int64_t group, void* dst) {
+  constexpr int V = DT == TC_U8 ? 16 : DT == TC_F32 ? 4 : 8;  // source bytes of one 16-byte store
+  if (wide)
+    hipLaunchKernelGGL((tc_gather_frames_k<DT, V>), grid, dim3(TC_HISTORY_NT), 0, st, src, src2, (long long)n_src, (long long)F,
+                       (const long long*)index, (long long)n_out, (long long)group, (unsigned char*)dst);
+  else
+    hipLaunchKernelGGL((tc_gather_frames_k<DT, 4>), grid, dim3(TC_HISTORY_NT), 0, st, src, src2, (long long)n_src, (long long)F,
+                       (const long long*)index, (long long)n_out, (long long)group, (unsigned char*)dst);
+}
+
+extern "C" int tc_gather_frames(const uint8_t* src, const uint8_t* src2, int64_t n_src_frames, int64_t frame_bytes,
+                                const int64_t* index, int64_t n_out, int64_t group, void* dst, int32_t dst_dtype, void* stream) {
+  auto bad = [](const char* what) {
+    set_err(std::string("tc_gather_frames: ") + what);
+    return TC_E_INVALID;
+  };
+  auto mis = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (!src || !index || !dst) return bad("src, index and dst are required");
+  if (n_src_frames < 1 || frame_bytes < 1 || n_out < 0) return bad("n_src_frames and frame_bytes must be positive, n_out not negative");
+  if (frame_bytes % 4 != 0) return bad("frame_bytes must be a multiple of 4");
+  if (src2 && group < 1) return bad("group must be at least 1 with a second source");
+  if (dst_dtype != TC_U8 && dst_dtype != TC_F16 && dst_dtype != TC_BF16 && dst_dtype != TC_F32)
+    return bad("dst_dtype must be TC_U8, TC_F16, TC_BF16 or TC_F32");
+  if (mis(src, 4) || mis(src2, 4) || mis(index, 8) || mis(dst, 16)) return bad("src and src2 must be 4-byte, index 8-byte, dst 16-byte aligned");
+  if (n_out == 0) return TC_OK;
+  const int V = dst_dtype == TC_U8 ? 16 : dst_dtype == TC_F32 ? 4 : 8;
+  const bool wide = frame_bytes % V == 0 && !mis(src, (uintptr_t)V) && !mis(src2, (uintptr_t)V);
+  const long long chunks = (frame_bytes / (wide ? V : 4) + TC_HISTORY_NT - 1) / TC_HISTORY_NT;
+  // (as tc_unpack_bits: enough workgroups to fill the device several times over, several stores in flight per lane)
+  const unsigned int gx = (unsigned int)(chunks < 64 ? chunks : (chunks + 3) / 4 < 64 ? 64 : (chunks + 3) / 4 < 1024 ? (chunks + 3) / 4 : 1024);
+  const long long want_y = (32768 + gx - 1) / gx;
+  const dim3 grid(gx, (unsigned int)(n_out < want_y ? n_out : want_y));
+  hipStream_t st = (hipStream_t)stream;
+  switch (dst_dtype) {
+    case TC_U8: launch_gather<TC_U8>(wide, grid, st, src, src2, n_src_frames, frame_bytes, index, n_out, group, dst); break;
+    case TC_F16: launch_gather<TC_F16>(wide, grid, st, src, src2, n_src_frames, frame_bytes, index, n_out, group, dst); break;
+    case TC_BF16: launch_gather<TC_BF16>(wide, grid, st, src, src2, n_src_frames, frame_bytes, index, n_out, group, dst); break;
+    default: launch_gather<TC_F32>(wide, grid, st, src, src2, n_src_frames, frame_bytes, index, n_out, group, dst); break;
+  }
   HIP_TRY(hipGetLastError());
   return TC_OK;
 }

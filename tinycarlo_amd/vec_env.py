@@ -901,8 +901,9 @@ class TinyCarloVecEnv(gym.Env):
     def make_sample_buffer(self, capacity: int, columns=("maneuver", "steer"), **kw):
         """A `tinycarlo_amd.SampleBuffer` for this env's K-step calls: num_envs, the frame shape, its packing and the device
         filled in.  columns: names of `[K, N]` rollout keys the env can produce now (a sequence: their rollout dtypes; a
-        mapping name -> dtype must agree with them).  Other arguments (next_obs, stride, overflow, seed, max_rows) pass
-        through.  `buf.begin(obs)` after `reset()`, `buf.collect(rollout)` after each call."""
+        mapping name -> dtype must agree with them).  Other arguments (next_obs, stride, overflow, seed, max_rows, history) pass
+        through; `history=T` keeps a link per slot so that `buf.sample` returns the last T frames of the episode
+        (ReplaybufferTemporal's samples).  `buf.begin(obs)` after `reset()`, `buf.collect(rollout)` after each call."""
         from .collect import SampleBuffer
         shapes = self._rollout_shapes(1)
         needs = ((self.EPISODE_ROLLOUT_KEYS, self._episodes, "track_episodes() / set_time_limit()"),
