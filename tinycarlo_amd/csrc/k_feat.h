@@ -1,6 +1,6 @@
 // k_feat.h -- the per-env feature blocks of the simulate stages: reward / termination terms (tinycarlo/wrapper/*.py, the
 // epilogue of a step), the TC_FEAT_* template mask, per-env car rows, the camera bank, episodes, the built-in controller
-// (tc_ctrl.h) and the drive randomisation behind it.  Defines no kernel: sim_body and the grouped kernel (tinycarlo_hip.hip)
+// (tc_ctrl.h) and the drive randomisation behind it.  Defines no kernel: sim_body (k_sim.h) and the grouped kernel (k_envg.h)
 // compile these in by mask.
 #ifndef K_FEAT_H
 #define K_FEAT_H

@@ -18,7 +18,7 @@
 // inside ONE list makes the order of that list's moves matter; the pair is then refused as well and the two passes run
 // in their literal form (which replays such chains in edge order).
 //
-// The kernels evaluate this with ballots over the edge slots of a wavefront (cam_group_regs, tinycarlo_hip.hip); the
+// The kernels evaluate this with ballots over the edge slots of a wavefront (cam_group_regs, k_camera.h); the
 // scalar form below is the definition, and what tests/test_clip_merge_cpu.py proves against the oracle.
 // Plain C / HIP like tc_trig.h and tc_rng.h: the tests build this header with the host compiler.
 #ifndef TC_CLIP_H

@@ -2,7 +2,7 @@
 """Per-phase shader-clock split of ONE wavefront's pass through the step kernel, from the instrumented build
 (make -C tinycarlo_amd/csrc timing).  Usage: python tools/phase_clock.py [--envs 64 4096] [--steps 40]
 Prints, per batch size, the mean over envs and steps of the clock deltas between the probes (TSTAMP of
-csrc/k_probe.h, placed in the stages of tinycarlo_hip.hip) and each delta's share of the wavefront's lifetime."""
+csrc/k_probe.h, placed in the stages: k_sim.h, k_camera.h, k_raster.h, k_frame.h) and each delta's share of the wavefront's lifetime."""
 import argparse
 import ctypes as C
 import os
