@@ -565,6 +565,17 @@ int tc_env_reserve_steps(tc_env* env, int32_t max_call_steps);
 int tc_env_launch_info(const tc_env* env, uint32_t flags, int32_t n_steps, int32_t* fused, int32_t* kvar,
                        int32_t* steps_per_dispatch, char* name, int32_t name_cap);
 
+/* The LDS plan of the handle's frame kernel (tc_frame_kernel: one workgroup per (step, env) frame of a K-step call), for
+ * benchmark labels and tests: lds_bytes = dynamic LDS per workgroup; head_entries = draw-list entries that stay in LDS
+ * between the camera and the raster stage (longer lists take the overflow path through the global array);
+ * workgroups_per_cu = what the runtime computes for that kernel and that LDS size
+ * (hipOccupancyMaxActiveBlocksPerMultiprocessor: registers and LDS together; nothing is launched); bits_offset = where
+ * that kernel's raster stage puts its bit-planes: behind the tables of the handle's outline form (the K = 5 kernel with
+ * batches of 32) or behind full-size tables of the kernel's own batch size.  Any pointer may be NULL.  Handles
+ * whose K-step calls never run the frame kernel (kvar 13) report the plan all the same, with workgroups_per_cu = 0. */
+int tc_env_frame_lds_info(const tc_env* env, int32_t* lds_bytes, int32_t* head_entries, int32_t* workgroups_per_cu,
+                          int32_t* bits_offset);
+
 /* Workload descriptor for benchmark lines -- what the most recent frames drew: mean / max length of the frames' draw
  * lists (segments handed to cv2.polylines, camera.py:95-106) and the fraction of frames with none, over the N frames of
  * the last tc_step or, of the last tc_step_multi call, the frames of its last (up to 48) steps.  Waits for the device. */

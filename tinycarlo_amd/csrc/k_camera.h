@@ -12,6 +12,7 @@
 #include "k_common.h"
 #include "tc_clip.h"
 #include "tc_cull.h"
+#include "tc_pack.h"
 #include "tc_device.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -119,6 +120,33 @@ __device__ inline void cam_chain_replay(double* Px, double* Py, double* Pz, unsi
   }
 }
 
+// The same replay over the one-word entries of tc_pack.h (cam_group_regs' lists): the word compares as its edge id.
+__device__ inline void cam_chain_replay_packed(double* Px, double* Py, double* Pz, unsigned char* flg, int bit, double tz,
+                                               const int* list, int n, double max_range, bool range_too, int tid) {
+  for (int k = tid; k < n; k += TC_NT) {
+    const int w = list[k];
+    const int t = tc_pack_target(w);
+    bool first = true;
+    for (int j = 0; j < n; j++)
+      if (tc_pack_target(list[j]) == t && list[j] < w) first = false;
+    if (!first) continue;
+    int cur = w;
+    for (int guard = 0; guard < n; guard++) {
+      cam_move_to_plane(Px, Py, Pz, tc_pack_other(cur), t, tz);
+      int nxt = 0x7fffffff;
+      for (int j = 0; j < n; j++) {
+        const int wj = list[j];
+        if (tc_pack_target(wj) == t && wj > cur && wj < nxt) nxt = wj;
+      }
+      if (nxt == 0x7fffffff) break;
+      cur = nxt;
+    }
+    unsigned int f = flg[t] | (unsigned)bit;
+    if (range_too) f = (f & ~2u) | (Pz[t] > -max_range ? 2u : 0u);
+    flg[t] = (unsigned char)f;
+  }
+}
+
 // camera.py:133-142 for one node + the np.int32 cast of renderer.py:43,50
 __device__ inline int2 cam_project(const double* K, double X, double Y, double Z, double& u, double& v) {
   double P3[3] = {X, Y, Z};
@@ -138,12 +166,17 @@ __device__ inline int2 cam_project(const double* K, double X, double Y, double Z
 //   idx_in_range (camera.py:80) is evaluated on the depths left by passes 1-2: it is set here from the transformed depth
 // and refreshed for exactly the nodes those passes move -- the same values, without a pass over all nodes.
 // Appends the group's visible edges to the draw list at segg[5 * nseg ...] and advances nseg (wave-uniform).
-template <int K>
+// PACKED: the lists hold the one-word entries of tc_pack.h (and 16-bit projection candidates) instead of two ints per entry
+// (edge id; target | other << 16): half the list region.  The form of the kernel whose LDS plan is sized for it -- the
+// five-wave frame kernel (plan_frame(), tinycarlo_hip.hip); every other kernel keeps the two-int entries, with which its
+// register count is what it was.
+template <int K, bool PACKED = false>
 __device__ __forceinline__ void cam_group_regs(const KArgs& a, const MapCache<K>& mc, const double* pose, const double* Kc,
                                                const int l0, const int l1, const int ge0, const int nn, const int ne,
                                                double* Px, double* Py, double* Pz, unsigned char* flg, int* list,
                                                int* segg, LdsIntPtr seg_lds, int& nseg, unsigned int& my_layers, const int env,
                                                const int tid) {
+  static_assert(!PACKED || TC_PACK_FITS(K), "a group's edge and node ids must fit the one-word list entries of tc_pack.h");
   const DevMap& m = a.m;
   const DevCam& cam = a.cam;
   const double max_range = cam.max_range;
@@ -210,8 +243,12 @@ __device__ __forceinline__ void cam_group_regs(const KArgs& a, const MapCache<K>
         if (s_k) {
           const int j = n + wave_rank(mk);
           const int t = h ? mc.ed[k].y : mc.ed[k].x, o = h ? mc.ed[k].x : mc.ed[k].y;
-          list[2 * j] = k * TC_NT + tid;
-          list[2 * j + 1] = t | (o << 16);
+          if constexpr (PACKED) {
+            list[j] = tc_pack(k * TC_NT + tid, t, o);
+          } else {
+            list[2 * j] = k * TC_NT + tid;
+            list[2 * j + 1] = t | (o << 16);
+          }
           // "target of the first list" for the test below (lanes sharing the node write the same byte)
           if (merged && h == 0) flg[t] = (unsigned char)((ff[k] & 0xff) | mark);
         }
@@ -240,8 +277,8 @@ __device__ __forceinline__ void cam_group_regs(const KArgs& a, const MapCache<K>
       if (n <= TC_NT) {
         // lane j < n takes list entry j; the target nodes are compared lane against lane through v_readlane (the loop
         // over the list in LDS was one dependent LDS round trip per entry, four passes per frame)
-        mine = tid < n ? list[2 * tid + 1] : -1;
-        const int my_t = mine & 0xffff;
+        mine = tid < n ? (PACKED ? list[tid] : list[2 * tid + 1]) : -1;
+        const int my_t = PACKED ? tc_pack_target(mine) : mine & 0xffff;
         for (int j = 0; j < n; j++) {
           const int tj = __builtin_amdgcn_readlane(my_t, j);
           dup |= tid < n && j != tid && tj == my_t;
@@ -254,14 +291,17 @@ __device__ __forceinline__ void cam_group_regs(const KArgs& a, const MapCache<K>
     }
     if (!dup) {
       if (tid < n) {
-        const int t = mine & 0xffff, o = (unsigned)mine >> 16;
+        const int t = PACKED ? tc_pack_target(mine) : mine & 0xffff, o = PACKED ? tc_pack_other(mine) : (int)((unsigned)mine >> 16);
         cam_move_to_plane(Px, Py, Pz, o, t, tz);
         unsigned int f = flg[t] | (unsigned)bit;
         if (pass < 2) f = (f & ~2u) | (Pz[t] > -max_range ? 2u : 0u);
         flg[t] = (unsigned char)f;
       }
     } else {
-      cam_chain_replay(Px, Py, Pz, flg, bit, tz, list, n, max_range, pass < 2, tid);
+      if constexpr (PACKED)
+        cam_chain_replay_packed(Px, Py, Pz, flg, bit, tz, list, n, max_range, pass < 2, tid);
+      else
+        cam_chain_replay(Px, Py, Pz, flg, bit, tz, list, n, max_range, pass < 2, tid);
     }
     lds_sync();
 #pragma unroll
@@ -289,17 +329,23 @@ __device__ __forceinline__ void cam_group_regs(const KArgs& a, const MapCache<K>
   }
   lds_sync();
   int ncand = 0;
+  unsigned short* cand_list = (unsigned short*)list;  // PACKED: node ids, 16 bits each
 #pragma unroll
   for (int k = 0; k < K; k++) {
     const int i = k * TC_NT + tid;
     const bool c = i < nn && (flg[i] & 16);
     const unsigned long long mk = __ballot(c);
-    if (c) list[ncand + wave_rank(mk)] = i;
+    if (c) {
+      if constexpr (PACKED)
+        cand_list[ncand + wave_rank(mk)] = (unsigned short)i;
+      else
+        list[ncand + wave_rank(mk)] = i;
+    }
     ncand += __popcll(mk);
   }
   lds_sync();
   for (int k = tid; k < ncand; k += TC_NT) {  // camera.py:133-142, 90
-    const int i = list[k];
+    const int i = PACKED ? (int)cand_list[k] : list[k];
     double u, v;
     int2 q = cam_project(Kc, Px[i], Py[i], Pz[i], u, v);
     const bool vis = (u > 0) && (u < cam.W) && (v > 0) && (v < cam.H) && (flg[i] & 3) == 3;
@@ -318,15 +364,19 @@ __device__ __forceinline__ void cam_group_regs(const KArgs& a, const MapCache<K>
     const unsigned long long mk = __ballot(draw);
     if (draw) {
       const int j = ndraw + wave_rank(mk);
-      list[2 * j] = k * TC_NT + tid;
-      list[2 * j + 1] = mc.ed[k].x | (mc.ed[k].y << 16);
+      if constexpr (PACKED) {
+        list[j] = tc_pack(k * TC_NT + tid, mc.ed[k].x, mc.ed[k].y);
+      } else {
+        list[2 * j] = k * TC_NT + tid;
+        list[2 * j + 1] = mc.ed[k].x | (mc.ed[k].y << 16);
+      }
     }
     ndraw += __popcll(mk);
   }
   lds_sync();
   for (int j = tid; j < ndraw; j += TC_NT) {  // both ends were marked above and hold pixel coordinates
-    const int e = list[2 * j], xy = list[2 * j + 1];
-    const int2 pa = ((int2*)Px)[xy & 0xffff], pb = ((int2*)Px)[(unsigned)xy >> 16];
+    const int w = PACKED ? list[j] : list[2 * j + 1], e = PACKED ? tc_pack_edge(w) : list[2 * j];
+    const int2 pa = ((int2*)Px)[PACKED ? tc_pack_target(w) : w & 0xffff], pb = ((int2*)Px)[PACKED ? tc_pack_other(w) : (int)((unsigned)w >> 16)];
     int layer = l0;
     for (int c = l0 + 1; c < l1; c++) layer += (ge0 + e) >= m.edge_off[c];
     my_layers |= 1u << layer;
@@ -509,7 +559,9 @@ __device__ __forceinline__ bool cam_cull(const KArgs& a, const double* pose) {
   return empty;
 }
 
-template <int K>
+// LEAN: the form of the five-wave frame kernel -- the camera's K matrix in scalar registers (see below) and the one-word list
+// entries of cam_group_regs<K, PACKED>
+template <int K, bool LEAN = false>
 __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, int env, int cam_row, const double* pose_in, MapCache<K>& mc,
                                          const bool mc_loaded, const int tid, const int seg_row, int& nseg_out,
                                          unsigned int& used_out, const bool store_n = true) {
@@ -541,10 +593,13 @@ __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, in
   int* list = (int*)(smem + a.lds.off_list);
   int* cnt = (int*)(smem + a.lds.off_cnt);
   const DevCam& cam = a.cam;
+  // (LEAN: wave-uniform like the pose, and kept in scalar registers like it: as vector values the nine entries are 18
+  // VGPRs held from here across the clip passes to the projection -- the registers the frame kernel's five-wave bound
+  // lacks.  The kernels that simulate in the same wavefront sit at their SGPR limit already and keep the vector form.)
   double Kc[9];
   if (a.cam_K) {  // (a branch, not a select of pointers: the shared camera's K then comes in scalar loads)
 #pragma unroll
-    for (int i = 0; i < 9; i++) Kc[i] = a.cam_K[(size_t)cam_row * 9 + i];  // (the row that came with the pose, not the env's latest)
+    for (int i = 0; i < 9; i++) Kc[i] = LEAN ? uni_d(a.cam_K[(size_t)cam_row * 9 + i]) : a.cam_K[(size_t)cam_row * 9 + i];  // (the row that came with the pose, not the env's latest)
   } else {
     const __attribute__((address_space(4))) double* kk = (const __attribute__((address_space(4))) double*)(unsigned long long)cam.K;
 #pragma unroll
@@ -577,7 +632,7 @@ __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, in
       }
     }
     if (one) {
-      cam_group_regs<K>(a, mc, pose, Kc, l0, l1, ge0, nn, ne, Px, Py, Pz, flg, list, segg, (LdsIntPtr)(smem + a.seg_lds_off), nseg,
+      cam_group_regs<K, LEAN>(a, mc, pose, Kc, l0, l1, ge0, nn, ne, Px, Py, Pz, flg, list, segg, (LdsIntPtr)(smem + a.seg_lds_off), nseg,
                         my_layers, env, tid);
       continue;
     }

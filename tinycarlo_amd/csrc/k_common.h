@@ -54,6 +54,15 @@ __device__ __forceinline__ const T& kernarg_again(const T& r) {
 #define R_OFF_TAB 0
 #define R_TAB_BYTES_OF(RB) (((RB) * 4 * 5 + (RB) * 4 + 5 * (RB) + 8 * (RB)) * 4 + 2 * 4 * (RB) * 8)
 #define R_OFF_BITS_OF(RB) ((R_TAB_BYTES_OF(RB) + 15) / 16 * 16)
+// The tables of the five-wave frame kernel (raster_body<.., FORM>), which is launched with an LDS plan of the handle's outline
+// form (plan_frame_lds, tc_plan.h): those of fixed size first (116 bytes per segment), then the two with an entry per outline
+// item, the chunk counts `lc` (4 bytes) and the outline-edge parameters `lt` (20 bytes).  A batch has RB << sh items: sh = 2,
+// the four edges of FillConvexPoly's quad, or sh = 1, the two long ones (R_F_LONG_EDGES); the bit-planes follow at
+// RArgs::off_bits = R_OFF_BITS_SH(RB, sh).  Every other kernel keeps room for RB * 4 items and the layout above.
+#define R_OFF_LC_OF(RB) ((RB) * 116)
+#define R_TAB_BYTES_SH(RB, sh) (R_OFF_LC_OF(RB) + ((RB) << (sh)) * (4 + 5 * 4))
+#define R_OFF_BITS_SH(RB, sh) ((R_TAB_BYTES_SH(RB, sh) + 15) / 16 * 16)
+static_assert(R_TAB_BYTES_SH(32, 2) == R_TAB_BYTES_OF(32) && R_TAB_BYTES_SH(16, 2) == R_TAB_BYTES_OF(16), "the four-edge form is the full size");
 #define LCH 8        // outline steps per chunk
 
 #define TC_MAX_GROUPS 8

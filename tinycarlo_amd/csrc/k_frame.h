@@ -107,6 +107,17 @@ __device__ __forceinline__ bool frame_pose(const size_t slot0, const int env, co
   return true;
 }
 
+// Waves per SIMD the frame kernel is compiled for.  The K = 5 kernel with batches of 32 (simple_layout and the other
+// small maps) is held to 96 VGPRs, five wavefronts per SIMD: its LDS plan (plan_frame_lds) leaves room for 18 workgroups
+// per CU, and with four per SIMD the register file would stop at 16.
+#ifndef TC_FRAME_WAVES_K5
+#define TC_FRAME_WAVES_K5 5
+#endif
+#define TC_FRAME_WAVES(K, RBT) ((K) <= 5 ? ((RBT) == 32 ? TC_FRAME_WAVES_K5 : 4) : (K) <= 9 ? 3 : 2)
+// ... and that kernel alone runs the forms that go with the plan: cam_body<K, LEAN> (one-word list entries, the camera's K
+// matrix in scalar registers) and raster_body<.., FORM> (outline tables sized by the form).  Every other instantiation, and the
+// recover kernel of every handle but that one's, is the code it was.
+#define TC_FRAME_LEAN(K, RBT) ((K) <= 5 && (RBT) == 32)
 // One frame: `rowy` is the frame's row in the launch (its step), `env` its env.
 // HOT (tc_frame_kernel): the raster stage in its LDS-only form (see raster_body); !HOT (the recover kernel): the generic form.
 template <int K, bool THICK, int FMT, bool HOT, int RBT>
@@ -125,7 +136,7 @@ __device__ __forceinline__ void frame_one(unsigned char* smem, const int env, co
     TSTAMP_CLEAR();
     TSTAMP(3);
     TSTAMP_REAL(30);
-    cam_body<K>(fa.a, smem, env, cam_row, pose, mc, false, tid, row, nseg, used, false);
+    cam_body<K, TC_FRAME_LEAN(K, RBT)>(fa.a, smem, env, cam_row, pose, mc, false, tid, row, nseg, used, false);
   }
   const FrameArgs& fr = frame_args();
   const size_t slot0 = (size_t)(fr.r.seg_row0 + rowy) * fr.a.N;
@@ -142,7 +153,7 @@ __device__ __forceinline__ void frame_one(unsigned char* smem, const int env, co
   } else {
     lds_sync();
   }
-  raster_body<THICK, FMT, HOT, RBT>(fr.r, smem, env, fr.r.obs + (size_t)rowy * fr.r.obs_row_stride, tid, slot0, nseg, used,
+  raster_body<THICK, FMT, HOT, RBT, TC_FRAME_LEAN(K, RBT)>(fr.r, smem, env, fr.r.obs + (size_t)rowy * fr.r.obs_row_stride, tid, slot0, nseg, used,
                                            fr.r.noise_row0 + rowy);
   {
     const FrameArgs& fe = frame_args();
@@ -160,7 +171,7 @@ __device__ __forceinline__ void frame_one(unsigned char* smem, const int env, co
 // raster batch.  K = 5 with RBT = 16 is the variant of maps whose camera groups are packs of connected components (knuffingen:
 // the map needs K = 9 as a whole or layer by layer, its component groups fit K = 5).
 template <int K, bool THICK, int FMT, int RBT = RB_OF_K(K)>
-__global__ __launch_bounds__(TC_NT, (K <= 5 ? 4 : K <= 9 ? 3 : 2)) void tc_frame_kernel(FrameArgs fa_unused) {
+__global__ __launch_bounds__(TC_NT, TC_FRAME_WAVES(K, RBT)) void tc_frame_kernel(FrameArgs fa_unused) {
   extern __shared__ __align__(16) unsigned char smem[];
   const FrameArgs& fa = frame_args();
   if ((int)blockIdx.x >= fa.a.N) return;

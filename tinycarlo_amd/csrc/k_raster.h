@@ -104,13 +104,17 @@ __device__ __forceinline__ void packed_copy_words(unsigned char* dst, const unsi
     for (int i = tid; i < nw; i += TC_NT) ((unsigned int*)dst)[i] = src[i];
   }
 }
-template <bool THICK, int FMT, bool LDSONLY = false, int RB = RB_MAX>
+// FORM (the five-wave frame kernel, whose LDS plan is sized for it: plan_frame_lds): the outline tables hold the RB << sh items
+// of the handle's outline form -- sh = 2, the four edges of FillConvexPoly's quad, or 1, the two long ones (R_F_LONG_EDGES) --
+// and the bit-planes follow at RArgs::off_bits.  Otherwise the tables have their full size at compile-time offsets.
+template <bool THICK, int FMT, bool LDSONLY = false, int RB = RB_MAX, bool FORM = false>
 __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem, int env, unsigned char* obs_base,
                                             const int tid, const size_t seg_slot0, const int nseg_in,
                                             const unsigned int used_in, const int frame_row) {
   const RArgs& a = a0;
   const RCam& cam = a.cam;
-  unsigned int* bits = (unsigned int*)(smem + R_OFF_BITS_OF(RB));
+  // (FORM: behind tables sized by the outline form, where the host's plan says: R_OFF_BITS_SH(RB, sh))
+  unsigned int* bits = (unsigned int*)(smem + (FORM ? a.off_bits : R_OFF_BITS_OF(RB)));
   const int* segg = a.seg_g + (seg_slot0 + env) * a.seg_cap * 5;
   // draw-list entry k: from LDS when the camera stage of this wavefront left it there (tc_frame_kernel), else global
   const LdsIntPtr seg_lds = (LdsIntPtr)(smem + a.seg_lds_off);
@@ -160,9 +164,12 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
   const int H = cam.H, W = cam.W, wpr = cam.wpr, C = a.C;
   constexpr bool CLS = TC_FMT_IS_CLASSES(FMT), BITS = FMT == TC_FMT_CLASSES_BITS;
   unsigned char* out = obs_base + (size_t)env * tc_obs_bytes_of(FMT, C, H, W);
-  int* lt = (int*)(smem + R_OFF_TAB);     // [RB*4][5] outline-edge parameters
-  int* lc = lt + RB * 4 * 5;              // [RB*4] chunks per outline edge, then exclusive prefix
-  int* fl = lc + RB * 4;                  // [RB] first fill row of the segment in this band
+  // Every kernel but FORM ones: lt and lc in front, with room for RB * 4 items, then the tables of fixed size -- all at
+  // compile-time offsets.  FORM: the tables of fixed size (116 bytes per segment) in front, then lc and lt for the RB << sh
+  // items of the handle's outline form (placed in the batch loop below, where sh is read).
+  int* lt0 = (int*)(smem + R_OFF_TAB);    // [RB*4][5] outline-edge parameters
+  int* lc0 = lt0 + RB * 4 * 5;            // [RB*4] chunks per outline edge, then exclusive prefix
+  int* fl = FORM ? (int*)(smem + R_OFF_TAB) : lc0 + RB * 4;  // [RB] first fill row of the segment in this band
   int* fc = fl + RB;                      // [RB] fill rows, then exclusive prefix
   int* fm = fc + RB;                      // [RB] pieces | walker mask << 8 | quad valid << 16
   int* fd = fm + RB;                      // [RB][2] ThickLine's (dp.x, dp.y)
@@ -170,6 +177,7 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
   int* fpv = fpy + 4 * RB;                // [RB][4] fill pieces: polygon vertices idx0 | idx << 2
   long long* fpx = (long long*)(fpv + 4 * RB);  // [RB][4] x at the start row (16.16)
   long long* fpd = fpx + 4 * RB;          // [RB][4] dx per row
+  static_assert(R_OFF_LC_OF(RB) == 13 * RB * 4 + 2 * 4 * RB * 8 && (13 * RB * 4) % 8 == 0, "FORM: lc starts where the fixed tables end");
   // Class masks, one band: the planes of layers that have no segment in this frame are all zeros (unless noise blobs are
   // going to copy into them) and are stored NOW, at the head of the stage -- their 16-byte stores drain while the used
   // planes are rasterised instead of queueing behind each other at the end of the wavefront's life (the store phase
@@ -240,7 +248,7 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
         continue;
       }
     }
-    {  // (R_OFF_BITS_OF(RB) is a multiple of 16: whole 16-byte writes, then the odd words)
+    {  // (the bit-planes' offset is a multiple of 16: whole 16-byte writes, then the odd words)
       const int n4 = nwords >> 2;
       for (int i = tid; i < n4; i += TC_NT) ((uint4*)bits)[i] = make_uint4(0, 0, 0, 0);
       for (int i = (n4 << 2) + tid; i < nwords; i += TC_NT) bits[i] = 0;
@@ -348,7 +356,10 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
         // no segment has more than two pieces).
         // (everything the two forms differ in hangs on one scalar: items per segment = 1 << sh)
         const int sh = (a.flags & R_F_LONG_EDGES) ? 1 : 2;
-        for (int t = tid; t < RB * 4; t += TC_NT) {
+        const int n_items = FORM ? RB << sh : RB * 4;  // entries of lc and lt that exist
+        int* lc = FORM ? (int*)(fpd + 4 * RB) : lc0;   // [items] chunks per outline edge, then exclusive prefix
+        int* lt = FORM ? lc + n_items : lt0;           // [items][5] outline-edge parameters
+        for (int t = tid; t < n_items; t += TC_NT) {
           int nchunk = 0;
           const int j = t >> sh;
           if (t < (nb << sh) && ((fm[j] >> 16) & 1)) {
@@ -395,16 +406,19 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
         {  // exclusive prefix sums (RB*4 = 2 entries per lane, or 1 when RB = 16; RB entries on the low lanes)
           static_assert(RB * 4 == 2 * TC_NT || RB * 4 == TC_NT, "outline-edge chunk counts: one or two per lane");
           constexpr bool TWO = RB * 4 == 2 * TC_NT;
-          int v0 = TWO ? lc[2 * tid] : lc[tid], v1 = TWO ? lc[2 * tid + 1] : 0;
+          // (FORM, two-edge form: half the items, one entry per lane -- or none: wave-uniform)
+          const bool two = TWO && !(FORM && sh == 1);
+          const bool mine = !FORM || tid < n_items;  // (without FORM every lane has its entry: RB * 4 >= TC_NT)
+          int v0 = two ? lc[2 * tid] : (mine ? lc[tid] : 0), v1 = two ? lc[2 * tid + 1] : 0;
           int inc = wave_incl_scan(v0 + v1, tid);
           tot_l = __builtin_amdgcn_readlane(inc, TC_NT - 1);
           int f = tid < RB ? fc[tid] : 0;
           int finc = wave_incl_scan(f, tid);
           tot_f = __builtin_amdgcn_readlane(finc, TC_NT - 1);
-          if (TWO) {
+          if (two) {
             lc[2 * tid] = inc - v0 - v1;  // each lane rewrites only the entries it read
             lc[2 * tid + 1] = inc - v1;
-          } else {
+          } else if (mine) {
             lc[tid] = inc - v0;
           }
           if (tid < RB) fc[tid] = finc - f;
@@ -412,7 +426,7 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
         lds_sync();
         TSTAMP(11);
         for (int c = tid; c < tot_l && !DBG_ON(a.flags, DBG_SKIP_R2); c += TC_NT) {  // outline pixels, LCH steps per chunk
-          int lo = 0, hi = RB * 4;
+          int lo = 0, hi = n_items;
           while (hi - lo > 1) {
             int mid = (lo + hi) >> 1;
             if (lc[mid] <= c) lo = mid; else hi = mid;
@@ -464,7 +478,7 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
       const int nbl = a.noise_blobs, nb = C * nbl, mr = a.noise_max_radius;
       int* bp = (int*)(smem + R_OFF_TAB);                 // [nb][2] (x | y << 16), (r | mode << 12 | src << 16): the
       unsigned char* bh = (unsigned char*)(bp + 2 * nb);  // raster tables are dead here;  [nb][rows] half widths
-      const bool staged = nb * 8 + nb * rows <= R_TAB_BYTES_OF(RB);
+      const bool staged = nb * 8 + nb * rows <= (FORM ? a.off_bits : R_OFF_BITS_OF(RB)) - R_OFF_TAB;
       const unsigned int nstep = *a.noise_step + (unsigned int)frame_row;
       for (int k = tid; k < nb; k += TC_NT) {
         const tc_blob bl = tc_noise_blob(a.noise_seed, (uint32_t)env, nstep, (uint32_t)k, W, H, mr, C);

@@ -184,6 +184,77 @@ static inline void plan_cam_lds(Layout& L, int cap_n, int cap_e, int total_nodes
   L.total = off;
 }
 
+// LDS of a tc_frame_kernel / tc_frame_recover_kernel workgroup.  These kernels keep no env state in LDS and run the
+// camera stage and the raster stage one after the other, so a workgroup needs the larger of the two stages plus the head
+// of the frame's draw list, which both stages see -- and how many workgroups a CU holds follows from that sum in steps of
+// 1280 bytes.  Where plan_cam_lds and the full-size raster tables are sized for every path a kernel may take, this plan
+// is sized for the paths THIS handle takes:
+//   - camera groups held in registers (`windowed` false) use the one-word list entries of tc_pack.h and keep their counts
+//     in registers: the list region is tc_pack_list_bytes, and there is no counter block (off_cnt then names the list
+//     region: nothing reads it).  A windowed group keeps the two-int entries and the 64-byte block of plan_cam_lds.
+//   - the outline table `lt` holds rb << sh items: sh = 1 when the handle draws with the two long outline edges
+//     (R_F_LONG_EDGES), 2 otherwise (the layout of k_common.h's R_OFF_LC_OF / R_OFF_BITS_SH, repeated here in plain
+//     arithmetic; the host source asserts that the two agree).
+// The head sits behind whichever stage is larger and takes what is left up to the next 1280-byte step (at least `live`
+// bytes, the slot the fused kernels park the env in: the head never gets smaller than it would be without any growth),
+// at most 4096 bytes more, and the whole never exceeds `limit`, the bytes the layout shared with the other kernels
+// gives a frame workgroup (0: no limit).  seg_lds / seg_lds_limit: the switches TC_SEG_LDS / TC_SEG_LDS_CAP; the frame
+// kernels read draw lists from LDS only, so the head holds 8 entries whatever they say.  reserve: bytes of static LDS
+// the build adds to every workgroup (the stamp buffer of the timing builds), taken out of the growth.
+struct FrameLds {
+  int off_p = 0, off_flg = 0, off_list = 0, off_cnt = 0;  // camera stage
+  int cam_total = 0;
+  int list_bytes = 0;
+  bool counters = false;
+  int r_off_tab = 0, r_off_bits = 0;  // raster stage
+  int r_total = 0;
+  int head_off = 0, head_cap = 0;  // draw-list head: head_cap entries of 20 bytes
+  int total = 0;                   // dynamic LDS of the launch
+};
+#define TC_LDS_STEP 1280
+#define TC_SEG_ENTRY_BYTES 20
+static inline FrameLds plan_frame_lds(int cap_n, int cap_e, int total_nodes, bool windowed, int rb, int sh, int band_bytes,
+                                      int live, bool seg_lds, int seg_lds_limit, int limit, int reserve) {
+  FrameLds f;
+  const int cap_nodes = cap_n > 0 ? cap_n : 1;
+  int off = 0;
+  f.off_p = off;
+  int pbytes = 3 * cap_nodes * 8;
+  if (total_nodes * 8 > pbytes) pbytes = total_nodes * 8;
+  off += align_up(pbytes, 16);
+  f.off_flg = off;
+  off += align_up(cap_nodes, 16);
+  f.off_list = off;
+  f.list_bytes = windowed ? (2 * cap_e > cap_n ? 2 * cap_e : cap_n) * 4 + 16 : (4 * cap_e > 2 * cap_n ? 4 * cap_e : 2 * cap_n) + 16;
+  f.list_bytes = align_up(f.list_bytes, 16);
+  off += f.list_bytes;
+  f.counters = windowed;
+  f.off_cnt = windowed ? off : f.off_list;
+  if (windowed) off += 64;
+  f.cam_total = off;
+  f.r_off_tab = 0;
+  f.r_off_bits = align_up(rb * 116 + (rb << sh) * (4 + 5 * 4), 16);
+  f.r_total = f.r_off_bits + align_up(band_bytes, 16);
+  f.head_off = align_up(f.cam_total > f.r_total ? f.cam_total : f.r_total, 16);
+  const int want = f.head_off + live;
+  int grown = align_up(want + reserve, TC_LDS_STEP) - reserve;
+  if (grown > want + 4096) grown = want + 4096;
+  if (limit > 0 && grown > limit) grown = limit;
+  if (grown < want) grown = want;
+  f.total = grown;
+  f.head_cap = (grown - f.head_off) / TC_SEG_ENTRY_BYTES;
+  if (!seg_lds) {
+    f.head_cap = 0;
+    f.total = want;
+  }
+  if (f.head_cap > seg_lds_limit) f.head_cap = seg_lds_limit;
+  if (f.head_cap < 8) {
+    f.head_cap = 8;
+    if (f.total < f.head_off + 8 * TC_SEG_ENTRY_BYTES) f.total = f.head_off + 8 * TC_SEG_ENTRY_BYTES;
+  }
+  return f;
+}
+
 // Which way a call of nsteps steps goes through launch() on a handle: decided here for launch(), which dispatches on
 // it, and for tc_env_launch_info, which reports it.  What the decision reads of the handle and of the call comes in as
 // plain values (the host side fills them in one place, plan_of()).

@@ -202,6 +202,13 @@ static frame_kern_t frame_kernel_of(int kcode, bool thick, int fmt, bool recover
       },
       Kcodes{kcode}, Thicks{thick}, FrameFmts{fmt}, Bools{recover});
 }
+// K and batch size of the kernel frame_kernel_of picks for a code: what the host plans that kernel's LDS from
+static int frame_k_of(int kcode) {
+  return lift([](auto kc) -> int { return FrameKRb<kc>::K; }, Kcodes{kcode});
+}
+static int frame_rb_of(int kcode) {
+  return lift([](auto kc) -> int { return FrameKRb<kc>::RB; }, Kcodes{kcode});
+}
 static raster_kern_t raster_kernel_of(bool thick, int fmt) {
   return lift([](auto t, auto f) -> raster_kern_t { return tc_raster_kernel<t, f>; }, Thicks{thick}, FrameFmts{fmt});
 }
@@ -476,6 +483,13 @@ struct tc_env {
   int kvar = 0;    // register-cache slots of the simulate stage: 5, 8 (whole map in one window), 9 (camera layer groups), 13
   int kframe = 0;  // tc_frame_kernel variant: kvar, or 516 (K = 5, batches of 16) when every component group fits 320 nodes / edges
   int frame_seg_cap = 0;  // tc_frame_kernel's own capacity: seg_lds_cap, but never below 8 (its raster stage reads the list from LDS only)
+  // tc_frame_kernel / tc_frame_recover_kernel: their own LDS plan (plan_frame_lds, tc_plan.h), remade when the camera's
+  // outline form changes (tc_env_set_camera).  frame_lds = fl.total (+ the experiments' padding); shared_frame_lds: what
+  // the layout shared with the other kernels would give a frame workgroup, the plan's upper limit
+  FrameLds fl;
+  int plan_cap_n = 0, plan_cap_e = 0;  // nodes / edges of the largest camera group, as planned at tc_env_create
+  int shared_frame_lds = 0, shared_seg_cap = 0;  // (and the head capacity that goes with them)
+  int r_off_bits_k = 0;  // bit-plane offset of the fused kernels of this handle's variant (full-size tables of their batch size)
   // optional per-kernel timing: a ring of (start, mid, end) HIP events recorded on the caller's stream
   int prof = 0;    // 0 = off, n = record every n-th tc_step
   int prof_n = 0;  // launches recorded so far
@@ -849,11 +863,69 @@ static void layout_lds(tc_env* e, int cap_n, int cap_e) {
   }
   e->r_off_tab = R_OFF_TAB;
   e->r_off_bits = R_OFF_BITS_OF(RB_MAX);
+  e->r_off_bits_k = r_off_bits_k;
+  e->plan_cap_n = cap_n;
+  e->plan_cap_e = cap_e;
   e->r_lds = e->r_off_bits + align_up(dc.band_rows * row_bytes, 16);
   // the env's parked state (tc_step_multi) sits behind whichever stage needs more, so that neither aliases it
   const int r_lds_k = r_off_bits_k + align_up(dc.band_rows * row_bytes, 16);
   L.off_live = align_up(L.total > r_lds_k ? L.total : r_lds_k, 16);
   L.total = L.off_live + TC_LIVE_BYTES;
+}
+
+// items per segment of the outline tables, as a shift: 1 = the two long edges (R_F_LONG_EDGES), 2 = all four
+static int outline_shift(const tc_env* e) {
+  const DevCam& c = e->k.cam;
+  return (!e->tune.short_edges && tc_short_edges_skip(c.thickness, c.W, c.H)) ? 1 : 2;
+}
+static_assert(R_OFF_BITS_SH(32, 1) == 32 * 116 + 64 * 24 && R_OFF_TAB == 0 && TC_LDS_STEP == 1280 && TC_SEG_ENTRY_BYTES == 20,
+              "plan_frame_lds spells the raster tables out in plain arithmetic");
+
+// The LDS of the frame kernels' launches.  The K = 5 kernel with batches of 32 -- compiled for five waves, with the one-word list
+// entries and the form-sized raster tables (TC_FRAME_LEAN, k_frame.h) -- gets a plan of its own (plan_frame_lds), never larger
+// than what grow_lds_for_draw_lists gave (cfg3: 8960 bytes instead of 10240, 18 workgroups per CU instead of 16).  Every
+// other frame kernel is the code it was and keeps the layout it shares with the other kernels.
+static void plan_frame(tc_env* e) {
+  const DevMap& m = e->k.m;
+  const DevCam& dc = e->k.cam;
+  const LdsLayout& L = e->k.lds;
+  const int kf = frame_k_of(e->kframe), rb = frame_rb_of(e->kframe);
+  FrameLds f;
+  if (TC_FRAME_LEAN(kf, rb)) {
+    bool windowed = false;  // a camera group larger than the register cache (cam_body's `one` is false; never at K = 5 today)
+    for (int g = 0; g < e->k.n_grp; g++)
+      windowed = windowed || e->k.grp_n0[g + 1] - e->k.grp_n0[g] > kf * TC_NT || e->k.grp_e0[g + 1] - e->k.grp_e0[g] > kf * TC_NT;
+    int reserve = 0;
+#ifdef TC_TIMING_LDS
+    reserve = 256;  // the stamp buffer (static LDS) comes out of the draw-list head: same workgroups per CU
+#endif
+    f = plan_frame_lds(e->plan_cap_n, e->plan_cap_e, m.total_nodes, windowed, rb, outline_shift(e), dc.band_rows * m.C * dc.wpr * 4,
+                       TC_LIVE_BYTES, e->tune.seg_lds != 0, e->tune.seg_lds_limit, e->shared_frame_lds, reserve);
+  } else {
+    f.off_p = L.off_p, f.off_flg = L.off_flg, f.off_list = L.off_list, f.off_cnt = L.off_cnt;
+    f.cam_total = L.off_cnt + 64;
+    f.list_bytes = L.off_cnt - L.off_list;
+    f.counters = true;
+    // (where this frame kernel puts its bit-planes: behind full-size tables of its own batch size, which for a handle whose
+    // fused kernels run larger batches is below the r_off_bits_k the shared layout was sized with)
+    f.r_off_tab = R_OFF_TAB, f.r_off_bits = R_OFF_BITS_OF(rb);
+    f.r_total = f.r_off_bits + align_up(dc.band_rows * m.C * dc.wpr * 4, 16);
+    f.head_off = e->seg_lds_off;
+    f.head_cap = e->shared_seg_cap;
+    f.total = e->shared_frame_lds;
+  }
+  e->fl = f;
+  e->frame_lds = f.total;
+  e->frame_seg_cap = f.head_cap;
+#ifdef TC_ABLATE
+  if (e->tune.print_lds)
+    fprintf(stderr, "tc_env_create: frame plan: camera %d raster %d (bits at %d) head at %d, %d entries, total %d (shared layout: %d)\n",
+            e->fl.cam_total, e->fl.r_total, e->fl.r_off_bits, e->fl.head_off, e->fl.head_cap, e->fl.total, e->shared_frame_lds);
+#endif
+#ifdef TC_EXPERIMENT
+  // occupancy experiments (make dev-exp, never shipped): unused LDS bytes per frame workgroup -> fewer workgroups per CU
+  e->frame_lds += e->tune.lds_pad;
+#endif
 }
 
 // tc_frame_kernel keeps no env state in LDS, so the bytes behind both stages' buffers -- the LiveLds slot and whatever
@@ -892,10 +964,11 @@ static void grow_lds_for_draw_lists(tc_env* e) {
     fprintf(stderr, "tc_env_create: lds.total %d off_live %d frame_lds %d seg_lds_cap %d r_lds %d band_rows %d n_bands %d\n", (int)L.total,
             (int)L.off_live, e->frame_lds, e->seg_lds_cap, e->r_lds, e->k.cam.band_rows, e->k.cam.n_bands);
 #endif
+  e->shared_frame_lds = e->frame_lds;
+  e->shared_seg_cap = e->frame_seg_cap;
+  plan_frame(e);
 #ifdef TC_EXPERIMENT
-  // occupancy experiments (make dev-exp, never shipped): unused LDS bytes per frame workgroup -> fewer workgroups per CU
-  e->frame_lds += e->tune.lds_pad;
-  e->step_lds += e->tune.step_lds_pad;
+  e->step_lds += e->tune.step_lds_pad;  // (occupancy experiments: see plan_frame)
 #endif
 }
 
@@ -1628,6 +1701,7 @@ extern "C" int tc_env_set_camera(tc_env* e, const tc_camera_params* cam) {
   e->k.cam.band_rows = band_rows;
   e->k.cam.n_bands = n_bands;
   if (rc == TC_OK) cover_cull(e);  // (the cover travels by value with the launch arguments: no table to replace, no wait)
+  if (rc == TC_OK) plan_frame(e);  // (a new thickness may change the outline form, and with it the raster tables' size)
   return rc;
 }
 
@@ -1670,7 +1744,7 @@ static RArgs make_rargs(tc_env* e, const int* seg_g, const int* seg_n, int seg_c
   r.off_tab = e->r_off_tab;
   r.off_bits = e->r_off_bits;
   r.flags = flags & ~R_F_LONG_EDGES;
-  if (!e->tune.short_edges && tc_short_edges_skip(c.thickness, c.W, c.H)) r.flags |= R_F_LONG_EDGES;
+  if (outline_shift(e) == 1) r.flags |= R_F_LONG_EDGES;
   r.seg_row0 = 0;
   r.noise_row0 = 0;
   r.obs_row_stride = 0;
@@ -1891,8 +1965,17 @@ static FrameArgs frame_args_of(const tc_env* e, uint32_t flags, const RArgs& r, 
   fa.a.seg_n = s.seg_n;
   fa.r = r;
   fa.pose_rows = s.pose;
-  fa.a.seg_lds_off = fa.r.seg_lds_off = e->seg_lds_off;
-  fa.a.seg_lds_cap = fa.r.seg_lds_cap = e->frame_seg_cap;
+  // the frame kernels' own LDS plan: camera regions, raster tables of the handle's outline form, the draw-list head
+  fa.a.lds.off_p = e->fl.off_p;
+  fa.a.lds.off_flg = e->fl.off_flg;
+  fa.a.lds.off_list = e->fl.off_list;
+  fa.a.lds.off_cnt = e->fl.off_cnt;
+  fa.a.lds.total = e->fl.total;
+  fa.a.lds.off_live = e->fl.head_off;
+  fa.r.off_tab = e->fl.r_off_tab;
+  fa.r.off_bits = e->fl.r_off_bits;
+  fa.a.seg_lds_off = fa.r.seg_lds_off = e->fl.head_off;
+  fa.a.seg_lds_cap = fa.r.seg_lds_cap = e->fl.head_cap;
   if (streamed) {
     fa.abort_word = e->st_words + 1;
     fa.resident = e->st_words;
@@ -2324,6 +2407,25 @@ extern "C" int tc_env_launch_info(const tc_env* e, uint32_t flags, int32_t n_ste
              : p.frames  ? (drive ? "tc_drive_env_kernel+tc_frame_kernel" : "tc_env_kernel+tc_frame_kernel")
              : p.do_raster ? (drive ? "tc_drive_env_kernel+tc_raster_kernel" : "tc_env_kernel+tc_raster_kernel")
                            : (drive ? "tc_drive_env_kernel" : "tc_env_kernel"));
+  return TC_OK;
+}
+
+extern "C" int tc_env_frame_lds_info(const tc_env* e, int32_t* lds_bytes, int32_t* head_entries, int32_t* workgroups_per_cu,
+                                     int32_t* bits_offset) {
+  if (!e) return TC_E_INVALID;
+  if (lds_bytes) *lds_bytes = e->frame_lds;
+  if (head_entries) *head_entries = e->fl.head_cap;
+  if (bits_offset) *bits_offset = e->fl.r_off_bits;
+  if (workgroups_per_cu) {
+    *workgroups_per_cu = 0;
+    if (e->kvar != 13) {  // (K = 13 handles have no frame kernel: plan_call)
+      const DevCam& c = e->k.cam;
+      int n = 0;
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)frame_kernel_of(e->kframe, c.thickness > 1, c.format, false), TC_NT,
+                                                           (size_t)e->frame_lds));
+      *workgroups_per_cu = n;
+    }
+  }
   return TC_OK;
 }
 

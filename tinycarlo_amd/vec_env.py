@@ -1218,6 +1218,15 @@ class TinyCarloVecEnv(gym.Env):
                                                name, 64), "tc_env_launch_info")
         return {"fused": bool(f.value), "kvar": kv.value, "kernel": name.value.decode(), "steps_per_dispatch": spd.value}
 
+    def frame_lds_info(self) -> Dict[str, int]:
+        """The LDS plan of the handle's frame kernel (tc_env_frame_lds_info): bytes per workgroup, draw-list entries its
+        LDS head holds, workgroups per CU as the runtime computes them, offset of the raster bit-planes.  No launch."""
+        b, h, w, o = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().tc_env_frame_lds_info(self._h, C.byref(b), C.byref(h), C.byref(w), C.byref(o)),
+                      "tc_env_frame_lds_info")
+        return {"lds_bytes": b.value, "head_entries": h.value, "workgroups_per_cu": w.value, "bits_offset": o.value}
+
     def draw_list_stats(self) -> Dict[str, Any]:
         """What the most recent frames drew (tc_env_draw_list_stats; waits for the device): workload descriptor."""
         m, e, mx, fr = C.c_double(), C.c_double(), C.c_int32(), C.c_int64()
