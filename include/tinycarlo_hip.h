@@ -576,6 +576,12 @@ int tc_env_launch_info(const tc_env* env, uint32_t flags, int32_t n_steps, int32
 int tc_env_frame_lds_info(const tc_env* env, int32_t* lds_bytes, int32_t* head_entries, int32_t* workgroups_per_cu,
                           int32_t* bits_offset);
 
+/* The raster bands of the handle's frames: a frame whose bit-planes do not fit the LDS budget of one band (TC_BAND_BYTES) is
+ * rasterised in n_bands bands of band_rows rows (the last one shorter).  n_bands == 1 is every bundled config at the
+ * benchmark resolutions up to 128 x 128; the K = 5 frame kernel with batches of 32 then runs its one-band form, and
+ * tc_frame_banded otherwise.  Either pointer may be NULL. */
+int tc_env_frame_bands(const tc_env* env, int32_t* n_bands, int32_t* band_rows);
+
 /* Workload descriptor for benchmark lines -- what the most recent frames drew: mean / max length of the frames' draw
  * lists (segments handed to cv2.polylines, camera.py:95-106) and the fraction of frames with none, over the N frames of
  * the last tc_step or, of the last tc_step_multi call, the frames of its last (up to 48) steps.  Waits for the device. */

@@ -157,6 +157,22 @@ __device__ inline int2 cam_project(const double* K, double X, double Y, double Z
   return make_int2(d_np_int32(u), d_np_int32(v));
 }
 
+// The nine entries of a frame's K matrix (camera.py:48-50) as wave-uniform values in scalar registers: the shared camera's in
+// scalar loads from the kernel-argument segment, or row cam_row of the camera rows -- vector loads made uniform: the row is the
+// same for the whole wavefront, but the rows are device memory that tc_env_set_camera_per_env / tc_env_set_camera_bank rewrite
+// between calls, and nothing shows that no such copy is ever in flight beside a frame launch, which a read through the
+// scalar cache would need.  Called with the argument block passed through kernarg_again(), so the loads stay at the call.
+__device__ __forceinline__ void cam_load_K(const KArgs& a, const int cam_row, double* Kc) {
+  if (a.cam_K) {  // (a branch, not a select of pointers: the shared camera's K then comes in scalar loads)
+#pragma unroll
+    for (int i = 0; i < 9; i++) Kc[i] = uni_d(a.cam_K[(size_t)cam_row * 9 + i]);  // (the row that came with the pose, not the env's latest)
+  } else {
+    const __attribute__((address_space(4))) double* kk = (const __attribute__((address_space(4))) double*)(unsigned long long)a.cam.K;
+#pragma unroll
+    for (int i = 0; i < 9; i++) Kc[i] = kk[i];  // (explicitly the kernarg segment: cannot be merged with the other branch)
+  }
+}
+
 // Phase C of one camera group whose nodes and edges sit in the wavefront's registers (one window: every bundled map).
 // camera.py:52-110 reads the whole node / edge arrays in each of its steps; here the flags of an edge's two ends are
 // carried in a register per edge slot (`ff`) and refreshed only after a pass that moved something, so a fix-up pass in
@@ -172,7 +188,7 @@ __device__ inline int2 cam_project(const double* K, double X, double Y, double Z
 // register count is what it was.
 template <int K, bool PACKED = false>
 __device__ __forceinline__ void cam_group_regs(const KArgs& a, const MapCache<K>& mc, const double* pose, const double* Kc,
-                                               const int l0, const int l1, const int ge0, const int nn, const int ne,
+                                               const int cam_row, const int l0, const int l1, const int ge0, const int nn, const int ne,
                                                double* Px, double* Py, double* Pz, unsigned char* flg, int* list,
                                                int* segg, LdsIntPtr seg_lds, int& nseg, unsigned int& my_layers, const int env,
                                                const int tid) {
@@ -344,10 +360,13 @@ __device__ __forceinline__ void cam_group_regs(const KArgs& a, const MapCache<K>
     ncand += __popcll(mk);
   }
   lds_sync();
+  double Kl[9];  // PACKED: the camera's K matrix, fetched here, where it is used, and not held across the clip passes (see cam_body)
+  if constexpr (PACKED) cam_load_K(kernarg_again(a), cam_row, Kl);
+  const double* Kp = PACKED ? Kl : Kc;
   for (int k = tid; k < ncand; k += TC_NT) {  // camera.py:133-142, 90
     const int i = PACKED ? (int)cand_list[k] : list[k];
     double u, v;
-    int2 q = cam_project(Kc, Px[i], Py[i], Pz[i], u, v);
+    int2 q = cam_project(Kp, Px[i], Py[i], Pz[i], u, v);
     const bool vis = (u > 0) && (u < cam.W) && (v > 0) && (v < cam.H) && (flg[i] & 3) == 3;
     ((int2*)Px)[i] = q;  // renderer.py:43,50 np.int32(...)
     if (vis) flg[i] |= 4;
@@ -593,13 +612,17 @@ __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, in
   int* list = (int*)(smem + a.lds.off_list);
   int* cnt = (int*)(smem + a.lds.off_cnt);
   const DevCam& cam = a.cam;
-  // (LEAN: wave-uniform like the pose, and kept in scalar registers like it: as vector values the nine entries are 18
-  // VGPRs held from here across the clip passes to the projection -- the registers the frame kernel's five-wave bound
-  // lacks.  The kernels that simulate in the same wavefront sit at their SGPR limit already and keep the vector form.)
+  // (LEAN: wave-uniform like the pose, and in scalar registers like it: as vector values the nine entries are 18 VGPRs held
+  // from here across the clip passes to the projection -- the registers the frame kernel's five-wave bound lacks -- and as
+  // scalar values fetched here they were 18 SGPRs spilled to vector lanes across the same span.  So that form fetches them
+  // at the projection: cam_load_K.  The kernels that simulate in the same wavefront sit at their SGPR limit already and keep
+  // the vector form, fetched here.)
   double Kc[9];
-  if (a.cam_K) {  // (a branch, not a select of pointers: the shared camera's K then comes in scalar loads)
+  if constexpr (LEAN) {
+    // (fetched where the projection needs them: in cam_group_regs, and below for a windowed group)
+  } else if (a.cam_K) {  // (a branch, not a select of pointers: the shared camera's K then comes in scalar loads)
 #pragma unroll
-    for (int i = 0; i < 9; i++) Kc[i] = LEAN ? uni_d(a.cam_K[(size_t)cam_row * 9 + i]) : a.cam_K[(size_t)cam_row * 9 + i];  // (the row that came with the pose, not the env's latest)
+    for (int i = 0; i < 9; i++) Kc[i] = a.cam_K[(size_t)cam_row * 9 + i];  // (the row that came with the pose, not the env's latest)
   } else {
     const __attribute__((address_space(4))) double* kk = (const __attribute__((address_space(4))) double*)(unsigned long long)cam.K;
 #pragma unroll
@@ -632,7 +655,7 @@ __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, in
       }
     }
     if (one) {
-      cam_group_regs<K, LEAN>(a, mc, pose, Kc, l0, l1, ge0, nn, ne, Px, Py, Pz, flg, list, segg, (LdsIntPtr)(smem + a.seg_lds_off), nseg,
+      cam_group_regs<K, LEAN>(a, mc, pose, Kc, cam_row, l0, l1, ge0, nn, ne, Px, Py, Pz, flg, list, segg, (LdsIntPtr)(smem + a.seg_lds_off), nseg,
                         my_layers, env, tid);
       continue;
     }
@@ -698,6 +721,7 @@ __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, in
       if (flg[i] & 16) list[atomicAdd(cnt + 4, 1)] = i;
     __syncthreads();
     const int ncand = cnt[4];
+    if constexpr (LEAN) cam_load_K(kernarg_again(a), cam_row, Kc);
     for (int k = tid; k < ncand; k += TC_NT) {  // camera.py:133-142, 90
       const int i = list[k];
       double u, v;

@@ -2,7 +2,8 @@
 // renderer.py:36-51):
 //   tc_frame_kernel<K, THICK, FMT, RBT>    camera + raster of one (step, env) frame per workgroup, from the pose row the
 //                                          simulate launch left (FrameArgs, frame_args(), frame_pose, frame_one);
-//                                          tc_frame_recover_kernel draws what a gated workgroup of a streamed call gave up on
+//                                          tc_frame_recover_kernel draws what a gated workgroup of a streamed call gave up on;
+//                                          tc_frame_banded is the K = 5 / batches-of-32 kernel for frames of several bands
 //   tc_step_kernel<K, THICK, FMT, RBT, FEAT>  simulate + camera + raster of an env in one launch (step_kernel_body over
 //                                          StepArgs of k_env.h); tc_drive_step_kernel is the TC_FEAT_CTRL entry point
 // Includes k_camera.h, k_raster.h, k_sim.h and k_env.h.
@@ -120,7 +121,8 @@ __device__ __forceinline__ bool frame_pose(const size_t slot0, const int env, co
 #define TC_FRAME_LEAN(K, RBT) ((K) <= 5 && (RBT) == 32)
 // One frame: `rowy` is the frame's row in the launch (its step), `env` its env.
 // HOT (tc_frame_kernel): the raster stage in its LDS-only form (see raster_body); !HOT (the recover kernel): the generic form.
-template <int K, bool THICK, int FMT, bool HOT, int RBT>
+// ONE_BAND: the handle's frames are one raster band (raster_body's form without the band loop).
+template <int K, bool THICK, int FMT, bool HOT, int RBT, bool ONE_BAND = false>
 __device__ __forceinline__ void frame_one(unsigned char* smem, const int env, const int rowy) {
   const int tid = threadIdx.x;
   int nseg;
@@ -153,7 +155,7 @@ __device__ __forceinline__ void frame_one(unsigned char* smem, const int env, co
   } else {
     lds_sync();
   }
-  raster_body<THICK, FMT, HOT, RBT, TC_FRAME_LEAN(K, RBT)>(fr.r, smem, env, fr.r.obs + (size_t)rowy * fr.r.obs_row_stride, tid, slot0, nseg, used,
+  raster_body<THICK, FMT, HOT, RBT, TC_FRAME_LEAN(K, RBT), ONE_BAND>(fr.r, smem, env, fr.r.obs + (size_t)rowy * fr.r.obs_row_stride, tid, slot0, nseg, used,
                                            fr.r.noise_row0 + rowy);
   {
     const FrameArgs& fe = frame_args();
@@ -177,7 +179,26 @@ __global__ __launch_bounds__(TC_NT, TC_FRAME_WAVES(K, RBT)) void tc_frame_kernel
   if ((int)blockIdx.x >= fa.a.N) return;
   const int env = fa.order ? uni_i(((const __attribute__((address_space(4))) int*)(unsigned long long)fa.order)[blockIdx.x])
                            : fa.a.env0 + (int)blockIdx.x;
-  frame_one<K, THICK, FMT, true, RBT>(smem, env, (int)blockIdx.y);
+  // (the five-wave kernel draws one-band frames only: frame_kernel_of sends a banded handle to tc_frame_banded)
+  frame_one<K, THICK, FMT, true, RBT, TC_FRAME_LEAN(K, RBT)>(smem, env, (int)blockIdx.y);
+}
+
+// The five-wave kernel for a handle whose frames are taller than one raster band (RCam::n_bands > 1; no benchmark config: a small
+// map at a large resolution): the same stages with the band loop.  tc_frame_kernel<5, .., 32> itself is the one-band form,
+// straight-line code -- the loop's invariants, set up in front of a loop that runs once, were 68 of its spilled scalar
+// registers ("Scalar spills, round 17").  Exists for TC_FRAME_LEAN (K, RBT) only: every other frame kernel
+// has the band loop in tc_frame_kernel, as it always had.  (Named without "_kernel": the kernel-variant matrix of the tests keeps
+// a ledger of the tc_*_kernel symbols by family; this one stands beside that matrix and has its cases in
+// tests/test_gpu_frame_scalars.py, one per instantiation.)
+template <int K, bool THICK, int FMT, int RBT = RB_OF_K(K)>
+__global__ __launch_bounds__(TC_NT, TC_FRAME_WAVES(K, RBT)) void tc_frame_banded(FrameArgs fa_unused) {
+  static_assert(TC_FRAME_LEAN(K, RBT), "only the five-wave kernel has a one-band form to stand beside");
+  extern __shared__ __align__(16) unsigned char smem[];
+  const FrameArgs& fa = frame_args();
+  if ((int)blockIdx.x >= fa.a.N) return;
+  const int env = fa.order ? uni_i(((const __attribute__((address_space(4))) int*)(unsigned long long)fa.order)[blockIdx.x])
+                           : fa.a.env0 + (int)blockIdx.x;
+  frame_one<K, THICK, FMT, true, RBT, false>(smem, env, (int)blockIdx.y);
 }
 
 // The pass behind a streamed call's simulate launch: one workgroup per env looks through the call's rows for frames a

@@ -107,12 +107,15 @@ __device__ __forceinline__ void packed_copy_words(unsigned char* dst, const unsi
 // FORM (the five-wave frame kernel, whose LDS plan is sized for it: plan_frame_lds): the outline tables hold the RB << sh items
 // of the handle's outline form -- sh = 2, the four edges of FillConvexPoly's quad, or 1, the two long ones (R_F_LONG_EDGES) --
 // and the bit-planes follow at RArgs::off_bits.  Otherwise the tables have their full size at compile-time offsets.
-template <bool THICK, int FMT, bool LDSONLY = false, int RB = RB_MAX, bool FORM = false>
+// ONE_BAND: the frame is known to be a single band (RCam::n_bands == 1, the caller's promise) -- the stage is then straight-line
+// code: no band loop, whose invariants the compiler would otherwise set up -- and spill -- in front of a loop that runs once.
+template <bool THICK, int FMT, bool LDSONLY = false, int RB = RB_MAX, bool FORM = false, bool ONE_BAND = false>
 __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem, int env, unsigned char* obs_base,
                                             const int tid, const size_t seg_slot0, const int nseg_in,
                                             const unsigned int used_in, const int frame_row) {
   const RArgs& a = a0;
   const RCam& cam = a.cam;
+  auto n_bands_of = [](const RCam& c) { return ONE_BAND ? 1 : c.n_bands; };  // (a constant under ONE_BAND: every test on it folds)
   // (FORM: behind tables sized by the outline form, where the host's plan says: R_OFF_BITS_SH(RB, sh))
   unsigned int* bits = (unsigned int*)(smem + (FORM ? a.off_bits : R_OFF_BITS_OF(RB)));
   const int* segg = a.seg_g + (seg_slot0 + env) * a.seg_cap * 5;
@@ -161,7 +164,7 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
     for (int off = 32; off > 0; off >>= 1) used_layers |= __shfl_xor(used_layers, off);
   }
 
-  const int H = cam.H, W = cam.W, wpr = cam.wpr, C = a.C;
+  int H = cam.H, W = cam.W, wpr = cam.wpr, C = a.C;  // (not const: the banded FORM kernel fetches them again per band)
   constexpr bool CLS = TC_FMT_IS_CLASSES(FMT), BITS = FMT == TC_FMT_CLASSES_BITS;
   unsigned char* out = obs_base + (size_t)env * tc_obs_bytes_of(FMT, C, H, W);
   // Every kernel but FORM ones: lt and lc in front, with room for RB * 4 items, then the tables of fixed size -- all at
@@ -184,7 +187,7 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
   // is 15 % of the kernel's time for 9 % of its instructions).  A frame with no segment at all (37-57 % of the
   // benchmark's frames once cars have wandered off the road) is done here: no planes to clear, no tables, no expansion.
   unsigned int early_zero = 0;
-  if (CLS && cam.n_bands == 1 && (W & 15) == 0 && a.noise_blobs == 0 && !DBG_ON(a.flags, DBG_SKIP_STORE)) {
+  if (CLS && n_bands_of(cam) == 1 && (W & 15) == 0 && a.noise_blobs == 0 && !DBG_ON(a.flags, DBG_SKIP_STORE)) {
     const int per_plane = H * (W >> 4);
     const uint4 zero4 = make_uint4(0, 0, 0, 0);
     for (int c = 0; c < C; c++) {
@@ -207,12 +210,18 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
       return;
     }
   }
-  for (int band = 0; band < cam.n_bands; band++) {
+  for (int band = 0; band < n_bands_of(cam); band++) {
+    // (FORM with a band loop -- tc_frame_banded: every band fetches the arguments it needs again; as loop invariants
+    // they were fetched in front of the loop and spilled across it)
+    if constexpr (FORM && !ONE_BAND) {
+      const RArgs& ab = kernarg_again(a0);
+      H = ab.cam.H, W = ab.cam.W, wpr = ab.cam.wpr, C = ab.C;
+    }
     const int y0 = band * cam.band_rows;
     const int y1 = (y0 + cam.band_rows < H) ? y0 + cam.band_rows : H;
     const int rows = y1 - y0;
     const int nwords = C * cam.band_rows * wpr;
-    if (cam.n_bands > 1 && (W & 15) == 0) {
+    if (n_bands_of(cam) > 1 && (W & 15) == 0) {
       // A frame taller than one LDS band (cfg5: 480 x 640 in 19 bands): most bands see no lane line at all.  Such a band
       // is all zeros whatever the format (and whatever the noise blobs copy or erase), so it is written as a plain
       // stream of 16-byte zero stores: no bit-planes to clear, nothing to scan, and no wait for the zeros to land before
@@ -290,7 +299,7 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
 #ifdef TC_TIMING_LDS
         if (cam.n_bands >= 0) TSTAMP(27);  // first value of the re-read argument block has arrived
 #endif
-        if (cam.n_bands > 1) {
+        if (n_bands_of(cam) > 1) {
           // Frames taller than one LDS band run this loop once per band (cfg5: 19 bands).  A batch none of whose
           // segments can reach the band's rows is skipped whole -- set-up, prefix sums, pixel loops: most bands of a
           // 480 x 640 frame see no lane line at all and are then a pure zero-store stream.
@@ -320,7 +329,7 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
             // (thickness + 1) / 2), and `thickness + 2` rows are allowed here.  On cfg5 (12 bands) a segment survives
             // this in 1-3 bands instead of 12.
             bool touch = true;
-            if (cam.n_bands > 1) {
+            if (n_bands_of(cam) > 1) {
               const long long ya = sg[2], yb = sg[4], mg = (long long)cam.thickness + 2;
               const long long ymin = (ya < yb ? ya : yb) - mg, ymax = (ya < yb ? yb : ya) + mg;
               touch = ymax >= y0 && ymin < y1;
@@ -456,7 +465,7 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
           const SegV sg = seg_get(k);
           r.bits = bits + sg[0] * plane;
           const int cx = (t & 1) ? sg[3] : sg[1], cy = (t & 1) ? sg[4] : sg[2];
-          if (cam.n_bands > 1 && ((long long)cy + cam.cap_r < y0 || (long long)cy - cam.cap_r >= y1)) continue;  // cap outside the band
+          if (n_bands_of(cam) > 1 && ((long long)cy + cam.cap_r < y0 || (long long)cy - cam.cap_r >= y1)) continue;  // cap outside the band
           if (cam.cap_r < 32)
             r_cap(r, cx, cy, cam.cap_r, cam.cap_hw, cam.cap_hw4);
           else
@@ -536,7 +545,7 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
     TSTAMP(12);
     const RArgs& a = kernarg_again(a0);
     const RCam& cam = a.cam;
-    if (cam.n_bands > 1) TC_BAND_THROTTLE();
+    if (n_bands_of(cam) > 1) TC_BAND_THROTTLE();
     if (DBG_ON(a.flags, DBG_SKIP_STORE)) {
     } else if (BITS) {
       // packed class masks: the store phase is a copy of the band's rows, plane by plane (planes of layers without a

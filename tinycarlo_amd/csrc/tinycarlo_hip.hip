@@ -86,6 +86,8 @@
 #define TC_INST_PFRAME(D, K, RB) TC_INST_PFRAME2(D, K, RB, true) TC_INST_PFRAME2(D, K, RB, false)
 #define TC_INST_PART2(D)                                                                                                  \
   TC_INST_PFRAME(D, 5, 16) TC_INST_PFRAME(D, 5, RB_OF_K(5)) TC_INST_PFRAME(D, 8, RB_OF_K(8)) TC_INST_PFRAME(D, 9, RB_OF_K(9)) \
+  D __global__ void tc_frame_banded<5, true, TC_FMT_CLASSES_BITS, RB_OF_K(5)>(FrameArgs);                            \
+  D __global__ void tc_frame_banded<5, false, TC_FMT_CLASSES_BITS, RB_OF_K(5)>(FrameArgs);                           \
   D __global__ void tc_raster_kernel<true, TC_FMT_CLASSES_BITS>(RArgs);                                                     \
   D __global__ void tc_raster_kernel<false, TC_FMT_CLASSES_BITS>(RArgs);
 #define TC_INST_UNPACK(D)                                                                                                          \
@@ -194,13 +196,17 @@ static step_kern_t envg_kernel_of(unsigned feat) {
   return lift([](auto ft) -> step_kern_t { return tc_envg_kernel<ft>; }, Feats{feat});
 }
 // recover: tc_frame_recover_kernel, the pass behind a streamed call's frame launch
-static frame_kern_t frame_kernel_of(int kcode, bool thick, int fmt, bool recover) {
+// banded: the handle's frames are taller than one raster band (DevCam::n_bands > 1).  The five-wave kernel (TC_FRAME_LEAN) is
+// the one-band form and has tc_frame_banded beside it; every other frame kernel, and every recover kernel, has the band loop
+static frame_kern_t frame_kernel_of(int kcode, bool thick, int fmt, bool recover, bool banded) {
   return lift(
-      [](auto kc, auto t, auto f, auto rec) -> frame_kern_t {
-        if constexpr (rec) return tc_frame_recover_kernel<FrameKRb<kc>::K, t, f, FrameKRb<kc>::RB>;
-        else return tc_frame_kernel<FrameKRb<kc>::K, t, f, FrameKRb<kc>::RB>;
+      [](auto kc, auto t, auto f, auto rec, auto bd) -> frame_kern_t {
+        constexpr int K = FrameKRb<kc>::K, RB = FrameKRb<kc>::RB;
+        if constexpr (rec) return tc_frame_recover_kernel<K, t, f, RB>;
+        else if constexpr (bd && TC_FRAME_LEAN(K, RB)) return tc_frame_banded<K, t, f, RB>;
+        else return tc_frame_kernel<K, t, f, RB>;
       },
-      Kcodes{kcode}, Thicks{thick}, FrameFmts{fmt}, Bools{recover});
+      Kcodes{kcode}, Thicks{thick}, FrameFmts{fmt}, Bools{recover}, Bools{banded});
 }
 // K and batch size of the kernel frame_kernel_of picks for a code: what the host plans that kernel's LDS from
 static int frame_k_of(int kcode) {
@@ -993,7 +999,8 @@ static int raise_lds_limits(const tc_env* e) {
         for (int fmt : {TC_FMT_CLASSES, TC_FMT_CLASSES_BITS, TC_FMT_RGB}) {
           for (unsigned feat = 0; feat <= (TC_FEAT_CTRL | TC_FEAT_ALL) && fmt != TC_FMT_CLASSES_BITS; feat++)
             raise((const void*)step_kernel_of(kcode, t, fmt, feat), lds, (feat & TC_FEAT_CTRL) ? "tc_drive_step_kernel" : "tc_step_kernel");
-          raise((const void*)frame_kernel_of(kcode, t, fmt, false), lds, "tc_frame_kernel");
+          for (int banded = 0; banded < 2; banded++)  // (the same kernel twice where there is no banded one)
+            raise((const void*)frame_kernel_of(kcode, t, fmt, false, banded), lds, "tc_frame_kernel");
         }
   // tc_envg_kernel's LDS copies of the map (edge records + fat lanepath nodes, see launch_envg()) can exceed the 48 KB default
   const size_t envg_lds = ((size_t)m.total_edges * 48 + 15) / 16 * 16 + (size_t)m.lpN * sizeof(LpNode);
@@ -2071,13 +2078,13 @@ static int launch_streamed(tc_env* e, const Call& c) {
     HIP_TRY(hipGetLastError());
     if (c.prof && si == 0) HIP_TRY(hipEventRecord(e->ev[3][c.slot], fs));
     fa.gate = 1;
-    hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, false), dim3(N, cn), dim3(TC_NT), e->frame_lds, fs, fa);
+    hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, false, fa.r.cam.n_bands > 1), dim3(N, cn), dim3(TC_NT), e->frame_lds, fs, fa);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamWaitEvent(fs, e->sim_ev, 0));
     fa.gate = 2;
     fa.recover_rows = cn;
     fa.order = nullptr;
-    hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, true), dim3(N), dim3(TC_NT), e->frame_lds, fs, fa);
+    hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, true, fa.r.cam.n_bands > 1), dim3(N), dim3(TC_NT), e->frame_lds, fs, fa);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->slot_ev[0], fs));
     if (e->frame_order[0]) e->cost_row[0] = e->streamed.seg_n + (size_t)(cn - 1) * N;
@@ -2172,7 +2179,7 @@ static int launch_chunked(tc_env* e, const Call& c) {
       // two streams, re-sort only once per call and otherwise keep the stream's last order)
       int rc = frame_order_of(e, fsi, fs, rows >= 8 || ci < 2, &fa.order);
       if (rc != TC_OK) return rc;
-      hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, false), dim3(N, rows), dim3(TC_NT), e->frame_lds, fs, fa);
+      hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, false, fa.r.cam.n_bands > 1), dim3(N, rows), dim3(TC_NT), e->frame_lds, fs, fa);
       if (e->frame_order[fsi]) e->cost_row[fsi] = e->ring.seg_n + ((size_t)r.seg_row0 + (size_t)rows - 1) * N;
     } else {
       hipLaunchKernelGGL(raster_kernel_of(c.thick, c.fmt), dim3(N, rows), dim3(TC_NT), e->r_lds, fs, r);
@@ -2421,11 +2428,18 @@ extern "C" int tc_env_frame_lds_info(const tc_env* e, int32_t* lds_bytes, int32_
     if (e->kvar != 13) {  // (K = 13 handles have no frame kernel: plan_call)
       const DevCam& c = e->k.cam;
       int n = 0;
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)frame_kernel_of(e->kframe, c.thickness > 1, c.format, false), TC_NT,
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)frame_kernel_of(e->kframe, c.thickness > 1, c.format, false, c.n_bands > 1), TC_NT,
                                                            (size_t)e->frame_lds));
       *workgroups_per_cu = n;
     }
   }
+  return TC_OK;
+}
+
+extern "C" int tc_env_frame_bands(const tc_env* e, int32_t* n_bands, int32_t* band_rows) {
+  if (!e) return TC_E_INVALID;
+  if (n_bands) *n_bands = e->k.cam.n_bands;
+  if (band_rows) *band_rows = e->k.cam.band_rows;
   return TC_OK;
 }
 

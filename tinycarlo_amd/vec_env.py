@@ -1220,12 +1220,16 @@ class TinyCarloVecEnv(gym.Env):
 
     def frame_lds_info(self) -> Dict[str, int]:
         """The LDS plan of the handle's frame kernel (tc_env_frame_lds_info): bytes per workgroup, draw-list entries its
-        LDS head holds, workgroups per CU as the runtime computes them, offset of the raster bit-planes.  No launch."""
+        LDS head holds, workgroups per CU as the runtime computes them, offset of the raster bit-planes; and the raster
+        bands of a frame (tc_env_frame_bands): their number and rows.  No launch."""
         b, h, w, o = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        nb, br = C.c_int32(), C.c_int32()
         with torch.cuda.device(self.device):
             nat.check(nat.lib().tc_env_frame_lds_info(self._h, C.byref(b), C.byref(h), C.byref(w), C.byref(o)),
                       "tc_env_frame_lds_info")
-        return {"lds_bytes": b.value, "head_entries": h.value, "workgroups_per_cu": w.value, "bits_offset": o.value}
+            nat.check(nat.lib().tc_env_frame_bands(self._h, C.byref(nb), C.byref(br)), "tc_env_frame_bands")
+        return {"lds_bytes": b.value, "head_entries": h.value, "workgroups_per_cu": w.value, "bits_offset": o.value,
+                "bands": nb.value, "band_rows": br.value}
 
     def draw_list_stats(self) -> Dict[str, Any]:
         """What the most recent frames drew (tc_env_draw_list_stats; waits for the device): workload descriptor."""
