@@ -3,8 +3,8 @@
 // phase B shares, the fix-up passes (cam_move_to_plane, cam_chain_replay, cam_group_regs for a group held in registers,
 // cam_fixup_pass for windowed groups; rules of the merged passes: tc_clip.h), cam_project (camera.py:133-142), what a
 // frame needs of an env (FramePose, the pose row and its markers, cam_pose12 = camera.py:62), the whole-frame cull
-// (cam_cull, tc_cull.h) and the stage itself, cam_body.  Defines no kernel: tc_env_kernel<.., CAM = true> (k_env.h),
-// tc_frame_kernel and tc_step_kernel (k_frame.h) run it.  Includes k_common.h and the plain-arithmetic tc_clip.h,
+// (cam_cull, and cam_cull_row for the pose-row writers of the simulate kernels; tc_cull.h) and the stage itself,
+// cam_body.  Defines no kernel: tc_env_kernel<.., CAM = true> (k_env.h), tc_frame_kernel and tc_step_kernel (k_frame.h) run it.  Includes k_common.h and the plain-arithmetic tc_clip.h,
 // tc_cull.h, tc_device.h.
 #ifndef K_CAMERA_H
 #define K_CAMERA_H
@@ -501,6 +501,10 @@ struct FramePose {
 // "not written yet" in a pose row of a streamed call (a NaN no arithmetic produces: all ones); and the marker a frame
 // workgroup that gave up waiting leaves in place of its draw-list length
 #define TC_POSE_EMPTY 0xFFFFFFFFFFFFFFFFull
+// (entry 12 is the camera bank's index, entry TC_CULL_ROW_ENTRY = 13 the whole-frame cull's verdict, tc_cull.h: written, polled and
+// reset like the twelve pose entries when the call's rows carry them, and like them never all ones)
+static_assert(TC_CULL_ROW_DRAW != TC_POSE_EMPTY && TC_CULL_ROW_CULLED != TC_POSE_EMPTY && TC_CULL_ROW_ENTRY == 13 && TC_CULL_ROW_ENTRY < TC_POSE_ROW,
+              "a verdict is never read as 'not written yet'");
 #define TC_FRAME_SKIPPED (-2)
 __device__ __forceinline__ void cam_pose12(const KArgs& a, int cam_row, const FramePose& fp, double* pose) {
   // this env's camera (camera.py:23-24,48-50): shared, or row cam_row of the camera rows (its own after
@@ -528,16 +532,15 @@ __device__ __forceinline__ void cam_pose12(const KArgs& a, int cam_row, const Fr
 #ifdef TC_ABLATE
 __device__ unsigned long long tc_cull_counts[2];  // frames that ran the test, frames it culled (lane 0 counts)
 #endif
-__device__ __forceinline__ bool cam_cull(const KArgs& a, const double* pose) {
+// the table's header fields the predicate reads, through scalar loads (one address for every lane)
+__device__ __forceinline__ void cam_cull_head(const KArgs& a, TcCullHead& h) {
   typedef const __attribute__((address_space(4))) double* DConst;
   typedef const __attribute__((address_space(4))) int* IConst;
-  typedef const __attribute__((address_space(4))) unsigned int* UConst;
   static_assert(offsetof(TcCullHead, margin) == 32 && offsetof(TcCullHead, nx) == 48 && offsetof(TcCullHead, n_special) == 56 &&
                     offsetof(TcCullHead, special) == 64 && TC_CULL_HEAD_BYTES % 4 == 0,
                 "the fields are read by offset below");
   const DConst hd = (DConst)(unsigned long long)a.cull_tab;
   const IConst hi = (IConst)(unsigned long long)a.cull_tab;
-  TcCullHead h;
   h.x0 = hd[0];
   h.y0 = hd[1];
   h.inv = hd[2];
@@ -546,6 +549,13 @@ __device__ __forceinline__ bool cam_cull(const KArgs& a, const double* pose) {
   h.nx = hi[12];
   h.ny = hi[13];
   h.n_special = hi[14];
+}
+__device__ __forceinline__ bool cam_cull(const KArgs& a, const double* pose) {
+  typedef const __attribute__((address_space(4))) double* DConst;
+  typedef const __attribute__((address_space(4))) unsigned int* UConst;
+  const DConst hd = (DConst)(unsigned long long)a.cull_tab;
+  TcCullHead h;
+  cam_cull_head(a, h);
   int cell[TC_CULL_NC];
   unsigned int word[TC_CULL_NC];
 #pragma unroll
@@ -578,12 +588,64 @@ __device__ __forceinline__ bool cam_cull(const KArgs& a, const double* pose) {
   return empty;
 }
 
+// The same predicate where the pose differs from lane to lane: the pose-row writers of the simulate kernels (k_envg.h holds an
+// env per group of lanes, k_env.h one per wavefront), which evaluate it once per (step, env) on the very pose they store and
+// leave the answer in entry TC_CULL_ROW_ENTRY of the row (tc_cull.h), so that no frame wavefront evaluates it again.  The same
+// pieces of tc_cull.h in the same order: header and special nodes through scalar loads, a cell's byte through a vector load.
+// Only called when a.cull_rows is set (then a.frame_cull is, and the table exists).
+__device__ __forceinline__ unsigned long long cam_cull_row(const KArgs& a, const double* pose) {
+  typedef const __attribute__((address_space(4))) double* DConst;
+  const DConst hd = (DConst)(unsigned long long)a.cull_tab;
+  TcCullHead h;
+  cam_cull_head(a, h);
+  bool empty = true;
+#pragma unroll
+  for (int i = 0; i < TC_CULL_NC; i++) {
+    double wx, wy;
+    tc_cull_world(pose, a.cull.c[i], &wx, &wy);
+    const int cell = tc_cull_cell(h, wx, wy, a.cull.r[i]);
+    // (a cell index is below nx * ny; the byte of cell 0 stands in for "no cell" and is not looked at)
+    const int q = (int)a.cull_tab[TC_CULL_HEAD_BYTES + (cell > 0 ? cell : 0)];
+    empty = empty && (cell == TC_CULL_CELL_CLEAR || (cell >= 0 && tc_cull_free(h, q, a.cull.r[i])));
+  }
+  if (empty) {  // guard G, only for a frame that would be culled
+    const double mr = a.cull.max_range;
+    for (int i = 0; i < h.n_special; i++) {
+      const double z = __builtin_fma(pose[9], hd[9 + 2 * i], __builtin_fma(pose[8], hd[8 + 2 * i], pose[11]));
+      empty = empty && tc_fabs(z + mr) >= TC_CULL_GUARD;
+    }
+  }
+  return tc_cull_row_encode(empty);
+}
+
 // LEAN: the form of the five-wave frame kernel -- the camera's K matrix in scalar registers (see below) and the one-word list
 // entries of cam_group_regs<K, PACKED>
-template <int K, bool LEAN = false>
+// ROW: the frame's pose came in a pose row, and with it the cull's verdict (`row_culled`, wave-uniform: what the simulate stage
+// left in entry TC_CULL_ROW_ENTRY, false when the call's rows carry none): the form of the frame, banded and recover kernels,
+// which never evaluate the predicate themselves.  !ROW: the pose was computed by this wavefront (the fused step kernels,
+// tc_env_kernel<.., CAM>): cam_cull here.
+// ONE_GROUP: the handle's camera groups are one group (KArgs::n_grp == 1) that fits the register cache -- cam_group_regs once,
+// no group loop whose invariants would have to be kept "because the loop could run again".  The form of tc_frame_kernel<5, .., 32>
+// alone (frame_kernel_of sends every other handle of that K to tc_frame_banded).
+template <int K, bool LEAN = false, bool ROW = false, bool ONE_GROUP = false>
 __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, int env, int cam_row, const double* pose_in, MapCache<K>& mc,
                                          const bool mc_loaded, const int tid, const int seg_row, int& nseg_out,
-                                         unsigned int& used_out, const bool store_n = true) {
+                                         unsigned int& used_out, const bool store_n = true, const bool row_culled = false) {
+  // Whole-frame cull: a pose whose visible ground footprint keeps clear of every lane-line segment has an empty draw
+  // list (tc_cull.h, DESIGN.md section 4) -- the stage ends here with what it delivers for an empty list: length 0, no
+  // layer, the length stored where it is stored otherwise, nothing written to the overflow list.
+#ifdef TC_ABLATE
+  if (ROW && a.cull_rows && threadIdx.x == 0) {  // (the counts of cam_cull, for the frames whose verdict came in the row)
+    atomicAdd(&tc_cull_counts[0], 1ull);
+    if (row_culled) atomicAdd(&tc_cull_counts[1], 1ull);
+  }
+#endif
+  if (ROW && row_culled) {  // (the pose was not even fetched: frame_pose)
+    nseg_out = 0;
+    used_out = 0;
+    if (store_n && tid == 0) a.seg_n[(size_t)seg_row * a.N + env] = 0;
+    return;
+  }
   unsigned int my_layers = 0;  // layers this lane put a segment into the draw list for
   const DevMap& m = a.m;
   const int nwin_n = (m.total_nodes + TC_NT * K - 1) / (TC_NT * K), nwin_e = (m.total_edges + TC_NT * K - 1) / (TC_NT * K);
@@ -592,10 +654,7 @@ __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, in
   double pose[12];
 #pragma unroll
   for (int i = 0; i < 12; i++) pose[i] = uni_d(pose_in[i]);
-  // Whole-frame cull: a pose whose visible ground footprint keeps clear of every lane-line segment has an empty draw
-  // list (tc_cull.h, DESIGN.md section 4) -- the stage ends here with what it delivers for an empty list: length 0, no
-  // layer, the length stored where it is stored otherwise, nothing written to the overflow list.
-  if (a.frame_cull && cam_cull(a, pose)) {
+  if (!ROW && a.frame_cull && cam_cull(a, pose)) {
     nseg_out = 0;
     used_out = 0;
     if (store_n && tid == 0) a.seg_n[(size_t)seg_row * a.N + env] = 0;
@@ -638,6 +697,22 @@ __device__ __forceinline__ void cam_body(const KArgs& a, unsigned char* smem, in
   const size_t seg_slot = (size_t)seg_row * a.N + env;
   int* segg = a.seg_g + seg_slot * a.seg_cap * 5;  // [seg_cap][5]: layer, x0, y0, x1, y1
   int nseg = 0;  // draw-list length so far (wave-uniform)
+  if constexpr (ONE_GROUP) {
+    // group 0 is all there is, and it sits in the register cache (the host checks both: frame_kernel_of's `looped`)
+    const int gn0 = a.grp_n0[0], ge0 = a.grp_e0[0];
+    const int nn = a.grp_n0[1] - gn0, ne = a.grp_e0[1] - ge0;
+    if (!single) {
+      if (a.cam_nodes) {
+        cache_nodes_from(mc, a.cam_nodes, gn0, gn0 + nn, tid);
+        cache_edges_from(mc, a.cam_edges_g, ge0, ge0 + ne, gn0, tid);
+      } else {
+        cache_nodes(mc, m, gn0, gn0 + nn, tid);
+        cache_edges(mc, m, ge0, ge0 + ne, gn0, tid);
+      }
+    }
+    cam_group_regs<K, LEAN>(a, mc, pose, Kc, cam_row, a.grp_l0[0], a.grp_l1[0], ge0, nn, ne, Px, Py, Pz, flg, list, segg,
+                            (LdsIntPtr)(smem + a.seg_lds_off), nseg, my_layers, env, tid);
+  } else
   for (int g = 0; g < a.n_grp; g++) {
     const int l0 = a.grp_l0[g], l1 = a.grp_l1[g];
     const int gn0 = a.grp_n0[g], ge0 = a.grp_e0[g];

@@ -155,6 +155,12 @@ struct KArgs {
   // Whole-frame cull (tc_cull.h).  frame_cull: TC_FRAME_CULL, and the map has a table, and the shared camera a cover (never
   // with per-env cameras: the cover is the shared camera's); cull_tab: header + cells (library owned, camera independent)
   int frame_cull;
+  // cull_rows: the pose rows of a call carry the verdict (entry TC_CULL_ROW_ENTRY, tc_cull.h): the simulate launch that writes
+  // a row evaluates the predicate on the pose it stores, and the frame kernels that draw from rows read the answer there.  Set
+  // where frame_cull is (cover_cull()): every frame launch draws from rows its own call's simulate launch wrote, so the two
+  // are on together -- and with a camera bank or per-env cameras both are off, entry 13 neither written nor polled.  0: the
+  // frame kernels draw every frame; the kernels that pose and draw in one wavefront go by frame_cull alone.
+  int cull_rows;
   const unsigned char* cull_tab;
   TcCullCover cull;
 };

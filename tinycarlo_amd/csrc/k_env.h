@@ -120,6 +120,8 @@ __device__ __forceinline__ void env_kernel_body() {
 #pragma unroll
         for (int i = 0; i < 6; i++) o[i] = make_double2(pose[2 * i], pose[2 * i + 1]);
         if (sa.flags & TC_FI_CAM_BANK) ((long long*)o)[12] = cam_row;  // (the bank index of this (step, env): see CamBank)
+        // the whole-frame cull's verdict on this pose, for the frame kernel that draws from the row (KArgs::cull_rows)
+        if (sa.a.cull_rows) ((unsigned long long*)o)[TC_CULL_ROW_ENTRY] = cam_cull_row(step_args().a, pose);
       }
     }
     if (CAM && sa.ma.cam_here) {

@@ -259,11 +259,17 @@ __device__ __forceinline__ void envg_kernel_body() {
             __hip_atomic_store(o + i, (unsigned long long)__double_as_longlong(pose[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           // with a bank, a thirteenth entry of the same kind: the index this (step, env) was posed with (never all ones)
           if (bank) __hip_atomic_store(o + 12, (unsigned long long)(unsigned int)cam_row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          // and the whole-frame cull's verdict on this very pose (cam_cull_row; KArgs::cull_rows), evaluated behind the twelve
+          // stores and stored last: the frame workgroup, which waits for it like for the others, then neither fetches the
+          // table nor runs the predicate -- here it is one evaluation per (step, env), eight envs to the wavefront
+          if (sa.a.cull_rows)
+            __hip_atomic_store(o + TC_CULL_ROW_ENTRY, cam_cull_row(sa.a, pose), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
           double2* o = (double2*)(sa.ma.pose_rows + (row0 + env) * TC_POSE_ROW);
 #pragma unroll
           for (int i = 0; i < 6; i++) o[i] = make_double2(pose[2 * i], pose[2 * i + 1]);
           if (bank) ((long long*)o)[12] = cam_row;
+          if (sa.a.cull_rows) ((unsigned long long*)o)[TC_CULL_ROW_ENTRY] = cam_cull_row(sa.a, pose);
         }
       }
     }

@@ -54,19 +54,26 @@ __device__ __forceinline__ const FrameArgs& frame_args() {
 // to be there (gate 2, or read before by this workgroup) -- one read.
 // cam_row: the frame's row of the camera rows -- the env, or with a bank the index the simulate stage left in entry 12,
 // polled and validated like the other twelve (kept inside the bank whatever the memory holds).
-__device__ __forceinline__ bool frame_pose(const size_t slot0, const int env, const int row, const bool wait, double* pose, int& cam_row) {
+// culled: the whole-frame cull's verdict on this pose, which the simulate stage left in entry TC_CULL_ROW_ENTRY when the call's
+// rows carry it (KArgs::cull_rows; tc_cull.h) -- polled and validated like the others, by lane 13.  A culled frame returns
+// without its pose: `pose` is then not set, and nothing moves to scalar registers.
+__device__ __forceinline__ bool frame_pose(const size_t slot0, const int env, const int row, const bool wait, double* pose, int& cam_row,
+                                           bool& culled) {
   const FrameArgs& fa = frame_args();
   const int tid = threadIdx.x;
   const int gate = fa.gate, bank = fa.bank;
-  const int np = bank ? 13 : 12;
+  const bool verdict = fa.a.cull_rows != 0;
   cam_row = env;
+  culled = false;
   if (gate) {
     unsigned long long* prow = (unsigned long long*)(fa.pose_rows + (slot0 + env) * TC_POSE_ROW);
     unsigned long long v = 0;
     bool give_up = wait && fa.gate == 1 && fa.gate_test > 0 && (row + env) % fa.gate_test == 0;
     long long t0 = 0;
     while (!give_up) {
-      v = tid < np ? __hip_atomic_load(prow + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+      v = (tid < 12 || (tid == 12 && bank) || (tid == TC_CULL_ROW_ENTRY && verdict))
+              ? __hip_atomic_load(prow + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+              : 0ull;
       if (__ballot(v == TC_POSE_EMPTY) == 0 || fa.gate == 2 || !wait) break;
       const long long now = wall_clock64();
       if (t0 == 0) t0 = now;
@@ -81,6 +88,11 @@ __device__ __forceinline__ bool frame_pose(const size_t slot0, const int env, co
         fa.a.seg_n[slot0 + env] = TC_FRAME_SKIPPED;
       }
       return false;
+    }
+    static_assert(TC_CULL_ROW_ENTRY > 12 && TC_CULL_ROW_ENTRY < TC_POSE_ROW && TC_CULL_ROW_ENTRY < TC_NT, "a lane and a row entry of its own");
+    if (__ballot(tid == TC_CULL_ROW_ENTRY && tc_cull_row_decode(v)) != 0) {  // (lane 13 holds 0 when the rows carry no verdict)
+      culled = true;
+      return true;
     }
     const unsigned int vlo = (unsigned int)v, vhi = (unsigned int)(v >> 32);
 #pragma unroll
@@ -98,6 +110,10 @@ __device__ __forceinline__ bool frame_pose(const size_t slot0, const int env, co
     // read through the scalar cache
     const __attribute__((address_space(4))) double* pr =
         (const __attribute__((address_space(4))) double*)(unsigned long long)(fa.pose_rows + (slot0 + env) * TC_POSE_ROW);
+    if (verdict && tc_cull_row_decode(((const __attribute__((address_space(4))) unsigned long long*)(unsigned long long)pr)[TC_CULL_ROW_ENTRY])) {
+      culled = true;
+      return true;
+    }
 #pragma unroll
     for (int i = 0; i < 12; i++) pose[i] = pr[i];
     if (bank) {
@@ -121,8 +137,9 @@ __device__ __forceinline__ bool frame_pose(const size_t slot0, const int env, co
 #define TC_FRAME_LEAN(K, RBT) ((K) <= 5 && (RBT) == 32)
 // One frame: `rowy` is the frame's row in the launch (its step), `env` its env.
 // HOT (tc_frame_kernel): the raster stage in its LDS-only form (see raster_body); !HOT (the recover kernel): the generic form.
-// ONE_BAND: the handle's frames are one raster band (raster_body's form without the band loop).
-template <int K, bool THICK, int FMT, bool HOT, int RBT, bool ONE_BAND = false>
+// ONE: the handle's frames are one raster band and its camera groups one group in the register cache (raster_body's form without
+// the band loop, cam_body's without the group loop).
+template <int K, bool THICK, int FMT, bool HOT, int RBT, bool ONE = false>
 __device__ __forceinline__ void frame_one(unsigned char* smem, const int env, const int rowy) {
   const int tid = threadIdx.x;
   int nseg;
@@ -133,12 +150,13 @@ __device__ __forceinline__ void frame_one(unsigned char* smem, const int env, co
     const size_t slot0 = (size_t)row * fa.a.N;
     double pose[12];
     int cam_row;
-    if (!frame_pose(slot0, env, row, true, pose, cam_row)) return;
+    bool culled;
+    if (!frame_pose(slot0, env, row, true, pose, cam_row, culled)) return;
     MapCache<K> mc;
     TSTAMP_CLEAR();
     TSTAMP(3);
     TSTAMP_REAL(30);
-    cam_body<K, TC_FRAME_LEAN(K, RBT)>(fa.a, smem, env, cam_row, pose, mc, false, tid, row, nseg, used, false);
+    cam_body<K, TC_FRAME_LEAN(K, RBT), true, ONE>(fa.a, smem, env, cam_row, pose, mc, false, tid, row, nseg, used, false, culled);
   }
   const FrameArgs& fr = frame_args();
   const size_t slot0 = (size_t)(fr.r.seg_row0 + rowy) * fr.a.N;
@@ -155,14 +173,15 @@ __device__ __forceinline__ void frame_one(unsigned char* smem, const int env, co
   } else {
     lds_sync();
   }
-  raster_body<THICK, FMT, HOT, RBT, TC_FRAME_LEAN(K, RBT), ONE_BAND>(fr.r, smem, env, fr.r.obs + (size_t)rowy * fr.r.obs_row_stride, tid, slot0, nseg, used,
+  raster_body<THICK, FMT, HOT, RBT, TC_FRAME_LEAN(K, RBT), ONE>(fr.r, smem, env, fr.r.obs + (size_t)rowy * fr.r.obs_row_stride, tid, slot0, nseg, used,
                                            fr.r.noise_row0 + rowy);
   {
     const FrameArgs& fe = frame_args();
     const size_t slot = (size_t)(fe.r.seg_row0 + rowy) * fe.a.N + env;
     if (tid == 0) fe.a.seg_n[slot] = nseg;  // workload statistics, the next dispatch's order, "drawn" for the recover pass
     // a streamed call's row goes back to "not written yet" for the next call (which starts behind this kernel)
-    if (fe.gate && tid < (fe.bank ? 13 : 12))
+    // (entry 12 with a bank, the cull's verdict in entry 13 when the rows carry it: what frame_pose polls)
+    if (fe.gate && (tid < 12 || (tid == 12 && fe.bank) || (tid == TC_CULL_ROW_ENTRY && fe.a.cull_rows)))
       __hip_atomic_store((unsigned long long*)(fe.pose_rows + slot * TC_POSE_ROW) + tid, TC_POSE_EMPTY, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -179,12 +198,13 @@ __global__ __launch_bounds__(TC_NT, TC_FRAME_WAVES(K, RBT)) void tc_frame_kernel
   if ((int)blockIdx.x >= fa.a.N) return;
   const int env = fa.order ? uni_i(((const __attribute__((address_space(4))) int*)(unsigned long long)fa.order)[blockIdx.x])
                            : fa.a.env0 + (int)blockIdx.x;
-  // (the five-wave kernel draws one-band frames only: frame_kernel_of sends a banded handle to tc_frame_banded)
+  // (the five-wave kernel draws one-band frames of one camera group only: frame_kernel_of sends every other handle to tc_frame_banded)
   frame_one<K, THICK, FMT, true, RBT, TC_FRAME_LEAN(K, RBT)>(smem, env, (int)blockIdx.y);
 }
 
 // The five-wave kernel for a handle whose frames are taller than one raster band (RCam::n_bands > 1; no benchmark config: a small
-// map at a large resolution): the same stages with the band loop.  tc_frame_kernel<5, .., 32> itself is the one-band form,
+// map at a large resolution) or whose camera groups are not one group in the register cache (KArgs::n_grp != 1: no handle of
+// this K and batch size today): the same stages with the band loop and the group loop.  tc_frame_kernel<5, .., 32> itself is the one-band form,
 // straight-line code -- the loop's invariants, set up in front of a loop that runs once, were 68 of its spilled scalar
 // registers ("Scalar spills, round 17").  Exists for TC_FRAME_LEAN (K, RBT) only: every other frame kernel
 // has the band loop in tc_frame_kernel, as it always had.  (Named without "_kernel": the kernel-variant matrix of the tests keeps

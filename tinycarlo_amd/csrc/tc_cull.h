@@ -98,6 +98,20 @@ TC_HD int tc_cull_empty(const TcCullHead& h, const unsigned char* cells, const T
   return tc_cull_guard(h, pose, cv.max_range);
 }
 
+// ---- the verdict as it travels in a pose row (entry TC_CULL_ROW_ENTRY of the row, k_camera.h): the simulate stage evaluates
+// the predicate once per (step, env) on the pose it stores, and the frame kernels read the answer instead of evaluating it
+// again on 64 lanes.  An 8-byte word like the pose entries, and like them never all ones ("not written yet").  Only the one
+// word "culled" skips a frame: whatever else the memory holds decodes as "draw", which is always right.
+#define TC_CULL_ROW_ENTRY 13
+#define TC_CULL_ROW_DRAW 0ull
+#define TC_CULL_ROW_CULLED 1ull
+TC_HD unsigned long long tc_cull_row_encode(int empty) { return empty ? TC_CULL_ROW_CULLED : TC_CULL_ROW_DRAW; }
+TC_HD int tc_cull_row_decode(unsigned long long w) { return w == TC_CULL_ROW_CULLED; }
+// the word a pose-row writer stores for `pose`
+TC_HD unsigned long long tc_cull_row_verdict(const TcCullHead& h, const unsigned char* cells, const TcCullCover& cv, const double* pose) {
+  return tc_cull_row_encode(tc_cull_empty(h, cells, cv, pose));
+}
+
 // ---- (a), (b): host functions
 #include <math.h>
 #include <vector>

@@ -196,9 +196,10 @@ static step_kern_t envg_kernel_of(unsigned feat) {
   return lift([](auto ft) -> step_kern_t { return tc_envg_kernel<ft>; }, Feats{feat});
 }
 // recover: tc_frame_recover_kernel, the pass behind a streamed call's frame launch
-// banded: the handle's frames are taller than one raster band (DevCam::n_bands > 1).  The five-wave kernel (TC_FRAME_LEAN) is
-// the one-band form and has tc_frame_banded beside it; every other frame kernel, and every recover kernel, has the band loop
-static frame_kern_t frame_kernel_of(int kcode, bool thick, int fmt, bool recover, bool banded) {
+// looped: the handle's frames need one of the loops (frame_looped()): more than one raster band, or camera groups that are not
+// one group in the register cache.  The five-wave kernel (TC_FRAME_LEAN) is the one-band, one-group form and has
+// tc_frame_banded, with both loops, beside it; every other frame kernel, and every recover kernel, has both loops itself
+static frame_kern_t frame_kernel_of(int kcode, bool thick, int fmt, bool recover, bool looped) {
   return lift(
       [](auto kc, auto t, auto f, auto rec, auto bd) -> frame_kern_t {
         constexpr int K = FrameKRb<kc>::K, RB = FrameKRb<kc>::RB;
@@ -206,7 +207,7 @@ static frame_kern_t frame_kernel_of(int kcode, bool thick, int fmt, bool recover
         else if constexpr (bd && TC_FRAME_LEAN(K, RB)) return tc_frame_banded<K, t, f, RB>;
         else return tc_frame_kernel<K, t, f, RB>;
       },
-      Kcodes{kcode}, Thicks{thick}, FrameFmts{fmt}, Bools{recover}, Bools{banded});
+      Kcodes{kcode}, Thicks{thick}, FrameFmts{fmt}, Bools{recover}, Bools{looped});
 }
 // K and batch size of the kernel frame_kernel_of picks for a code: what the host plans that kernel's LDS from
 static int frame_k_of(int kcode) {
@@ -999,8 +1000,8 @@ static int raise_lds_limits(const tc_env* e) {
         for (int fmt : {TC_FMT_CLASSES, TC_FMT_CLASSES_BITS, TC_FMT_RGB}) {
           for (unsigned feat = 0; feat <= (TC_FEAT_CTRL | TC_FEAT_ALL) && fmt != TC_FMT_CLASSES_BITS; feat++)
             raise((const void*)step_kernel_of(kcode, t, fmt, feat), lds, (feat & TC_FEAT_CTRL) ? "tc_drive_step_kernel" : "tc_step_kernel");
-          for (int banded = 0; banded < 2; banded++)  // (the same kernel twice where there is no banded one)
-            raise((const void*)frame_kernel_of(kcode, t, fmt, false, banded), lds, "tc_frame_kernel");
+          for (int looped = 0; looped < 2; looped++)  // (the same kernel twice where there is no looped one)
+            raise((const void*)frame_kernel_of(kcode, t, fmt, false, looped), lds, "tc_frame_kernel");
         }
   // tc_envg_kernel's LDS copies of the map (edge records + fat lanepath nodes, see launch_envg()) can exceed the 48 KB default
   const size_t envg_lds = ((size_t)m.total_edges * 48 + 15) / 16 * 16 + (size_t)m.lpN * sizeof(LpNode);
@@ -1069,6 +1070,9 @@ static void alloc_orders(tc_env* e) {
 static void cover_cull(tc_env* e) {
   tc_cull_cover(e->k.cam.E, e->k.cam.K, e->k.cam.W, e->k.cam.H, e->k.cam.max_range, e->cull_head, &e->k.cull);
   e->k.frame_cull = e->tune.frame_cull && e->k.cull_tab && e->k.cull.on && !e->k.cam_E;
+  // the verdict travels in the pose rows (KArgs::cull_rows): every frame launch reads rows that a simulate launch of the same
+  // call wrote with this very block, so whenever the cull is on the rows carry it
+  e->k.cull_rows = e->k.frame_cull;
 }
 static int plan_cull(tc_env* e) {
   const tc_map* map = e->map;
@@ -1959,6 +1963,14 @@ static StepArgs step_args_at(const tc_env* e, const Call& c, int c0) {
   return sa;
 }
 
+// frame_kernel_of's `looped`: a handle whose frames are taller than one raster band, or whose camera groups are not one group
+// that sits in the register cache (no handle of the five-wave kernel today: a map of several groups gets K = 9 or K = 5 with
+// batches of 16), draws with the kernels that keep the band loop and the group loop
+static bool frame_looped(const tc_env* e) {
+  const int kf = frame_k_of(e->kframe);
+  return e->k.cam.n_bands > 1 || e->k.n_grp != 1 || e->k.grp_n0[1] - e->k.grp_n0[0] > kf * TC_NT || e->k.grp_e0[1] - e->k.grp_e0[0] > kf * TC_NT;
+}
+
 // The argument block of a frame launch over scratch rows: of the streamed form (gated: see launch_streamed()) or of the ring.
 // `gate` and `order` are the launch's own.
 static FrameArgs frame_args_of(const tc_env* e, uint32_t flags, const RArgs& r, bool streamed) {
@@ -2078,13 +2090,13 @@ static int launch_streamed(tc_env* e, const Call& c) {
     HIP_TRY(hipGetLastError());
     if (c.prof && si == 0) HIP_TRY(hipEventRecord(e->ev[3][c.slot], fs));
     fa.gate = 1;
-    hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, false, fa.r.cam.n_bands > 1), dim3(N, cn), dim3(TC_NT), e->frame_lds, fs, fa);
+    hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, false, frame_looped(e)), dim3(N, cn), dim3(TC_NT), e->frame_lds, fs, fa);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamWaitEvent(fs, e->sim_ev, 0));
     fa.gate = 2;
     fa.recover_rows = cn;
     fa.order = nullptr;
-    hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, true, fa.r.cam.n_bands > 1), dim3(N), dim3(TC_NT), e->frame_lds, fs, fa);
+    hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, true, frame_looped(e)), dim3(N), dim3(TC_NT), e->frame_lds, fs, fa);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->slot_ev[0], fs));
     if (e->frame_order[0]) e->cost_row[0] = e->streamed.seg_n + (size_t)(cn - 1) * N;
@@ -2179,7 +2191,7 @@ static int launch_chunked(tc_env* e, const Call& c) {
       // two streams, re-sort only once per call and otherwise keep the stream's last order)
       int rc = frame_order_of(e, fsi, fs, rows >= 8 || ci < 2, &fa.order);
       if (rc != TC_OK) return rc;
-      hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, false, fa.r.cam.n_bands > 1), dim3(N, rows), dim3(TC_NT), e->frame_lds, fs, fa);
+      hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thick, c.fmt, false, frame_looped(e)), dim3(N, rows), dim3(TC_NT), e->frame_lds, fs, fa);
       if (e->frame_order[fsi]) e->cost_row[fsi] = e->ring.seg_n + ((size_t)r.seg_row0 + (size_t)rows - 1) * N;
     } else {
       hipLaunchKernelGGL(raster_kernel_of(c.thick, c.fmt), dim3(N, rows), dim3(TC_NT), e->r_lds, fs, r);
@@ -2428,7 +2440,7 @@ extern "C" int tc_env_frame_lds_info(const tc_env* e, int32_t* lds_bytes, int32_
     if (e->kvar != 13) {  // (K = 13 handles have no frame kernel: plan_call)
       const DevCam& c = e->k.cam;
       int n = 0;
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)frame_kernel_of(e->kframe, c.thickness > 1, c.format, false, c.n_bands > 1), TC_NT,
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)frame_kernel_of(e->kframe, c.thickness > 1, c.format, false, frame_looped(e)), TC_NT,
                                                            (size_t)e->frame_lds));
       *workgroups_per_cu = n;
     }
