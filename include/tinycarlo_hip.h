@@ -576,6 +576,18 @@ int tc_env_launch_info(const tc_env* env, uint32_t flags, int32_t n_steps, int32
 int tc_env_frame_lds_info(const tc_env* env, int32_t* lds_bytes, int32_t* head_entries, int32_t* workgroups_per_cu,
                           int32_t* bits_offset);
 
+/* The LDS of a workgroup of the grouped simulate launch of a K-step call (tc_envg_kernel / tc_drive_envg_kernel, the variant
+ * of the features installed on the handle), which in a streamed call shares its CU with the frame workgroups for most of
+ * the call.  info_every != 0: a call whose every step computes the lane-line distances (a rollout with laneline_distances /
+ * nearest_edge rows; an installed lane-line term or TC_INFO_EVERY_STEP=1 make every call such a call) -- the launch then
+ * holds the lane-line edge records in LDS (map_in_lds = 1) where the map allows it; otherwise only a launch's last step
+ * reads them, from global memory.  dynamic_bytes = what the launch asks for, static_bytes = the kernel's own,
+ * workgroups = of a launch over the handle's envs, frames_beside = frame workgroups (tc_env_frame_lds_info's lds_bytes,
+ * granted in steps of 1280 bytes) that fit a CU's 160 KB beside one simulate workgroup; 0 for handles without a frame
+ * kernel.  The figures are the launch's own plan; nothing is launched.  Any pointer may be NULL. */
+int tc_env_envg_lds_info(const tc_env* env, int32_t info_every, int32_t* dynamic_bytes, int32_t* static_bytes,
+                         int32_t* workgroups, int32_t* frames_beside, int32_t* map_in_lds);
+
 /* The raster bands of the handle's frames: a frame whose bit-planes do not fit the LDS budget of one band (TC_BAND_BYTES) is
  * rasterised in n_bands bands of band_rows rows (the last one shorter).  n_bands == 1 is every bundled config at the
  * benchmark resolutions up to 128 x 128; the K = 5 frame kernel with batches of 32 then runs its one-band form, and

@@ -49,7 +49,7 @@ PAD_ZERO, PAD_EDGE = 0, 1  # TC_PAD_*
 EXPORTS = ["tc_abi_version", "tc_last_error", "tc_map_create", "tc_map_destroy", "tc_env_create", "tc_env_destroy",
            "tc_env_bind", "tc_env_set_camera", "tc_env_set_camera_per_env", "tc_env_set_camera_bank", "tc_env_set_car", "tc_env_set_car_per_env",
            "tc_env_set_car_randomization", "tc_env_set_episodes", "tc_env_set_episode_rollout", "tc_env_set_controller", "tc_env_set_drive_randomization", "tc_draw_normals", "tc_env_set_terms", "tc_env_set_spawn_table", "tc_env_set_noise", "tc_noise", "tc_env_obs_bytes", "tc_env_lds_bytes", "tc_env_profile",
-           "tc_env_profile_read", "tc_reset", "tc_step", "tc_step_multi", "tc_env_reserve_steps", "tc_env_launch_info", "tc_env_frame_lds_info", "tc_env_frame_bands", "tc_env_draw_list_stats", "tc_render",
+           "tc_env_profile_read", "tc_reset", "tc_step", "tc_step_multi", "tc_env_reserve_steps", "tc_env_launch_info", "tc_env_frame_lds_info", "tc_env_envg_lds_info", "tc_env_frame_bands", "tc_env_draw_list_stats", "tc_render",
            "tc_render_segments", "tc_unpack_bits", "tc_collect", "tc_collect_scratch_bytes",
            "tc_collect_link", "tc_history_resolve", "tc_gather_frames"]
 
@@ -186,6 +186,7 @@ def lib():
     L.tc_env_draw_list_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int64)]
     L.tc_env_frame_lds_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 4
+    L.tc_env_envg_lds_info.argtypes = [C.c_void_p, C.c_int32] + [C.POINTER(C.c_int32)] * 5
     L.tc_env_frame_bands.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
     L.tc_env_launch_info.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32), C.c_char_p, C.c_int32]

@@ -222,6 +222,9 @@ struct MultiArgs {
                       // copied into the workgroup's LDS at kernel start and phase B reads them from there
   int fat_lds;        // tc_envg_kernel: 1 = the lanepath's fat node records (96 bytes per node) sit in LDS too, behind the
                       // edge records (or at offset 0 without them), and lanepath tracking reads them there
+  int grp_off, grp_stride, cnt_off;  // tc_envg_kernel: the per-env block of distances and term counters in dynamic LDS
+                                     // (GroupLds, k_envg.h): env g of the workgroup at grp_off + g * grp_stride, its
+                                     // counters cnt_off bytes in (plan_envg_lds, tc_plan.h)
   tc_rollout roll;
 };
 // (base pointers and the row: the address of a row is formed where it is stored, under its null test -- forming all 15 row

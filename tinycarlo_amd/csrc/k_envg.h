@@ -1,6 +1,6 @@
 // k_envg.h -- the grouped simulate kernels for K-step calls: the two phases of k_sim.h (car.py:70-148, 46-53;
 // layer.py:33-44, car.py:55-64) restated for TC_EL = 8 lanes per env, 64 / TC_EL envs per wavefront, state in registers
-// for the whole launch, the edge records in LDS.  Holds TC_EL, the tunables TC_ENVG_NT / TC_ENVG_PRIO, GroupLds,
+// for the whole launch, the lanepath records in LDS and -- when every step reads them -- the edge records too.  Holds TC_EL, the tunables TC_ENVG_NT / TC_ENVG_PRIO, GroupLds,
 // envg_kernel_body<FEAT>, tc_envg_kernel and tc_drive_envg_kernel (the TC_FEAT_CTRL entry point).  Leaves poses, never
 // frames: tc_frame_kernel (k_frame.h) draws them.  Includes k_env.h (StepArgs and its idiom; through it k_sim.h, k_feat.h).
 #ifndef K_ENVG_H
@@ -27,9 +27,13 @@
 #ifndef TC_ENVG_PRIO
 #define TC_ENVG_PRIO 3
 #endif
-struct GroupLds {  // per env of the wavefront: what the reward / termination terms read and count
-  double dist[TC_MAX_LAYERS];
-  int cnt[TC_MAX_TERMS];
+// Per env of the workgroup, what the reward / termination terms read and count: one distance per lane-line layer of the
+// map and the TC_MAX_TERMS counters.  The block sits in the launch's dynamic LDS, behind the map
+// records, sized by plan_envg_lds (tc_plan.h) for the map -- as a static array of TC_MAX_LAYERS doubles and TC_MAX_TERMS
+// ints per env it was 5 KB, most of which a five-layer map never touched.
+struct GroupLds {
+  double* dist;  // [C]
+  int* cnt;      // [TC_MAX_TERMS]
 };
 
 // Where the edge records are read from matters when the kernel runs beside the frame kernel: a frame wavefront ends
@@ -37,11 +41,13 @@ struct GroupLds {  // per env of the wavefront: what the reward / termination te
 // the CU's vector-memory pipeline (measured: 22 us per step alone, 35 us beside the frame kernel, 23 us beside a frame
 // kernel with its stores switched off).  The edge scan is ~33 loads per lane and step: from LDS it neither waits for
 // the stores nor pays an L2 round trip per batch of loads.
+//   That holds for a launch whose every step scans (TC_FI_INFO_EVERY).  A launch that scans in its last step only reads
+// the records from global memory (ma.map_lds = 0, plan_envg_lds): the workgroup sits on a CU beside the frame workgroups
+// for the whole launch, and 12 KB held for 128 steps to be read in one are LDS those cannot have.
 typedef const __attribute__((address_space(3))) double* LdsDouble;
 template <unsigned FEAT>
 __device__ __forceinline__ void envg_kernel_body() {
   constexpr bool PER = (FEAT & TC_FEAT_CAR) != 0, EP = (FEAT & TC_FEAT_EP) != 0, CTRL = (FEAT & TC_FEAT_CTRL) != 0;
-  __shared__ GroupLds glds[TC_ENVG_NT / TC_EL];
   extern __shared__ __align__(16) unsigned char gsm[];
   // Highest issue priority: when this kernel shares the chip with the frame kernel of the previous chunk it is the
   // critical path (a serial chain per step, few instructions), and the frame wavefronts would otherwise crowd it out
@@ -83,7 +89,9 @@ __device__ __forceinline__ void envg_kernel_body() {
   if (map_lds || fat_lds) __syncthreads();
   const bool live = env < N;  // groups past the last env compute on a copy of it and store nothing
   env = live ? env : N - 1;
-  GroupLds& gl = glds[grp];
+  GroupLds gl;
+  gl.dist = (double*)(gsm + s0.ma.grp_off + grp * s0.ma.grp_stride);
+  gl.cnt = (int*)(gsm + s0.ma.grp_off + grp * s0.ma.grp_stride + s0.ma.cnt_off);
   CarState s;
   int nr = 0, cursor = 0, cursor0 = 0;
   bool have_trig = false;
@@ -106,7 +114,10 @@ __device__ __forceinline__ void envg_kernel_body() {
       nr = b.needs_reset[env];
       cursor = cursor0 = b.spawn_cursor[env];
     }
-    if (sub < TC_MAX_TERMS) gl.cnt[sub] = (s0.a.n_terms > 0 && s0.a.term_counters) ? s0.a.term_counters[(size_t)env * TC_MAX_TERMS + sub] : 0;
+    // (without terms the counters are never read; the variants with the episode accounting set them all the same, as they
+    // always did: leaving the store out moves their register allocation off the recorded 123 / 125 VGPRs)
+    if (sub < TC_MAX_TERMS && (EP || s0.a.n_terms > 0))
+      gl.cnt[sub] = (s0.a.n_terms > 0 && s0.a.term_counters) ? s0.a.term_counters[(size_t)env * TC_MAX_TERMS + sub] : 0;
     static_assert(TC_EL >= TC_MAX_TERMS, "one lane per term counter");
   }
   // the running episode (EP) waits in LDS between its two uses per step (three registers per lane across the whole step

@@ -255,6 +255,60 @@ static inline FrameLds plan_frame_lds(int cap_n, int cap_e, int total_nodes, boo
   return f;
 }
 
+// LDS of a tc_envg_kernel / tc_drive_envg_kernel workgroup.  The simulate launch of a streamed call runs BESIDE the frame
+// dispatch for most of the call, one workgroup on a CU, and what it holds there the frame workgroups cannot have: every
+// TC_LDS_STEP * 7 = 8960 bytes (cfg3) is one frame workgroup fewer on that CU while the launch lasts.  So the launch asks
+// for what THIS call reads:
+//   - the lane-line edge records (48 bytes per edge; phase B's edge scan) only when every step runs phase B
+//     (`info_every`, CallPlan::info_every).  Otherwise phase B runs in the launch's last step alone and reads the records
+//     from global memory: a copy held for 128 steps and read in one is not worth its bytes.
+//   - the lanepath's fat node records (`lp_node_bytes` each; the tracking of every step), as before.
+//   - per env of the workgroup (`groups` of them), one double per lane-line layer of THIS map (the distances the terms
+//     read), not TC_MAX_LAYERS of them, and the terms' `max_terms` counters.
+// `map_switch`: TC_ENVG_MAP_LDS (0: neither table in LDS).  `static_bytes`: the kernel's own static LDS (the per-env words
+// of the features compiled in: envg_static_lds).  `pad`: unused bytes (experiment builds).  `frame_lds`: the dynamic LDS of
+// a frame workgroup of the handle (0: the handle has no frame kernel), for frames_beside.
+#define TC_CU_LDS (160 * 1024)
+struct EnvgLds {
+  int map_lds = 0, fat_lds = 0;  // MultiArgs::map_lds / fat_lds
+  int fat_off = 0;               // the fat node records: behind the edge records, or at 0 without them
+  int grp_off = 0, grp_stride = 0, cnt_off = 0;  // env g's block at grp_off + g * grp_stride: distances, counters at cnt_off
+  int dynamic = 0;               // dynamic LDS of the launch
+  int static_bytes = 0;
+  int granted = 0;               // dynamic + static as a CU grants it: whole steps of TC_LDS_STEP
+  int workgroups = 0;            // of the launch
+  int frames_beside = 0;         // frame workgroups that fit on a CU beside one simulate workgroup
+};
+// static LDS of the kernel: the camera-bank index of every env, the running episode (EP) and the drive randomisation's
+// maneuver / draw counter / OU value (CTRL) -- per env where the feature is compiled in, nothing otherwise (the host
+// source reports the compiler's own figure, tc_env_envg_lds_info; this restates it for the CPU tests)
+static inline int envg_static_lds(int groups, bool ep, bool ctrl) {
+  return groups * 4 + (ep ? groups * (4 + 8) : 0) + (ctrl ? groups * (4 + 4 + 8) : 0);
+}
+static inline EnvgLds plan_envg_lds(int total_edges, int lpN, int lp_node_bytes, int C, int max_terms, int N,
+                                    int groups, bool info_every, bool map_switch, int static_bytes, int frame_lds, int pad) {
+  EnvgLds p;
+  const long long map_bytes = align_up(total_edges * 48, 16), fat_bytes = (long long)lpN * lp_node_bytes;
+  p.map_lds = (map_switch && info_every && map_bytes <= 40 * 1024) ? 1 : 0;
+  p.fat_lds = (map_switch && fat_bytes <= 56 * 1024) ? 1 : 0;
+  int off = 0;
+  if (p.map_lds) off += (int)map_bytes;
+  p.fat_off = off;
+  if (p.fat_lds) off += (int)fat_bytes;
+  off = align_up(off, 16);
+  p.grp_off = off;
+  p.cnt_off = C * 8;
+  p.grp_stride = C * 8 + align_up(max_terms * 4, 8);
+  off += groups * p.grp_stride;
+  p.dynamic = align_up(off, 16) + pad;
+  p.static_bytes = static_bytes;
+  p.granted = align_up(p.dynamic + p.static_bytes, TC_LDS_STEP);
+  p.workgroups = (N + groups - 1) / groups;
+  const int frame_granted = align_up(frame_lds, TC_LDS_STEP);
+  p.frames_beside = frame_granted > 0 && p.granted < TC_CU_LDS ? (TC_CU_LDS - p.granted) / frame_granted : 0;
+  return p;
+}
+
 // Which way a call of nsteps steps goes through launch() on a handle: decided here for launch(), which dispatches on
 // it, and for tc_env_launch_info, which reports it.  What the decision reads of the handle and of the call comes in as
 // plain values (the host side fills them in one place, plan_of()).

@@ -287,7 +287,7 @@ struct Tuning {
   int order_every;    // the env order of single steps is refreshed every n-th tc_step, 0 = no such order
   double scratch_bytes;  // budget of the scratch of streamed K-step calls
   bool print_lds = false;             // development builds only (TC_ABLATE)
-  int lds_pad = 0, step_lds_pad = 0;  // development builds only (TC_EXPERIMENT)
+  int lds_pad = 0, step_lds_pad = 0, envg_lds_pad = 0;  // development builds only (TC_EXPERIMENT)
 };
 
 static Tuning read_tuning() {
@@ -324,6 +324,7 @@ static Tuning read_tuning() {
 #ifdef TC_EXPERIMENT
       {"TC_LDS_PAD", "0", "unused LDS bytes per frame workgroup (occupancy experiments)"},
       {"TC_STEP_LDS_PAD", "0", "unused LDS bytes per tc_step_kernel workgroup"},
+      {"TC_ENVG_LDS_PAD", "0", "unused LDS bytes per tc_envg_kernel workgroup (what a simulate workgroup costs the frames beside it)"},
 #endif
   };
   // the switch's text, or its default; *set: whether the environment has it
@@ -371,6 +372,7 @@ static Tuning read_tuning() {
 #ifdef TC_EXPERIMENT
   t.lds_pad = atoi(sw("TC_LDS_PAD"));
   t.step_lds_pad = atoi(sw("TC_STEP_LDS_PAD"));
+  t.envg_lds_pad = atoi(sw("TC_ENVG_LDS_PAD"));
 #endif
   return t;
 }
@@ -979,8 +981,19 @@ static void grow_lds_for_draw_lists(tc_env* e) {
 #endif
 }
 
+// The LDS of a workgroup of the grouped simulate launch (launch_envg(); plan_envg_lds, tc_plan.h), for a call whose every step runs phase B
+// (`info_every`) or whose launches do so in their last step only: for launch_envg(), which asks for it, for
+// raise_lds_limits() and for tc_env_envg_lds_info, which reports it.  static_bytes: of the kernel variant, 0 = not asked.
+static EnvgLds envg_lds_of(const tc_env* e, bool info_every, int static_bytes) {
+  int pad = 0;
+#ifdef TC_EXPERIMENT
+  pad = e->tune.envg_lds_pad;  // (occupancy experiments: see plan_frame)
+#endif
+  return plan_envg_lds(e->k.m.total_edges, e->k.m.lpN, (int)sizeof(LpNode), e->k.m.C, TC_MAX_TERMS, e->k.N,
+                       TC_ENVG_NT / TC_EL, info_every, e->tune.envg_map_lds != 0, static_bytes, e->kvar != 13 ? e->frame_lds : 0, pad);
+}
+
 static int raise_lds_limits(const tc_env* e) {
-  const DevMap& m = e->k.m;
   const int total = e->k.lds.total;
   int rc = TC_OK;
   // lets `kernel` be launched with `bytes` of dynamic LDS (beyond the runtime's default limit); after a refusal no more are tried
@@ -1004,7 +1017,8 @@ static int raise_lds_limits(const tc_env* e) {
             raise((const void*)frame_kernel_of(kcode, t, fmt, false, looped), lds, "tc_frame_kernel");
         }
   // tc_envg_kernel's LDS copies of the map (edge records + fat lanepath nodes, see launch_envg()) can exceed the 48 KB default
-  const size_t envg_lds = ((size_t)m.total_edges * 48 + 15) / 16 * 16 + (size_t)m.lpN * sizeof(LpNode);
+  // (the larger form: every step reads the edge records)
+  const size_t envg_lds = (size_t)envg_lds_of(e, true, 0).dynamic;
   if (envg_lds > 40 * 1024)
     for (unsigned feat = 0; feat <= (TC_FEAT_CTRL | TC_FEAT_ALL); feat++)
       raise((const void*)envg_kernel_of(feat), (int)(envg_lds < 150 * 1024 ? envg_lds : 150 * 1024),
@@ -2008,14 +2022,16 @@ static FrameArgs frame_args_of(const tc_env* e, uint32_t flags, const RArgs& r, 
 // The grouped simulate launch (tc_envg_kernel: 32 envs per workgroup) of the steps `sa` describes.
 static unsigned int envg_grid(int N) { return (unsigned int)((N + TC_ENVG_NT / TC_EL - 1) / (TC_ENVG_NT / TC_EL)); }
 static int launch_envg(const tc_env* e, unsigned feat, StepArgs& sa, hipStream_t stream) {
-  // LDS copies of the lane-line edge records (48 B per edge) and of the lanepath's fat node records (96 B per node):
-  // simple_layout 12.4 + 17.5 KB, knuffingen 34.6 + 40.2 KB per workgroup of 32 envs (a CU holds one or two such
-  // workgroups: 128 of them cover 4096 envs)
-  const size_t map_bytes = ((size_t)e->k.m.total_edges * 48 + 15) / 16 * 16, fat_bytes = (size_t)e->k.m.lpN * sizeof(LpNode);
-  sa.ma.map_lds = (e->tune.envg_map_lds && map_bytes <= 40 * 1024) ? 1 : 0;
-  sa.ma.fat_lds = (e->tune.envg_map_lds && fat_bytes <= 56 * 1024) ? 1 : 0;
-  hipLaunchKernelGGL(envg_kernel_of(feat), dim3(envg_grid(e->k.N)), dim3(TC_ENVG_NT),
-                     (sa.ma.map_lds ? map_bytes : 0) + (sa.ma.fat_lds ? fat_bytes : 0), stream, sa);
+  // The lanepath's fat node records (96 B per node) always; the lane-line edge records (48 B per edge) only when every
+  // step reads them; the per-env distances and counters behind them.  simple_layout: 17.5 KB + 2.3 KB, with the edge
+  // records 12.4 KB more; knuffingen 40.2 KB (+ 34.6 KB).  128 such workgroups cover 4096 envs, one to a CU.
+  const EnvgLds p = envg_lds_of(e, (sa.flags & TC_FI_INFO_EVERY) != 0, 0);
+  sa.ma.map_lds = p.map_lds;
+  sa.ma.fat_lds = p.fat_lds;
+  sa.ma.grp_off = p.grp_off;
+  sa.ma.grp_stride = p.grp_stride;
+  sa.ma.cnt_off = p.cnt_off;
+  hipLaunchKernelGGL(envg_kernel_of(feat), dim3(envg_grid(e->k.N)), dim3(TC_ENVG_NT), (size_t)p.dynamic, stream, sa);
   HIP_TRY(hipGetLastError());
   return TC_OK;
 }
@@ -2445,6 +2461,22 @@ extern "C" int tc_env_frame_lds_info(const tc_env* e, int32_t* lds_bytes, int32_
       *workgroups_per_cu = n;
     }
   }
+  return TC_OK;
+}
+
+extern "C" int tc_env_envg_lds_info(const tc_env* e, int32_t info_every, int32_t* dynamic_bytes, int32_t* static_bytes,
+                                    int32_t* workgroups, int32_t* frames_beside, int32_t* map_in_lds) {
+  if (!e) return TC_E_INVALID;
+  // the variant a K-step call of the handle as it stands would launch (launch(): the features installed)
+  const unsigned feat = (e->cr.rows ? TC_FEAT_CAR : 0u) | (e->ep.length ? TC_FEAT_EP : 0u) | (e->ct.tab ? TC_FEAT_CTRL : 0u);
+  hipFuncAttributes fa;
+  HIP_TRY(hipFuncGetAttributes(&fa, (const void*)envg_kernel_of(feat)));
+  const EnvgLds p = envg_lds_of(e, info_every != 0 || e->terms_read_dist || e->tune.info_every, (int)fa.sharedSizeBytes);
+  if (dynamic_bytes) *dynamic_bytes = p.dynamic;
+  if (static_bytes) *static_bytes = p.static_bytes;
+  if (workgroups) *workgroups = p.workgroups;
+  if (frames_beside) *frames_beside = p.frames_beside;
+  if (map_in_lds) *map_in_lds = p.map_lds;
   return TC_OK;
 }
 

@@ -1218,6 +1218,17 @@ class TinyCarloVecEnv(gym.Env):
                                                name, 64), "tc_env_launch_info")
         return {"fused": bool(f.value), "kvar": kv.value, "kernel": name.value.decode(), "steps_per_dispatch": spd.value}
 
+    def envg_lds_info(self, info_every: bool = False) -> Dict[str, int]:
+        """The LDS of a workgroup of the grouped simulate launch of a K-step call (tc_env_envg_lds_info): dynamic and
+        static bytes, workgroups per launch, frame workgroups that fit on a CU beside one, and whether the lane-line edge
+        records sit in LDS.  info_every: a call with laneline_distances / nearest_edge rows.  No launch."""
+        d, s, w, f, m = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().tc_env_envg_lds_info(self._h, int(bool(info_every)), C.byref(d), C.byref(s), C.byref(w),
+                                                     C.byref(f), C.byref(m)), "tc_env_envg_lds_info")
+        return {"dynamic_bytes": d.value, "static_bytes": s.value, "workgroups": w.value, "frames_beside": f.value,
+                "map_in_lds": m.value}
+
     def frame_lds_info(self) -> Dict[str, int]:
         """The LDS plan of the handle's frame kernel (tc_env_frame_lds_info): bytes per workgroup, draw-list entries its
         LDS head holds, workgroups per CU as the runtime computes them, offset of the raster bit-planes; and the raster
