@@ -44,11 +44,14 @@
 extern "C" {
 #endif
 
-/* ABI 6: per-env car constants and their per-episode draw (tc_env_set_car, tc_env_set_car_per_env,
+/* ABI 7: the per-step rows of the per-episode features are arguments of the K-step call (tc_step_rows, a parameter of
+ * tc_step_multi) and no longer installed on the handle: the episode-rollout setter and the row members of tc_controller,
+ * tc_drive_randomization and tc_camera_bank are gone.
+ * ABI 6: per-env car constants and their per-episode draw (tc_env_set_car, tc_env_set_car_per_env,
  * tc_env_set_car_randomization, TC_CAR_*) */
-#define TC_ABI_VERSION 6
-/* Additive within ABI 6 (new entry points only, no struct changed): tc_env_set_episodes, tc_env_set_episode_rollout,
- * TC_S_TIME_LIMIT.  Callers that must run against an older ABI-6 library test for this macro / the symbols. */
+#define TC_ABI_VERSION 7
+/* Additive within ABI 6 (new entry points only, no struct changed): tc_env_set_episodes, TC_S_TIME_LIMIT.  Callers that
+ * must run against an older ABI-6 library test for this macro / the symbols. */
 #define TC_HAS_EPISODES 1
 /* Likewise additive within ABI 6: tc_env_set_controller, tc_controller, TC_CTRL_STANLEY. */
 #define TC_HAS_CONTROLLER 1
@@ -245,18 +248,16 @@ int tc_env_set_camera_per_env(tc_env* env, const double* E, const double* K);
  * (tinycarlo_amd/csrc/tc_rng.h: tc_camera_index; a stream of its own, and a counter apart from the cars').
  * The index in force when a step was simulated travels WITH that (step, env) to wherever its frame is drawn -- in a streamed,
  * chunked or recovered K-step call that is possibly after the env has re-spawned again -- so a frame is always projected with
- * the E and K of the episode it belongs to.  index_rows[k][i] receives the index in force at step k of a tc_step_multi call.
+ * the E and K of the episode it belongs to.  tc_step_rows.camera_out[k][i] receives the index in force at step k of a
+ * tc_step_multi call.
  * Everything else is as with per-env cameras: resolution, max_range, thickness and format stay shared, draw-list capacity and
  * plan hold for arbitrary E / K, and the whole-frame cull is off while a bank is installed.  A bank and the static rows of
  * tc_env_set_camera_per_env exclude each other: installing one removes the other.  bank = NULL returns to the shared camera.
  * seed, count and env_offset sit in a library-owned device table updated in place (a captured graph sees new settings
- * without re-capture; a call that changes them waits for the device); the pointers are kernel arguments of the launches
- * enqueued afterwards (a call that only changes them does not wait).  Because of that wait, do not change seed, count or
- * env_offset while a stream is being captured (the capture would fail); a call that only installs other index_rows, as one
- * per K-step call does, is safe there.  An index found outside [0, count) in `index` is read
+ * without re-capture; a call that changes them waits for the device, one that leaves them as they are does not); the
+ * pointers are kernel arguments of the launches enqueued afterwards.  An index found outside [0, count) in `index` is read
  * as count - 1; nothing is read out of bounds.
- * TC_E_INVALID: a NULL E, K, index or episode, count < 1, n_rows < 0, index_rows with n_rows = 0, and from a tc_step_multi
- * call of more than n_rows steps while index_rows is set. */
+ * TC_E_INVALID: a NULL E, K, index or episode, count < 1. */
 typedef struct {
   const double* E;     /* device [count][12] */
   const double* K;     /* device [count][9] */
@@ -265,8 +266,6 @@ typedef struct {
   uint64_t seed;
   int32_t* index;      /* device [N], in/out, caller owned: the camera each env uses */
   int32_t* episode;    /* device [N], in/out, caller owned: cameras drawn so far */
-  int32_t* index_rows; /* device [n_rows][N], out, or NULL */
-  int32_t n_rows;      /* rows of index_rows (0 when it is NULL) */
 } tc_camera_bank;
 int tc_env_set_camera_bank(tc_env* env, const tc_camera_bank* bank); /* NULL = off */
 /* New shared car (Car constants assigned at run time: the reference's Car.step reads them on every step, car.py:70-125).
@@ -292,8 +291,7 @@ int tc_env_set_car_randomization(tc_env* env, const double* lo, const double* hi
 /* Episode time limit and per-env episode statistics, kept by the step kernels (gymnasium's TimeLimit and
  * RecordEpisodeStatistics; `for ep_step in range(MAX_STEPS)` / `ep_rew += rew` of examples/train_td3.py:181,199).
  * All members are DEVICE arrays of N, caller owned, read and written by every tc_reset / tc_step / tc_step_multi until
- * replaced.  length and ret are required, the others may be NULL.  bufs = NULL switches the feature off (and drops the
- * per-step rows below); without it nothing changes, and the kernels that do the accounting are separate instantiations
+ * replaced.  length and ret are required, the others may be NULL.  bufs = NULL switches the feature off; without it nothing changes, and the kernels that do the accounting are separate instantiations
  * chosen at launch (the TC_FEAT_EP bit of their feature mask): the others are untouched.
  * Per env i; limit_i = limit[i] when limit is given, else max_episode_steps; a value <= 0 means no limit:
  *   1. (re)spawned by tc_reset (mask) or by a TC_F_AUTORESET re-spawn at the start of a step: length = 0, ret = 0.0.  The
@@ -320,11 +318,8 @@ typedef struct {
   const int32_t* limit; /* [N] per-env limit, or NULL */
 } tc_episode_buffers;
 int tc_env_set_episodes(tc_env* env, const tc_episode_buffers* bufs, int32_t max_episode_steps);
-/* Per-step rows of tc_step_multi calls: after step k of a call, length_rows[k][i] / return_rows[k][i] hold env i's
- * length / ret (the episode's totals on a row where it ended, 0 / 0.0 on a re-spawn row).  [n_rows][N] each, device,
- * caller owned, either may be NULL; (NULL, NULL, 0) removes them.  TC_E_INVALID for n_rows < 0, for rows without episode
- * buffers, and from a tc_step_multi call of more than n_rows steps. */
-int tc_env_set_episode_rollout(tc_env* env, int32_t* length_rows, double* return_rows, int32_t n_rows);
+/* Per step of a tc_step_multi call: tc_step_rows.episode_length_out[k][i] / episode_return_out[k][i] hold env i's length /
+ * ret after step k (the episode's totals on a row where it ended, 0 / 0.0 on a re-spawn row). */
 /* Built-in controller: the action of every step is computed by the simulate kernels from what the env reported after its
  * previous step, so a closed control loop -- the `while: step(controller(info))` of examples/stanley_control.py:50-60 and
  * of the data collection of examples/train_stanley_il.py -- runs inside ONE tc_step_multi call.  With a controller
@@ -335,28 +330,23 @@ int tc_env_set_episode_rollout(tc_env* env, int32_t* length_rows, double* return
  *     after its previous step: the bound cte / heading_error buffers at the first step of a call, 0 / 0 after a reset or
  *     re-spawn -- exactly what a host loop reads between two tc_step calls.  max_steering_angle is the env's own: its
  *     per-env car row when rows are installed (tc_env_set_car_per_env), else the shared car's.
- *   - the applied action is (speed, steer + steer_noise[k][i]) with noise rows, else (speed, steer); from there the
- *     existing path: velocity clip, steering shift, steering clip, kinematics.
- *   - steer (BEFORE noise: the imitation-learning label, train_stanley_il.py:73) goes to steer_rows[k][i] and to
- *     steer_last[i].  A step that applies no action -- a TC_F_AUTORESET re-spawn, whose action is ignored as ever, or an env
- *     with TC_S_NOT_RESET, which is left alone -- stores 0.0 there.
- *   - the rows belong to tc_step_multi calls, like the episode rows: a tc_step neither reads steer_noise nor writes
- *     steer_rows (its command goes to steer_last only).
+ *   - the applied action is (speed, steer + steer_noise_in[k][i]) with a call's noise rows (tc_step_rows), else
+ *     (speed, steer); from there the existing path: velocity clip, steering shift, steering clip, kinematics.
+ *   - steer (BEFORE noise: the imitation-learning label, train_stanley_il.py:73) goes to the call's steer_out[k][i]
+ *     (tc_step_rows) and to steer_last[i].  A step that applies no action -- a TC_F_AUTORESET re-spawn, whose action is
+ *     ignored as ever, or an env with TC_S_NOT_RESET, which is left alone -- stores 0.0 there.
+ *   - a tc_step has no rows: its command goes to steer_last only.
  * k and speed sit in a library-owned device table updated in place (a captured graph sees new gains without re-capture;
- * a call that changes them waits for the device); the row pointers are kernel arguments of the launches enqueued
- * afterwards (a call that only changes them does not wait).  The kernels that run the controller are entry points of
- * their own chosen at launch (tc_drive_step_kernel, tc_drive_env_kernel, tc_drive_envg_kernel: the TC_FEAT_CTRL bit of
- * the feature mask); without a controller nothing changes.  c = NULL switches it off.
- * TC_E_INVALID: an unknown kind, non-finite k or speed, n_rows < 0, rows with n_rows = 0, and from a tc_step_multi call of
- * more than n_rows steps while either row pointer is set. */
+ * a call that changes them waits for the device, one that leaves them as they are does not).  The kernels that run the
+ * controller are entry points of their own chosen at launch (tc_drive_step_kernel, tc_drive_env_kernel,
+ * tc_drive_envg_kernel: the TC_FEAT_CTRL bit of the feature mask); without a controller nothing changes.  c = NULL
+ * switches it off.
+ * TC_E_INVALID: an unknown kind, non-finite k or speed. */
 #define TC_CTRL_STANLEY 1
 typedef struct {
-  int32_t kind;              /* TC_CTRL_STANLEY */
-  int32_t n_rows;            /* rows of steer_noise / steer_rows (0 when both are NULL) */
-  double k, speed;           /* gain; velocity command in [-1,1] units, also atan2's second argument (stanley_control.py:56) */
-  const double* steer_noise; /* device [n_rows][N] or NULL: added to the command of step k of a call */
-  double* steer_rows;        /* device [n_rows][N] or NULL, out: the command BEFORE noise (the IL label, train_stanley_il.py:73) */
-  double* steer_last;        /* device [N] or NULL, out: the same for the call's last step */
+  int32_t kind;       /* TC_CTRL_STANLEY */
+  double k, speed;    /* gain; velocity command in [-1,1] units, also atan2's second argument (stanley_control.py:56) */
+  double* steer_last; /* device [N] or NULL, out: the command BEFORE noise of the most recent step (the IL label, train_stanley_il.py:73) */
 } tc_controller;
 int tc_env_set_controller(tc_env* env, const tc_controller* c); /* NULL = off; drops the drive randomisation too */
 /* Drive randomisation: what examples/train_stanley_il.py and examples/train_td3.py do to the action at an episode boundary,
@@ -372,25 +362,25 @@ int tc_env_set_controller(tc_env* env, const tc_controller* c); /* NULL = off; d
  *                     z = SplitMix64(SplitMix64(seed)[0x6D616E])[(env_offset + i) << 32 | e]
  *       TC_MAN_CYCLE  maneuver[i] = maneuvers[(env_offset + i + e) % n_maneuvers]
  *     then episode[i] += 1; with ou_reset != 0, ou_state[i] = 0.0.  The re-spawn step applies no action: it consumes no
- *     normal, stores 0.0 in noise_rows and the NEW episode's maneuver in maneuver_rows.
+ *     normal, stores 0.0 in the call's ou_noise_out row and the NEW episode's maneuver in its maneuver_out row (tc_step_rows).
  *   - a step that applies an action: the maneuver is maneuver[i] when n_maneuvers > 0 (the `maneuver` argument of tc_step /
  *     tc_step_multi is then ignored and may be NULL), else the call's maneuver row as ever.  With OU noise:
  *       eps = normal number ou_draws[i] of env (env_offset + i) of the seed; ou_draws[i] = (ou_draws[i] + 1) mod 2^31
  *       n   = ou_state[i] + (theta * (mu - ou_state[i]) + sigma * eps); ou_state[i] = n
  *     (tinycarlo_amd/csrc/tc_rng.h: tc_normal_at -- Box-Muller on a sub-stream of its own -- and tc_ou_step) and the applied
- *     steering is steer + n, or (steer + steer_noise[k][i]) + n when the controller has noise rows.  steer_rows / steer_last
- *     keep the command before any noise; noise_rows[k][i] = n, maneuver_rows[k][i] = the maneuver used.
+ *     steering is steer + n, or (steer + steer_noise_in[k][i]) + n when the call has noise rows.  steer_out / steer_last
+ *     keep the command before any noise; ou_noise_out[k][i] = n, maneuver_out[k][i] = the maneuver used.
  *   - envs with TC_S_NOT_RESET are left alone: no draw, noise row 0.0.
  * All state lives in the caller's arrays between calls, so a K-step call is bit-identical to K tc_step calls and to any
- * split of the K steps.  The rows belong to tc_step_multi calls, like the steer rows.
+ * split of the K steps.
  * seed, env_offset, candidates, mode, theta, mu, sigma and ou_reset sit in a library-owned device table updated in place (a
- * captured graph sees new values without re-capture; a call that changes them waits for the device); the pointers are
+ * captured graph sees new values without re-capture; a call that changes them waits for the device, one that leaves them as
+ * they are does not); the pointers are
  * kernel arguments of the launches enqueued afterwards, and so is which of the two parts is on.  Runs in the tc_drive_*
  * entry points behind a run-time branch; while it is on, tc_reset takes them too.  d = NULL switches it off, and so does a
  * struct with neither part (n_maneuvers = 0 and ou_state = NULL).
  * TC_E_INVALID, before any device work: no controller installed, a maneuver outside 0..3, n_maneuvers outside 0..8, an
- * unknown mode, a non-finite theta / mu / sigma, n_maneuvers > 0 with a NULL maneuver or episode, ou_state without ou_draws,
- * n_rows < 0, rows with n_rows = 0, and from a tc_step_multi call of more than n_rows steps while a row pointer is set. */
+ * unknown mode, a non-finite theta / mu / sigma, n_maneuvers > 0 with a NULL maneuver or episode, ou_state without ou_draws. */
 #define TC_MAN_DRAW 0
 #define TC_MAN_CYCLE 1
 typedef struct {
@@ -405,9 +395,6 @@ typedef struct {
   int32_t* episode;       /* device [N], in/out: episodes drawn so far */
   double* ou_state;       /* device [N], in/out, or NULL: no OU noise */
   int32_t* ou_draws;      /* device [N], in/out: normals consumed so far (never reset; wraps at 2^31) */
-  int32_t* maneuver_rows; /* device [n_rows][N], out, or NULL */
-  double* noise_rows;     /* device [n_rows][N], out, or NULL */
-  int32_t n_rows;         /* rows of maneuver_rows / noise_rows (0 when both are NULL) */
 } tc_drive_randomization;
 int tc_env_set_drive_randomization(tc_env* env, const tc_drive_randomization* d); /* NULL = off */
 /* Normal number first_draw + j (mod 2^31) of env `env` (tc_normal_at of tc_rng.h) for j < n into out[j], on the host (no
@@ -543,8 +530,25 @@ typedef struct {
   int32_t* local_path;         /* [K][N][8] */
   int32_t* lp_len;             /* [K][N] */
 } tc_rollout;
+/* The per-step rows of a call's per-episode features: like the members of tc_rollout they are arguments of ONE tc_step_multi
+ * call, [n_rows][N] on the device, caller owned, each may be NULL, and step k of the call reads / writes row k.  n_rows is
+ * the one capacity of all of them.  The library keeps none of the pointers beyond the launches the call enqueues; tc_step
+ * and tc_reset have no rows.  `_in` is read, `_out` is written.  tc_step_multi returns TC_E_INVALID, before any device work
+ * and without allocating or waiting: for n_rows < 0, a pointer set with n_rows < 1, n_steps > n_rows while a pointer is set,
+ * steer_noise_in / steer_out without a controller, maneuver_out / ou_noise_out without drive randomisation,
+ * episode_*_out without episode buffers, camera_out without a camera bank. */
+typedef struct {
+  int32_t n_rows;
+  const double* steer_noise_in; /* tc_env_set_controller: added to the command of step k */
+  double* steer_out;            /* the command BEFORE any noise (the IL label, train_stanley_il.py:73) */
+  int32_t* maneuver_out;        /* tc_env_set_drive_randomization: the maneuver in force */
+  double* ou_noise_out;         /* the OU value applied */
+  int32_t* episode_length_out;  /* tc_env_set_episodes: length / ret after the step */
+  double* episode_return_out;
+  int32_t* camera_out;          /* tc_env_set_camera_bank: the camera index in force */
+} tc_step_rows;
 int tc_step_multi(tc_env* env, const void* car_control, int32_t control_dtype, const int32_t* maneuver, int32_t n_steps,
-                  uint32_t flags, const tc_rollout* rollout, void* stream);
+                  uint32_t flags, const tc_rollout* rollout, const tc_step_rows* rows /* may be NULL */, void* stream);
 
 /* Sizes the scratch of K-step calls that render observations, for calls of up to max_call_steps steps: per (step, env)
  * a pose row (128 B), a draw-list length and room for a draw list (20 B x lane-line edges of the map; only a frame's

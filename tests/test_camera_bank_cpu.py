@@ -143,15 +143,18 @@ def test_header_and_binding():
     from tinycarlo_amd import _native
     hdr = open(os.path.join(ROOT, "include", "tinycarlo_hip.h")).read()
     assert re.search(r"^#define TC_HAS_CAMERA_BANK 1$", hdr, re.M)
-    assert re.search(r"^#define TC_ABI_VERSION 6$", hdr, re.M) and _native.ABI_VERSION == 6
+    assert re.search(r"^#define TC_ABI_VERSION 7$", hdr, re.M) and _native.ABI_VERSION == 7
     assert re.search(r"^int tc_env_set_camera_bank\(tc_env\* env, const tc_camera_bank\* bank\);", hdr, re.M)
     assert "tc_env_set_camera_bank" in _native.EXPORTS and _native.HAS_CAMERA_BANK == 1
     L = _native.lib()
-    assert hasattr(L, "tc_env_set_camera_bank") and L.tc_abi_version() == 6
+    assert hasattr(L, "tc_env_set_camera_bank") and L.tc_abi_version() == 7
     import ctypes as C
-    # tc_camera_bank: 2 pointers, count + env_offset, seed, 3 pointers, n_rows padded to 8
-    assert C.sizeof(_native.CameraBankC) == 2 * 8 + 8 + 8 + 3 * 8 + 8
+    # tc_camera_bank: 2 pointers, count + env_offset, seed, 2 pointers (the index rows are the call's: tc_step_rows.camera_out)
+    assert C.sizeof(_native.CameraBankC) == 2 * 8 + 8 + 8 + 2 * 8
     assert _native.CameraBankC.seed.offset == 24 and _native.CameraBankC.index.offset == 32
+    assert _native.CameraBankC.episode.offset == 40 and [n for n, _ in _native.CameraBankC._fields_][-1] == "episode"
+    body = re.search(r"typedef struct \{([^}]*)\} tc_camera_bank;", hdr).group(1)
+    assert "rows" not in body and _native.StepRows.camera_out.offset == 7 * 8
 
 
 @pytest.mark.parametrize("kcode", cbr.KCODES)

@@ -121,7 +121,7 @@ def test_validation():
 def test_header_constants_match_the_binding():
     h = open(os.path.join(ROOT, "include", "tinycarlo_hip.h")).read()
     d = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define (TC_\w+) (-?\d+)\s", h, re.M)}
-    assert d["TC_ABI_VERSION"] == nat.ABI_VERSION == 6
+    assert d["TC_ABI_VERSION"] == nat.ABI_VERSION == 7
     assert d["TC_CAR_NP"] == nat.CAR_NP == len(nat.CAR_COLUMNS) == 8
     assert nat.CAR_COLUMNS == CAR_COLUMNS
     for j, name in enumerate(CAR_COLUMNS):

@@ -157,13 +157,13 @@ def test_header_declares_and_binding_lists_the_entry_points():
     h = open(os.path.join(ROOT, "include", "tinycarlo_hip.h")).read()
     assert "int tc_collect(" in h and "int64_t tc_collect_scratch_bytes(" in h
     assert "tc_collect" in nat.EXPORTS and "tc_collect_scratch_bytes" in nat.EXPORTS
-    assert re.search(r"#define TC_ABI_VERSION 6\b", h) and nat.ABI_VERSION == 6
+    assert re.search(r"#define TC_ABI_VERSION 7\b", h) and nat.ABI_VERSION == 7
     assert re.search(r"#define TC_HAS_COLLECT 1\b", h) and nat.HAS_COLLECT == 1
     for name, v in col.OVERFLOW.items():
         assert re.search(r"#define TC_COLLECT_%s %d\b" % (name.upper(), v), h)
     assert re.search(r"#define TC_COLLECT_MAX_COLUMNS %d\b" % col.MAX_COLUMNS, h)
     L = nat.lib()
-    assert L.tc_abi_version() == 6
+    assert L.tc_abi_version() == 7
     assert C.sizeof(col.CollectDescC) == 8 + 4 * 4 + 8 + 8 + 4 * 8 + 8 * 24 + 6 * 8
 
 

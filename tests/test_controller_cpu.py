@@ -24,9 +24,16 @@ extern "C" double stanley(double cte, double he, double k, double speed, double 
 extern "C" double shim_atan2(double y, double x) { return tc_atan2(y, x); }
 extern "C" int controller_sizeof(void) { return (int)sizeof(tc_controller); }
 extern "C" int controller_offset(int i) {
-  const size_t o[7] = {offsetof(tc_controller, kind), offsetof(tc_controller, n_rows), offsetof(tc_controller, k),
-                       offsetof(tc_controller, speed), offsetof(tc_controller, steer_noise), offsetof(tc_controller, steer_rows),
+  const size_t o[4] = {offsetof(tc_controller, kind), offsetof(tc_controller, k), offsetof(tc_controller, speed),
                        offsetof(tc_controller, steer_last)};
+  return (int)o[i];
+}
+extern "C" int step_rows_sizeof(void) { return (int)sizeof(tc_step_rows); }
+extern "C" int step_rows_offset(int i) {
+  const size_t o[8] = {offsetof(tc_step_rows, n_rows), offsetof(tc_step_rows, steer_noise_in), offsetof(tc_step_rows, steer_out),
+                       offsetof(tc_step_rows, maneuver_out), offsetof(tc_step_rows, ou_noise_out),
+                       offsetof(tc_step_rows, episode_length_out), offsetof(tc_step_rows, episode_return_out),
+                       offsetof(tc_step_rows, camera_out)};
   return (int)o[i];
 }
 """
@@ -53,30 +60,50 @@ def _header():
 def test_header_binding_and_library_agree():
     h = _header()
     d = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define (TC_\w+) (-?\d+)\s", h, re.M)}
-    assert d["TC_ABI_VERSION"] == nat.ABI_VERSION == 6  # additive: the ABI number does not move
+    assert d["TC_ABI_VERSION"] == nat.ABI_VERSION == 7
     assert d["TC_HAS_CONTROLLER"] == nat.HAS_CONTROLLER == 1
     assert d["TC_CTRL_STANLEY"] == nat.CTRL_STANLEY == 1
     assert re.search(r"\bint tc_env_set_controller\(tc_env\* env, const tc_controller\* c\);", h)
     assert "tc_env_set_controller" in nat.EXPORTS
     L = nat.lib()
-    assert hasattr(L, "tc_env_set_controller") and L.tc_abi_version() == 6
+    assert hasattr(L, "tc_env_set_controller") and L.tc_abi_version() == 7
     assert L.tc_env_set_controller(None, None) == -1  # TC_E_INVALID: refused before any device work
     # without a controller the action stays required
     assert L.tc_step(None, None, nat.F64, None, 0, None) == -1
-    assert L.tc_step_multi(None, None, nat.F64, None, 1, 0, None, None) == -1
+    assert L.tc_step_multi(None, None, nat.F64, None, 1, 0, None, None, None) == -1
+
+
+def _header_members(struct):
+    body = re.search(r"typedef struct \{([^}]*)\} %s;" % struct, _header()).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    return [re.sub(r"[\s*]", "", n) for f in body.split(";") if f.strip()
+            for n in re.sub(r"^\s*(const\s+)?\w+\s*\*?", "", f.strip()).split(",")]
 
 
 def test_struct_mirror_matches_the_header(shim):
-    assert C.sizeof(nat.ControllerC) == shim.controller_sizeof() == 48
+    assert C.sizeof(nat.ControllerC) == shim.controller_sizeof() == 32
     for i, (name, _) in enumerate(nat.ControllerC._fields_):
         assert getattr(nat.ControllerC, name).offset == shim.controller_offset(i), name
-    body = re.search(r"typedef struct \{([^}]*)\} tc_controller;", _header()).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [re.sub(r"[\s*]", "", n) for f in body.split(";") if f.strip()
-             for n in re.sub(r"^\s*(const\s+)?\w+\s*\*?", "", f.strip()).split(",")]
-    assert names == [n for n, _ in nat.ControllerC._fields_]
+    assert _header_members("tc_controller") == [n for n, _ in nat.ControllerC._fields_]
     # the structs out-of-tree callers were compiled against did not grow
     assert C.sizeof(nat.Buffers) == 23 * 8 + 8 and C.sizeof(nat.Rollout) == 15 * 8 and C.sizeof(nat.EpisodeBuffers) == 8 * 8
+
+
+def test_step_rows_mirror_matches_the_header(shim):
+    """tc_step_rows, the per-step feature rows of a tc_step_multi call: one n_rows and seven pointers, in / out in the names"""
+    assert C.sizeof(nat.StepRows) == shim.step_rows_sizeof() == 8 + 7 * 8
+    for i, (name, _) in enumerate(nat.StepRows._fields_):
+        assert getattr(nat.StepRows, name).offset == shim.step_rows_offset(i), name
+    names = _header_members("tc_step_rows")
+    assert names == [n for n, _ in nat.StepRows._fields_]
+    assert names[0] == "n_rows" and [n for n in names[1:] if n.endswith("_in")] == ["steer_noise_in"]
+    assert all(n.endswith("_out") for n in names[2:])
+    h = _header()
+    assert re.search(r"const tc_rollout\* rollout, const tc_step_rows\* rows[^,]*, void\* stream\);", h)
+    # nothing about rows is left on the handle: no setter struct has a row member, and the episode rows' setter is gone
+    for struct in ("tc_controller", "tc_drive_randomization", "tc_camera_bank", "tc_episode_buffers"):
+        assert not [n for n in _header_members(struct) if "rows" in n], struct
+    assert "episode_rollout" not in h and not [n for n in nat.EXPORTS if "rollout" in n]
 
 
 def test_stanley_law_bit_for_bit(shim):

@@ -16,7 +16,7 @@ from tinycarlo_amd import randomization as R
 
 CSRC = os.path.join(ROOT, "tinycarlo_amd", "csrc")
 FIELDS = ("seed", "env_offset", "n_maneuvers", "maneuvers", "maneuver_mode", "ou_reset", "theta", "mu", "sigma", "maneuver",
-          "episode", "ou_state", "ou_draws", "maneuver_rows", "noise_rows", "n_rows")
+          "episode", "ou_state", "ou_draws")
 
 SHIM = r"""
 #include <stddef.h>
@@ -37,14 +37,13 @@ extern "C" void shim_normals(unsigned long long seed, unsigned int env0, unsigne
 }
 extern "C" int drive_sizeof(void) { return (int)sizeof(tc_drive_randomization); }
 extern "C" int drive_offset(int i) {
-  const size_t o[16] = {offsetof(tc_drive_randomization, seed), offsetof(tc_drive_randomization, env_offset),
+  const size_t o[13] = {offsetof(tc_drive_randomization, seed), offsetof(tc_drive_randomization, env_offset),
                         offsetof(tc_drive_randomization, n_maneuvers), offsetof(tc_drive_randomization, maneuvers),
                         offsetof(tc_drive_randomization, maneuver_mode), offsetof(tc_drive_randomization, ou_reset),
                         offsetof(tc_drive_randomization, theta), offsetof(tc_drive_randomization, mu),
                         offsetof(tc_drive_randomization, sigma), offsetof(tc_drive_randomization, maneuver),
                         offsetof(tc_drive_randomization, episode), offsetof(tc_drive_randomization, ou_state),
-                        offsetof(tc_drive_randomization, ou_draws), offsetof(tc_drive_randomization, maneuver_rows),
-                        offsetof(tc_drive_randomization, noise_rows), offsetof(tc_drive_randomization, n_rows)};
+                        offsetof(tc_drive_randomization, ou_draws)};
   return (int)o[i];
 }
 """
@@ -85,19 +84,19 @@ def _header():
 def test_header_binding_and_library_agree():
     h = _header()
     d = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define (TC_\w+) (-?\d+)\s", h, re.M)}
-    assert d["TC_ABI_VERSION"] == nat.ABI_VERSION == 6  # additive: the ABI number does not move
+    assert d["TC_ABI_VERSION"] == nat.ABI_VERSION == 7
     assert d["TC_HAS_DRIVE_RANDOMIZATION"] == nat.HAS_DRIVE_RANDOMIZATION == 1
     assert (d["TC_MAN_DRAW"], d["TC_MAN_CYCLE"]) == (nat.MAN_DRAW, nat.MAN_CYCLE) == (0, 1)
     assert re.search(r"\bint tc_env_set_drive_randomization\(tc_env\* env, const tc_drive_randomization\* d\);", h)
     assert re.search(r"\bint tc_draw_normals\(uint64_t seed, uint32_t env, uint32_t first_draw, int32_t n, double\* out\);", h)
     assert "tc_env_set_drive_randomization" in nat.EXPORTS and "tc_draw_normals" in nat.EXPORTS
     L = nat.lib()
-    assert hasattr(L, "tc_env_set_drive_randomization") and hasattr(L, "tc_draw_normals") and L.tc_abi_version() == 6
+    assert hasattr(L, "tc_env_set_drive_randomization") and hasattr(L, "tc_draw_normals") and L.tc_abi_version() == 7
     assert L.tc_env_set_drive_randomization(None, None) == -1
 
 
 def test_struct_mirror_matches_the_header(shim):
-    assert C.sizeof(nat.DriveRandomizationC) == shim.drive_sizeof() == 136
+    assert C.sizeof(nat.DriveRandomizationC) == shim.drive_sizeof() == 112
     assert tuple(n for n, _ in nat.DriveRandomizationC._fields_) == FIELDS
     for i, name in enumerate(FIELDS):
         assert getattr(nat.DriveRandomizationC, name).offset == shim.drive_offset(i), name
@@ -107,7 +106,7 @@ def test_struct_mirror_matches_the_header(shim):
              for n in re.sub(r"^\s*(const\s+)?\w+\s*\*?", "", f.strip()).split(",")]
     assert tuple(names) == FIELDS
     # the structs out-of-tree callers were compiled against did not grow
-    assert C.sizeof(nat.ControllerC) == 48
+    assert C.sizeof(nat.ControllerC) == 32
     assert C.sizeof(nat.Buffers) == 23 * 8 + 8 and C.sizeof(nat.Rollout) == 15 * 8 and C.sizeof(nat.EpisodeBuffers) == 8 * 8
 
 
@@ -135,8 +134,7 @@ def test_bad_settings_are_refused_before_any_device_work():
            (drv(n_maneuvers=-1), b"0..8"), (drv(maneuver_mode=2), b"maneuver_mode"), (drv(maneuver_mode=-1), b"maneuver_mode"),
            (drv(theta=float("nan")), b"finite"), (drv(mu=float("inf")), b"finite"), (drv(sigma=float("-inf")), b"finite"),
            (drv(maneuver=None), b"maneuver and episode"), (drv(episode=None), b"maneuver and episode"),
-           (drv(ou_draws=None), b"ou_draws"), (drv(n_rows=-1), b"negative"), (drv(n_rows=0, maneuver_rows=ip), b"n_rows = 0"),
-           (drv(n_rows=0, noise_rows=dpp), b"n_rows = 0")]
+           (drv(ou_draws=None), b"ou_draws")]
     for c, why in bad:  # (refused for the struct's own sake, whatever the handle is: the message names the field)
         assert L.tc_env_set_drive_randomization(None, C.byref(c)) == -1
         assert why in L.tc_last_error(), (why, L.tc_last_error())
@@ -148,7 +146,12 @@ def test_bad_settings_are_refused_before_any_device_work():
     assert b"no env" in L.tc_last_error()
     # the maneuver argument stays required where no device maneuvers can be installed
     assert L.tc_step(None, None, nat.F64, None, 0, None) == -1
-    assert L.tc_step_multi(None, None, nat.F64, None, 1, 0, None, None) == -1
+    assert L.tc_step_multi(None, None, nat.F64, None, 1, 0, None, None, None) == -1
+    # the maneuver / OU rows are the call's (tc_step_rows): a bad struct is refused whatever the handle is, the message says why
+    for rows, why in ((nat.StepRows(n_rows=-1), b"negative"), (nat.StepRows(n_rows=0, maneuver_out=ip), b"n_rows = 0"),
+                      (nat.StepRows(n_rows=0, ou_noise_out=dpp), b"n_rows = 0")):
+        assert L.tc_step_multi(None, None, nat.F64, None, 1, 0, None, C.byref(rows), None) == -1
+        assert why in L.tc_last_error(), (why, L.tc_last_error())
     assert L.tc_draw_normals(0, 0, 0, -1, None) == -1 and L.tc_draw_normals(0, 0, 0, 1, None) == -1
     assert L.tc_draw_normals(0, 0, 0, 0, None) == 0
 

@@ -10,7 +10,7 @@ import pytest
 from common import HIPCC, ROOT, TC_FEAT_CAR, TC_FEAT_EP, assert_one_variant_set, dev_kernel_resources, kernel_variant
 from tinycarlo_amd import _native as nat
 
-NEW = ("tc_env_set_episodes", "tc_env_set_episode_rollout")
+NEW = ("tc_env_set_episodes",)
 
 
 def _header():
@@ -20,7 +20,7 @@ def _header():
 def test_header_binding_and_library_agree():
     h = _header()
     d = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define (TC_\w+) (-?\d+)\s", h, re.M)}
-    assert d["TC_ABI_VERSION"] == nat.ABI_VERSION == 6  # additive: the ABI number does not move
+    assert d["TC_ABI_VERSION"] == nat.ABI_VERSION == 7
     assert d["TC_HAS_EPISODES"] == nat.HAS_EPISODES == 1
     assert d["TC_S_TIME_LIMIT"] == nat.S_TIME_LIMIT == 32
     others = [v for k, v in d.items() if k.startswith("TC_S_") and k != "TC_S_TIME_LIMIT"]
@@ -28,7 +28,7 @@ def test_header_binding_and_library_agree():
     L = nat.lib()
     for f in NEW:
         assert f in nat.EXPORTS and re.search(r"\bint " + f + r"\(", h) and hasattr(L, f)
-    assert L.tc_abi_version() == 6
+    assert L.tc_abi_version() == 7
 
 
 def test_struct_size_equals_the_headers_field_count():
@@ -52,9 +52,17 @@ def test_argument_validation_needs_no_device():
     b = nat.EpisodeBuffers()  # length / ret missing: refused before the handle is looked at
     assert L.tc_env_set_episodes(None, C.byref(b), 10) == -1
     assert b"length and ret are required" in L.tc_last_error()
-    assert L.tc_env_set_episode_rollout(None, None, None, 0) == -1
-    assert L.tc_env_set_episode_rollout(None, None, None, -1) == -1
-    assert b"n_rows" in L.tc_last_error()
+    # the episode rows are arguments of the K-step call (tc_step_rows): NULL handle, and a bad n_rows whatever the handle is
+    dummy = C.c_void_p(256)  # (never dereferenced: the struct is refused first)
+
+    def multi(n_steps, **kw):
+        rows = nat.StepRows(**kw)
+        return L.tc_step_multi(None, None, nat.F64, None, n_steps, 0, None, C.byref(rows), None)
+    assert multi(1) == -1 and multi(1, n_rows=4, episode_length_out=dummy) == -1
+    assert multi(1, n_rows=-1) == -1 and b"n_rows" in L.tc_last_error()
+    for member in ("episode_length_out", "episode_return_out"):
+        assert multi(1, n_rows=0, **{member: dummy}) == -1 and b"n_rows = 0" in L.tc_last_error()
+        assert multi(5, n_rows=4, **{member: dummy}) == -1 and b"rows" in L.tc_last_error()
 
 
 def _host_env(n=4):

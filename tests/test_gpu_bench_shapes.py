@@ -233,11 +233,11 @@ def test_step_multi_without_ring_is_refused_and_never_allocates():
     roll = env.alloc_rollout(4, keys=("obs",))
     r = nat.Rollout()
     r.obs = roll["obs"].data_ptr()
-    rc = nat.lib().tc_step_multi(env._h, cc.data_ptr(), nat.F32, man.data_ptr(), 4, 0, C.byref(r), env._stream())
+    rc = nat.lib().tc_step_multi(env._h, cc.data_ptr(), nat.F32, man.data_ptr(), 4, 0, C.byref(r), None, env._stream())
     assert rc == -1 and b"tc_env_reserve_steps" in nat.lib().tc_last_error()
     assert nat.lib().tc_env_reserve_steps(env._h, 0) == -1
     assert nat.lib().tc_env_reserve_steps(env._h, 4) == 0
-    rc = nat.lib().tc_step_multi(env._h, cc.data_ptr(), nat.F32, man.data_ptr(), 4, 0, C.byref(r), env._stream())
+    rc = nat.lib().tc_step_multi(env._h, cc.data_ptr(), nat.F32, man.data_ptr(), 4, 0, C.byref(r), None, env._stream())
     assert rc == 0
     torch.cuda.synchronize()
     assert int(roll["obs"].max()) == 255

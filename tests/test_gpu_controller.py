@@ -256,9 +256,8 @@ def test_single_steps_after_a_drive_call_take_none_of_its_rows(ref):
     for key in fb:
         assert np.array_equal(bits(fa[key]), bits(fb[key])), ("step after drive", key)
     assert (a.steer_last.abs() > 1e-3).any()
-    # the C entry point itself: rows installed, tc_step still reads and writes none of them
+    # the C entry point itself: a call prepared with rows changes nothing on the handle, tc_step reads and writes none of them
     a.prepare_drive(man, rolls[0], torch.from_numpy(ref["noise"]).cuda())
-    assert a._ctrl_rows[0] and a._ctrl_rows[1]
     from tinycarlo_amd import _native as nat
     assert nat.lib().tc_step(a._h, None, nat.F64, man[3].data_ptr(), a._flags(), a._stream()) == 0
     b.drive_step(man[3])
@@ -266,8 +265,18 @@ def test_single_steps_after_a_drive_call_take_none_of_its_rows(ref):
     assert np.array_equal(bits(rolls[0]["steer"]), bits(before))
     for key in OUT_KEYS + ("obs",):
         assert np.array_equal(bits(a.out[key]), bits(b.out[key])), ("tc_step with rows installed", key)
-    a.set_controller(k=GAIN, speed=SPEED)  # new gains drop the rows of the earlier call
-    assert a._ctrl_rows == (0, 0, 0)
+    # the rows are a call's own: after drive call A (rollout A) and drive call B (rollout B), every tensor of A is bit-unchanged
+    noise = torch.from_numpy(ref["noise"]).cuda()
+    roll_a, roll_b = (a.alloc_rollout(K, keys=("reward", "cte", "steer")) for _ in range(2))
+    a.drive(man, rollout=roll_a, steer_noise=noise)
+    torch.cuda.synchronize()
+    kept = {key: t.clone() for key, t in roll_a.items()}
+    a.drive(man, rollout=roll_b, steer_noise=noise + 0.125)
+    a.drive_step(man[0])
+    torch.cuda.synchronize()
+    for key, t in roll_a.items():
+        assert np.array_equal(bits(t), bits(kept[key])), ("rollout of the earlier drive call written by a later one", key)
+    assert not np.array_equal(bits(roll_b["steer"]), bits(roll_a["steer"]))  # (B ran on from A's state: its own labels)
     a.close()
     b.close()
 
@@ -348,7 +357,7 @@ def test_controller_off_again_and_refusals(ref):
     for k in fb:
         assert np.array_equal(bits(fa[k]), bits(fb[k])), k
     # without a controller the action is required
-    assert L.tc_step_multi(a._h, None, nat.F64, man.data_ptr(), K, a._flags(), None, a._stream()) == -1
+    assert L.tc_step_multi(a._h, None, nat.F64, man.data_ptr(), K, a._flags(), None, None, a._stream()) == -1
     assert L.tc_step(a._h, None, nat.F64, man.data_ptr(), a._flags(), a._stream()) == -1
     with pytest.raises(RuntimeError):
         a.drive(man)
@@ -358,18 +367,27 @@ def test_controller_off_again_and_refusals(ref):
     last = torch.zeros(N, dtype=torch.float64, device="cuda:0")
     rows = torch.zeros((4, N), dtype=torch.float64, device="cuda:0")
 
-    def ctl(kind=nat.CTRL_STANLEY, n_rows=0, k=GAIN, speed=SPEED, noise=None, out=None):
-        return nat.ControllerC(kind, n_rows, k, speed, noise, out, last.data_ptr())
-    for bad in (ctl(kind=2), ctl(kind=0), ctl(k=float("nan")), ctl(k=float("inf")), ctl(speed=float("-inf")), ctl(n_rows=-1),
-                ctl(n_rows=0, out=rows.data_ptr())):
+    def ctl(kind=nat.CTRL_STANLEY, k=GAIN, speed=SPEED):
+        return nat.ControllerC(kind, k, speed, last.data_ptr())
+
+    def multi(n_steps, cc_ptr=None, **kw):  # tc_step_multi with the feature rows kw
+        sr = nat.StepRows(**kw)
+        return L.tc_step_multi(a._h, cc_ptr, nat.F64, man.data_ptr(), n_steps, a._flags() | nat.F_NO_OBSERVATION, None,
+                               C.byref(sr), a._stream())
+    for bad in (ctl(kind=2), ctl(kind=0), ctl(k=float("nan")), ctl(k=float("inf")), ctl(speed=float("-inf"))):
         assert L.tc_env_set_controller(a._h, C.byref(bad)) == -1
     assert a.launch_info(1)["kernel"] == "tc_step_kernel"  # a refused call installs nothing
-    for kw in ({"out": rows.data_ptr()}, {"noise": rows.data_ptr()}):
-        assert L.tc_env_set_controller(a._h, C.byref(ctl(n_rows=4, **kw))) == 0
-        assert L.tc_step_multi(a._h, None, nat.F64, man.data_ptr(), 5, a._flags() | nat.F_NO_OBSERVATION, None, a._stream()) == -1
-        assert b"rows" in L.tc_last_error()
-    assert L.tc_env_set_controller(a._h, C.byref(ctl())) == 0  # no rows: any length
-    assert L.tc_step_multi(a._h, None, nat.F64, man.data_ptr(), 5, a._flags() | nat.F_NO_OBSERVATION, None, a._stream()) == 0
+    # rows for a feature that is off: no controller, steer rows
+    for kw in ({"steer_out": rows.data_ptr()}, {"steer_noise_in": rows.data_ptr()}):
+        assert multi(4, cc.data_ptr(), n_rows=4, **kw) == -1 and b"rows without a controller" in L.tc_last_error()
+    assert L.tc_env_set_controller(a._h, C.byref(ctl())) == 0
+    # the rows' own refusals: negative n_rows, rows with n_rows = 0, a K-step call longer than n_rows
+    assert multi(4, n_rows=-1) == -1 and b"negative" in L.tc_last_error()
+    for kw in ({"steer_out": rows.data_ptr()}, {"steer_noise_in": rows.data_ptr()}):
+        assert multi(4, n_rows=0, **kw) == -1 and b"n_rows = 0" in L.tc_last_error()
+        assert multi(5, n_rows=4, **kw) == -1 and b"rows" in L.tc_last_error()
+    assert multi(5) == 0  # no rows: any length
+    assert L.tc_step_multi(a._h, None, nat.F64, man.data_ptr(), 5, a._flags() | nat.F_NO_OBSERVATION, None, None, a._stream()) == 0
     with pytest.raises(ValueError):
         a.set_controller(k=float("nan"))
     torch.cuda.synchronize()

@@ -536,20 +536,30 @@ def test_refusals_with_a_handle():
         for k, v in kw.items():
             setattr(c, k, v)
         return c
+    def multi(n_steps, **kw):  # tc_step_multi with the feature rows kw
+        sr = nat.StepRows(**kw)
+        return L.tc_step_multi(vec._h, None, nat.F64, None, n_steps, flags, None, C.byref(sr), vec._stream())
     assert L.tc_env_set_drive_randomization(vec._h, C.byref(drv())) == -1 and b"controller" in L.tc_last_error()
     with pytest.raises(ValueError):
         vec.randomize_drive(maneuvers=CAND)
     vec.set_controller(k=GAIN, speed=SPEED)
+    flags = vec._flags() | nat.F_NO_OBSERVATION
+    # rows for a feature that is off: a controller but no drive randomisation
+    for kw in ({"maneuver_out": rows.data_ptr()}, {"ou_noise_out": nrows.data_ptr()}):
+        sr = nat.StepRows(n_rows=4, **kw)
+        man4 = torch.zeros((4, N), dtype=torch.int32, device="cuda:0")
+        assert L.tc_step_multi(vec._h, None, nat.F64, man4.data_ptr(), 4, flags, None, C.byref(sr), vec._stream()) == -1
+        assert b"rows without drive randomisation" in L.tc_last_error()
     assert L.tc_env_set_drive_randomization(vec._h, C.byref(drv(maneuver_mode=7))) == -1
     assert vec.launch_info(1)["kernel"] == "tc_drive_step_kernel"
-    flags = vec._flags() | nat.F_NO_OBSERVATION
-    for kw in ({"maneuver_rows": rows.data_ptr()}, {"noise_rows": nrows.data_ptr()}):
-        assert L.tc_env_set_drive_randomization(vec._h, C.byref(drv(n_rows=4, **kw))) == 0
-        assert L.tc_step_multi(vec._h, None, nat.F64, None, 5, flags, None, vec._stream()) == -1
-        assert b"rows" in L.tc_last_error()
-        assert L.tc_step_multi(vec._h, None, nat.F64, None, 4, flags, None, vec._stream()) == 0
-    assert L.tc_env_set_drive_randomization(vec._h, C.byref(drv())) == 0  # no rows: any length, and no maneuver argument
-    assert L.tc_step_multi(vec._h, None, nat.F64, None, 5, flags, None, vec._stream()) == 0
+    assert L.tc_env_set_drive_randomization(vec._h, C.byref(drv())) == 0
+    for kw in ({"maneuver_out": rows.data_ptr()}, {"ou_noise_out": nrows.data_ptr()}):
+        assert multi(5, n_rows=4, **kw) == -1 and b"rows" in L.tc_last_error()  # a K-step call longer than n_rows
+        assert multi(4, n_rows=-1, **kw) == -1 and b"negative" in L.tc_last_error()
+        assert multi(4, n_rows=0, **kw) == -1 and b"n_rows = 0" in L.tc_last_error()
+        assert multi(4, n_rows=4, **kw) == 0
+    assert multi(5) == 0  # no rows: any length, and no maneuver argument
+    assert L.tc_step_multi(vec._h, None, nat.F64, None, 5, flags, None, None, vec._stream()) == 0
     assert L.tc_step(vec._h, None, nat.F64, None, flags, vec._stream()) == 0
     torch.cuda.synchronize()
     # (the envs under way keep maneuver 0 until they re-spawn, then take the one candidate; some action row carries noise)
@@ -557,7 +567,7 @@ def test_refusals_with_a_handle():
     assert int(dr_t.min()) > 0 and int(ep_t.max()) > 0
     # OU alone: the maneuver argument is required again
     assert L.tc_env_set_drive_randomization(vec._h, C.byref(drv(n_maneuvers=0))) == 0
-    assert L.tc_step_multi(vec._h, None, nat.F64, None, 5, flags, None, vec._stream()) == -1
+    assert L.tc_step_multi(vec._h, None, nat.F64, None, 5, flags, None, None, vec._stream()) == -1
     # a struct with neither part is "off": the maneuver argument is required, as after NULL
     assert L.tc_env_set_drive_randomization(vec._h, C.byref(drv())) == 0
     assert L.tc_env_set_drive_randomization(vec._h, C.byref(drv(n_maneuvers=0, ou_state=None))) == 0

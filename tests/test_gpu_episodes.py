@@ -398,20 +398,28 @@ def test_argument_validation_with_a_live_handle():
     env = make_env(8)
     L = nat.lib()
     rows = torch.zeros((4, 8), dtype=torch.int32, device="cuda:0")
-    assert L.tc_env_set_episode_rollout(env._h, rows.data_ptr(), None, 4) == -1  # rows without episode buffers
-    assert b"episode buffers" in L.tc_last_error()
-    env.track_episodes()
-    assert L.tc_env_set_episode_rollout(env._h, rows.data_ptr(), None, -1) == -1
-    assert L.tc_env_set_episode_rollout(env._h, rows.data_ptr(), None, 4) == 0
-    env.reset(seed=0)
     cc = torch.zeros((5, 8, 2), dtype=torch.float32, device="cuda:0")
     man = torch.zeros((5, 8), dtype=torch.int32, device="cuda:0")
-    rc = L.tc_step_multi(env._h, cc.data_ptr(), nat.F32, man.data_ptr(), 5, nat.F_NO_OBSERVATION, None, None)
-    assert rc == -1 and b"episode rows" in L.tc_last_error()  # a K-step call longer than n_rows
+
+    def multi(n_steps, **kw):  # tc_step_multi with the feature rows kw
+        sr = nat.StepRows(**kw)
+        return L.tc_step_multi(env._h, cc.data_ptr(), nat.F32, man.data_ptr(), n_steps, nat.F_NO_OBSERVATION, None, C.byref(sr), None)
+    env.reset(seed=0)
+    assert multi(4, n_rows=4, episode_length_out=rows.data_ptr()) == -1  # rows for a feature that is off
+    assert b"episode buffers" in L.tc_last_error()
+    env.track_episodes()
+    assert multi(4, n_rows=-1, episode_length_out=rows.data_ptr()) == -1
+    assert multi(4, n_rows=0, episode_length_out=rows.data_ptr()) == -1 and b"n_rows = 0" in L.tc_last_error()
+    assert multi(5, n_rows=4, episode_length_out=rows.data_ptr()) == -1 and b"rows" in L.tc_last_error()  # a K-step call longer than n_rows
+    torch.cuda.synchronize()
+    assert int(rows.abs().sum()) == 0 and int(env.episode_stats["length"].sum()) == 0  # a refused call writes nothing
+    assert multi(4, n_rows=4, episode_length_out=rows.data_ptr()) == 0
+    assert multi(5) == 0  # no rows: any length
+    torch.cuda.synchronize()
+    assert np.array_equal(rows.cpu().numpy(), np.tile(np.arange(1, 5, dtype=np.int32)[:, None], (1, 8)))
     b = nat.EpisodeBuffers()
     b.length = rows.data_ptr()
     assert L.tc_env_set_episodes(env._h, C.byref(b), 5) == -1  # ret missing
-    assert L.tc_env_set_episode_rollout(env._h, None, None, 0) == 0
     env.close()
 
 

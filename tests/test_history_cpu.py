@@ -189,11 +189,11 @@ def test_header_declares_and_binding_lists_the_entry_points(shim):
     from tinycarlo_amd import _native as nat
     h = open(os.path.join(ROOT, "include", "tinycarlo_hip.h")).read()
     assert re.search(r"#define TC_HAS_HISTORY 1\b", h) and nat.HAS_HISTORY == 1
-    assert re.search(r"#define TC_ABI_VERSION 6\b", h) and nat.ABI_VERSION == 6
+    assert re.search(r"#define TC_ABI_VERSION 7\b", h) and nat.ABI_VERSION == 7
     for name, v in col.PAD.items():
         assert re.search(r"#define TC_PAD_%s %d\b" % (name.upper(), v), h)
     L = nat.lib()
-    assert L.tc_abi_version() == 6
+    assert L.tc_abi_version() == 7
     for name in ("tc_collect_link", "tc_history_resolve", "tc_gather_frames"):
         assert re.search(r"\bint %s\(" % name, h), name
         assert name in nat.EXPORTS and hasattr(L, name), name

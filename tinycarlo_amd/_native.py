@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # TINYCARLO_HIP_LIB: load another build of the same library (tools/phase_clock.py uses the instrumented one)
 LIB_PATH = os.environ.get("TINYCARLO_HIP_LIB") or os.path.join(_HERE, "libtinycarlo_hip.so")
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 # per-env car parameter rows (tc_env_set_car_per_env): column order of TC_CAR_*
 CAR_NP = 8
 CAR_WHEELBASE, CAR_TRACK_WIDTH, CAR_MAX_VELOCITY, CAR_MAX_STEERING_ANGLE = 0, 1, 2, 3
@@ -48,7 +48,7 @@ PAD_ZERO, PAD_EDGE = 0, 1  # TC_PAD_*
 
 EXPORTS = ["tc_abi_version", "tc_last_error", "tc_map_create", "tc_map_destroy", "tc_env_create", "tc_env_destroy",
            "tc_env_bind", "tc_env_set_camera", "tc_env_set_camera_per_env", "tc_env_set_camera_bank", "tc_env_set_car", "tc_env_set_car_per_env",
-           "tc_env_set_car_randomization", "tc_env_set_episodes", "tc_env_set_episode_rollout", "tc_env_set_controller", "tc_env_set_drive_randomization", "tc_draw_normals", "tc_env_set_terms", "tc_env_set_spawn_table", "tc_env_set_noise", "tc_noise", "tc_env_obs_bytes", "tc_env_lds_bytes", "tc_env_profile",
+           "tc_env_set_car_randomization", "tc_env_set_episodes", "tc_env_set_controller", "tc_env_set_drive_randomization", "tc_draw_normals", "tc_env_set_terms", "tc_env_set_spawn_table", "tc_env_set_noise", "tc_noise", "tc_env_obs_bytes", "tc_env_lds_bytes", "tc_env_profile",
            "tc_env_profile_read", "tc_reset", "tc_step", "tc_step_multi", "tc_env_reserve_steps", "tc_env_launch_info", "tc_env_frame_lds_info", "tc_env_envg_lds_info", "tc_env_frame_bands", "tc_env_draw_list_stats", "tc_render",
            "tc_render_segments", "tc_unpack_bits", "tc_collect", "tc_collect_scratch_bytes",
            "tc_collect_link", "tc_history_resolve", "tc_gather_frames"]
@@ -92,21 +92,26 @@ class EpisodeBuffers(C.Structure):  # tc_episode_buffers: device arrays of N, le
                                           "return_sum", "limit")]
 
 
-class ControllerC(C.Structure):  # tc_controller: gains by value, the rows device arrays [n_rows][N] (steer_last [N]) or NULL
-    _fields_ = [("kind", C.c_int32), ("n_rows", C.c_int32), ("k", C.c_double), ("speed", C.c_double),
-                ("steer_noise", C.c_void_p), ("steer_rows", C.c_void_p), ("steer_last", C.c_void_p)]
+class StepRows(C.Structure):  # tc_step_rows: per-step feature rows of ONE tc_step_multi call, each [n_rows][N] or NULL
+    _fields_ = [("n_rows", C.c_int32), ("steer_noise_in", C.c_void_p), ("steer_out", C.c_void_p),
+                ("maneuver_out", C.c_void_p), ("ou_noise_out", C.c_void_p), ("episode_length_out", C.c_void_p),
+                ("episode_return_out", C.c_void_p), ("camera_out", C.c_void_p)]
 
 
-class DriveRandomizationC(C.Structure):  # tc_drive_randomization: settings by value; device arrays of N, rows [n_rows][N] or NULL
+class ControllerC(C.Structure):  # tc_controller: gains by value, steer_last a device array [N] or NULL
+    _fields_ = [("kind", C.c_int32), ("k", C.c_double), ("speed", C.c_double), ("steer_last", C.c_void_p)]
+
+
+class DriveRandomizationC(C.Structure):  # tc_drive_randomization: settings by value; device arrays of N
     _fields_ = [("seed", C.c_uint64), ("env_offset", C.c_uint32), ("n_maneuvers", C.c_int32), ("maneuvers", C.c_int32 * 8),
                 ("maneuver_mode", C.c_int32), ("ou_reset", C.c_int32), ("theta", C.c_double), ("mu", C.c_double),
                 ("sigma", C.c_double), ("maneuver", C.c_void_p), ("episode", C.c_void_p), ("ou_state", C.c_void_p),
-                ("ou_draws", C.c_void_p), ("maneuver_rows", C.c_void_p), ("noise_rows", C.c_void_p), ("n_rows", C.c_int32)]
+                ("ou_draws", C.c_void_p)]
 
 
-class CameraBankC(C.Structure):  # tc_camera_bank: device pointers; index / episode [N], index_rows [n_rows][N] or NULL
+class CameraBankC(C.Structure):  # tc_camera_bank: device pointers; index / episode [N]
     _fields_ = [("E", C.c_void_p), ("K", C.c_void_p), ("count", C.c_int32), ("env_offset", C.c_uint32), ("seed", C.c_uint64),
-                ("index", C.c_void_p), ("episode", C.c_void_p), ("index_rows", C.c_void_p), ("n_rows", C.c_int32)]
+                ("index", C.c_void_p), ("episode", C.c_void_p)]
 
 
 class TermC(C.Structure):  # tc_term
@@ -164,7 +169,6 @@ def lib():
     L.tc_env_set_car_per_env.argtypes = [C.c_void_p, C.c_void_p]
     L.tc_env_set_car_randomization.argtypes = [C.c_void_p, _dp, _dp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]
     L.tc_env_set_episodes.argtypes = [C.c_void_p, C.POINTER(EpisodeBuffers), C.c_int32]
-    L.tc_env_set_episode_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.tc_env_set_controller.argtypes = [C.c_void_p, C.POINTER(ControllerC)]
     L.tc_env_set_drive_randomization.argtypes = [C.c_void_p, C.POINTER(DriveRandomizationC)]
     L.tc_draw_normals.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, _dp]
@@ -181,7 +185,7 @@ def lib():
     L.tc_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.tc_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p]
     L.tc_step_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint32,
-                                C.POINTER(Rollout), C.c_void_p]
+                                C.POINTER(Rollout), C.POINTER(StepRows), C.c_void_p]
     L.tc_env_reserve_steps.argtypes = [C.c_void_p, C.c_int32]
     L.tc_env_draw_list_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int64)]

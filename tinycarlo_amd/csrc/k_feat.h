@@ -151,7 +151,7 @@ struct EpArgs {
   double* return_sum;
   const int* limit;      // [N] per-env limit, or NULL: *shared
   const int* shared;     // library owned, updated in place by tc_env_set_episodes (a captured graph sees a new limit)
-  int* len_rows;         // [K][N] rows of a K-step call (tc_env_set_episode_rollout), first row of this launch; or NULL
+  int* len_rows;         // [K][N] rows of a K-step call (tc_step_rows.episode_*_out), first row of this launch; or NULL
   double* ret_rows;
 };
 typedef const __attribute__((address_space(4))) int* EpIntConst;  // never written by a kernel: scalar load

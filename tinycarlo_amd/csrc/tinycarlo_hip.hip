@@ -439,24 +439,22 @@ struct tc_env {
   TcCullHead cull_head{};          // its header (tc_cull_cover reads it when the camera changes)
   CarRows cr{};          // per-env cars (tc_env_set_car_per_env / tc_env_set_car_randomization); rows NULL = shared car
   DevPtr<CarDrawTab> car_tab;  // device copy of the randomisation ranges (updated in place), or NULL
-  EpArgs ep{};           // episodes (tc_env_set_episodes / tc_env_set_episode_rollout); length NULL = feature off
+  // The features' kernel arguments as the handle holds them: the per-step row members of ep, ct, dr and cb stay NULL here,
+  // they are a call's (tc_step_rows: step_args_at() fills them)
+  EpArgs ep{};           // episodes (tc_env_set_episodes); length NULL = feature off
   DevPtr<int> ep_tab;    // device word holding max_episode_steps (updated in place), or NULL
-  int ep_rows = 0;       // rows of ep.len_rows / ep.ret_rows
   CtrlArgs ct{};         // built-in controller (tc_env_set_controller); tab NULL = off
   DevPtr<CtrlTab> ctrl_tab;  // device copy of the gains (updated in place), or NULL
   CtrlTab ctrl_host{};   // what ctrl_tab holds
-  int ctrl_rows = 0;     // rows of ct.noise / ct.rows
   DriveArgs dr{};        // drive randomisation (tc_env_set_drive_randomization); tab NULL = off
   DevPtr<DriveTab> drive_tab;  // device copy of the settings (updated in place), or NULL
   DriveTab drive_host{};  // what drive_tab holds
-  int drive_rows = 0;    // rows of dr.man_rows / dr.noise_rows
   unsigned drive_flags = 0;  // TC_FI_DRIVE_* of every launch while it is on
   bool terms_read_dist = false;  // an installed term reads lane-line distances (term_reads_distances; tc_env_set_terms)
   CamBank cb{};          // camera bank (tc_env_set_camera_bank); index NULL = off.  k.cam_E / k.cam_K then point to the bank
   DevPtr<CamDrawTab> cam_tab;  // device copy of the draw settings (updated in place), or NULL
   CamDrawTab cam_host{};       // what cam_tab holds
   int cam_count = 0;     // cameras in the bank (0 = off)
-  int cam_rows = 0;      // rows of cb.rows
   bool bound = false;
   int64_t obs_bytes = 0;
   int r_off_tab = 0, r_off_bits = 0, r_lds = 0;
@@ -1280,11 +1278,10 @@ extern "C" int tc_env_set_episodes(tc_env* e, const tc_episode_buffers* bufs, in
     return TC_E_INVALID;
   }
   if (!e) return TC_E_INVALID;
-  if (!bufs) {  // feature off: the per-step rows go with it
+  if (!bufs) {  // feature off
     const int* tab = e->ep_tab;
     memset(&e->ep, 0, sizeof(e->ep));
     e->ep.shared = tab;
-    e->ep_rows = 0;
     return TC_OK;
   }
   if (!e->ep_tab) HIP_TRY(e->ep_tab.alloc(1));
@@ -1304,34 +1301,11 @@ extern "C" int tc_env_set_episodes(tc_env* e, const tc_episode_buffers* bufs, in
   return TC_OK;
 }
 
-extern "C" int tc_env_set_episode_rollout(tc_env* e, int32_t* length_rows, double* return_rows, int32_t n_rows) {
-  if (n_rows < 0) {
-    set_err("tc_env_set_episode_rollout: n_rows must not be negative");
-    return TC_E_INVALID;
-  }
-  if (!e) return TC_E_INVALID;
-  const bool any = length_rows || return_rows;
-  if (any && !e->ep.length) {
-    set_err("tc_env_set_episode_rollout: no episode buffers installed (tc_env_set_episodes)");
-    return TC_E_INVALID;
-  }
-  if (any && n_rows < 1) {
-    set_err("tc_env_set_episode_rollout: rows given with n_rows = 0");
-    return TC_E_INVALID;
-  }
-  e->ep.len_rows = length_rows;
-  e->ep.ret_rows = return_rows;
-  e->ep_rows = any ? n_rows : 0;
-  return TC_OK;
-}
-
 extern "C" int tc_env_set_controller(tc_env* e, const tc_controller* c) {
   if (!e) return TC_E_INVALID;
   if (!c) {  // feature off (the table stays for a graph captured earlier); the drive randomisation goes with it
     memset(&e->ct, 0, sizeof(e->ct));
-    e->ctrl_rows = 0;
     memset(&e->dr, 0, sizeof(e->dr));
-    e->drive_rows = 0;
     e->drive_flags = 0;
     return TC_OK;
   }
@@ -1343,30 +1317,19 @@ extern "C" int tc_env_set_controller(tc_env* e, const tc_controller* c) {
     set_err("tc_env_set_controller: k and speed must be finite");
     return TC_E_INVALID;
   }
-  if (c->n_rows < 0) {
-    set_err("tc_env_set_controller: n_rows must not be negative");
-    return TC_E_INVALID;
-  }
-  if ((c->steer_noise || c->steer_rows) && c->n_rows < 1) {
-    set_err("tc_env_set_controller: rows given with n_rows = 0");
-    return TC_E_INVALID;
-  }
   const bool fresh_tab = !e->ctrl_tab;
   if (fresh_tab) HIP_TRY(e->ctrl_tab.alloc(1));
   const CtrlTab want = {c->k, c->speed};
   if (fresh_tab || memcmp(&want, &e->ctrl_host, sizeof(want)) != 0) {  // (bitwise: -0.0 is another speed than 0.0 to atan2)
     // (in place: a graph captured earlier keeps reading this table; the copy waits for launches that may still read it.
-    // A call that only changes the row pointers -- kernel arguments -- has nothing to wait for.)
+    // A call that leaves the gains as they are has nothing to wait for.)
     const CtrlTab t = want;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(e->ctrl_tab, &t, sizeof(t), hipMemcpyHostToDevice));
     e->ctrl_host = t;
   }
   e->ct.tab = e->ctrl_tab;
-  e->ct.noise = c->steer_noise;
-  e->ct.rows = c->steer_rows;
   e->ct.last = c->steer_last;
-  e->ctrl_rows = (c->steer_noise || c->steer_rows) ? c->n_rows : 0;
   return TC_OK;
 }
 
@@ -1374,7 +1337,6 @@ extern "C" int tc_env_set_drive_randomization(tc_env* e, const tc_drive_randomiz
   if (!d) {  // feature off (the table stays for a graph captured earlier)
     if (!e) return TC_E_INVALID;
     memset(&e->dr, 0, sizeof(e->dr));
-    e->drive_rows = 0;
     e->drive_flags = 0;
     return TC_OK;
   }
@@ -1404,14 +1366,6 @@ extern "C" int tc_env_set_drive_randomization(tc_env* e, const tc_drive_randomiz
     set_err("tc_env_set_drive_randomization: ou_state needs ou_draws");
     return TC_E_INVALID;
   }
-  if (d->n_rows < 0) {
-    set_err("tc_env_set_drive_randomization: n_rows must not be negative");
-    return TC_E_INVALID;
-  }
-  if ((d->maneuver_rows || d->noise_rows) && d->n_rows < 1) {
-    set_err("tc_env_set_drive_randomization: rows given with n_rows = 0");
-    return TC_E_INVALID;
-  }
   if (!e) {
     set_err("tc_env_set_drive_randomization: no env");
     return TC_E_INVALID;
@@ -1422,7 +1376,6 @@ extern "C" int tc_env_set_drive_randomization(tc_env* e, const tc_drive_randomiz
   }
   if (d->n_maneuvers == 0 && !d->ou_state) {  // neither part: off (no launch takes a drive entry point for nothing)
     memset(&e->dr, 0, sizeof(e->dr));
-    e->drive_rows = 0;
     e->drive_flags = 0;
     return TC_OK;
   }
@@ -1441,7 +1394,7 @@ extern "C" int tc_env_set_drive_randomization(tc_env* e, const tc_drive_randomiz
   if (fresh_tab) HIP_TRY(e->drive_tab.alloc(1));
   if (fresh_tab || memcmp(&want, &e->drive_host, sizeof(want)) != 0) {
     // (in place: a graph captured earlier keeps reading this table; the copy waits for launches that may still read it.
-    // A call that only changes the pointers -- kernel arguments -- has nothing to wait for.)
+    // A call that leaves the settings as they are has nothing to wait for.)
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(e->drive_tab, &want, sizeof(want), hipMemcpyHostToDevice));
     e->drive_host = want;
@@ -1451,9 +1404,6 @@ extern "C" int tc_env_set_drive_randomization(tc_env* e, const tc_drive_randomiz
   e->dr.episode = d->n_maneuvers > 0 ? d->episode : nullptr;
   e->dr.ou_state = d->ou_state;
   e->dr.ou_draws = d->ou_state ? d->ou_draws : nullptr;
-  e->dr.man_rows = d->maneuver_rows;
-  e->dr.noise_rows = d->noise_rows;
-  e->drive_rows = (d->maneuver_rows || d->noise_rows) ? d->n_rows : 0;
   e->drive_flags = (d->n_maneuvers > 0 ? TC_FI_DRIVE_MAN : 0u) | (d->ou_state ? TC_FI_DRIVE_OU : 0u);
   return TC_OK;
 }
@@ -1469,7 +1419,7 @@ extern "C" int tc_env_set_camera_per_env(tc_env* e, const double* E, const doubl
   e->k.cam_E = E;
   e->k.cam_K = K;
   memset(&e->cb, 0, sizeof(e->cb));  // (static rows and a bank exclude each other: installing one removes the other)
-  e->cam_count = e->cam_rows = 0;
+  e->cam_count = 0;
   cover_cull(e);  // (per-env cameras: the cull is off, its cover is the shared camera's)
   return TC_OK;
 }
@@ -1479,7 +1429,7 @@ extern "C" int tc_env_set_camera_bank(tc_env* e, const tc_camera_bank* b) {
   if (!b) {  // bank off: back to the shared camera (the table stays for a graph captured earlier)
     if (e->cb.index) e->k.cam_E = e->k.cam_K = nullptr;
     memset(&e->cb, 0, sizeof(e->cb));
-    e->cam_count = e->cam_rows = 0;
+    e->cam_count = 0;
     cover_cull(e);
     return TC_OK;
   }
@@ -1487,16 +1437,12 @@ extern "C" int tc_env_set_camera_bank(tc_env* e, const tc_camera_bank* b) {
     set_err("tc_env_set_camera_bank: E, K, index and episode are required, and count must be at least 1");
     return TC_E_INVALID;
   }
-  if (b->n_rows < 0 || (b->index_rows && b->n_rows < 1)) {
-    set_err("tc_env_set_camera_bank: index_rows need n_rows >= 1 (and n_rows must not be negative)");
-    return TC_E_INVALID;
-  }
   const CamDrawTab t = {b->seed, (unsigned int)b->count, b->env_offset};
   const bool fresh_tab = !e->cam_tab;
   if (fresh_tab) HIP_TRY(e->cam_tab.alloc(1));
   if (fresh_tab || memcmp(&t, &e->cam_host, sizeof(t)) != 0) {
     // (in place: a graph captured earlier keeps reading this table; the copy waits for launches that may still read it.
-    // A call that only changes pointers -- kernel arguments -- has nothing to wait for.)
+    // A call that leaves seed, count and env_offset as they are has nothing to wait for.)
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(e->cam_tab, &t, sizeof(t), hipMemcpyHostToDevice));
     e->cam_host = t;
@@ -1506,9 +1452,7 @@ extern "C" int tc_env_set_camera_bank(tc_env* e, const tc_camera_bank* b) {
   e->cb.index = b->index;
   e->cb.episode = b->episode;
   e->cb.tab = e->cam_tab;
-  e->cb.rows = b->index_rows;
   e->cam_count = b->count;
-  e->cam_rows = b->index_rows ? b->n_rows : 0;
   cover_cull(e);  // (a bank: the cull is off, as with per-env cameras)
   return TC_OK;
 }
@@ -1919,6 +1863,21 @@ static tc_rollout rollout_at(const tc_rollout& r, size_t r0, size_t obs_bytes, s
   return q;
 }
 
+// a call's feature rows from [step][env] row r0 on
+static tc_step_rows rows_at(const tc_step_rows& r, size_t r0) {
+  auto at = [r0](auto* p) { return p ? p + r0 : p; };
+  tc_step_rows q;
+  q.n_rows = r.n_rows;  // (of the whole call: checked by tc_step_multi, not read again)
+  q.steer_noise_in = at(r.steer_noise_in);
+  q.steer_out = at(r.steer_out);
+  q.maneuver_out = at(r.maneuver_out);
+  q.ou_noise_out = at(r.ou_noise_out);
+  q.episode_length_out = at(r.episode_length_out);
+  q.episode_return_out = at(r.episode_return_out);
+  q.camera_out = at(r.camera_out);
+  return q;
+}
+
 // One call of launch(): its arguments and what every route needs of them.
 struct Call {
   int mode;
@@ -1930,7 +1889,7 @@ struct Call {
   hipStream_t main;  // the caller's stream
   int nsteps;
   const tc_rollout* roll;
-  bool ep_rows;
+  const tc_step_rows* rows;  // the features' per-step rows (tc_step_multi), or NULL
   // per-env cars (tc_env_set_car_per_env) and episodes (tc_env_set_episodes): the instantiations of the simulate stages
   // with those bits, the same launches otherwise
   unsigned feat;
@@ -1943,31 +1902,31 @@ struct Call {
 };
 
 // What a simulate launch is given of the CALL, for the launch whose first step is step c0 of it: the handle's arguments
-// and feature rows, mode / dtype / flags, and the control, maneuver, rollout and episode rows from [step][env] row c0 * N
+// and features, mode / dtype / flags, and the control, maneuver, rollout and feature rows from [step][env] row c0 * N
 // on.  What belongs to the path is left to the caller: ma.nsteps and the members of ma behind it, the scratch a.seg_g /
 // a.seg_n point to, r, env_order.
 static StepArgs step_args_at(const tc_env* e, const Call& c, int c0) {
   const size_t r0 = (size_t)c0 * e->k.N;
-  const bool ep_rows = c.ep_rows;
+  const tc_step_rows fr = c.rows ? rows_at(*c.rows, r0) : tc_step_rows{};  // (tc_step, tc_reset: no rows)
   StepArgs sa;
   memset(&sa, 0, sizeof(sa));
   sa.a = e->k;
   sa.a.env0 = 0;
   sa.cr = e->cr;
-  sa.ep = e->ep;  // (the per-step rows belong to K-step calls only)
-  sa.ep.len_rows = ep_rows && e->ep.len_rows ? e->ep.len_rows + r0 : nullptr;
-  sa.ep.ret_rows = ep_rows && e->ep.ret_rows ? e->ep.ret_rows + r0 : nullptr;
-  sa.ct = e->ct;  // (the per-step rows belong to K-step calls only, like the episode rows: tc_step reads and writes none)
-  sa.ct.noise = ep_rows && e->ct.noise ? e->ct.noise + r0 : nullptr;
-  sa.ct.rows = ep_rows && e->ct.rows ? e->ct.rows + r0 : nullptr;
-  sa.cb = e->cb;  // (the index rows likewise)
-  sa.cb.rows = ep_rows && e->cb.index && e->cb.rows ? e->cb.rows + r0 : nullptr;
+  sa.ep = e->ep;
+  sa.ep.len_rows = fr.episode_length_out;
+  sa.ep.ret_rows = fr.episode_return_out;
+  sa.ct = e->ct;
+  sa.ct.noise = fr.steer_noise_in;
+  sa.ct.rows = fr.steer_out;
+  sa.cb = e->cb;
+  sa.cb.rows = fr.camera_out;
   if (c.roll) sa.ma.roll = rollout_at(*c.roll, r0, (size_t)e->obs_bytes, (size_t)e->k.m.C);
   sa.mode = c.mode;
   sa.cdtype = c.cdtype;
-  sa.dr = e->dr;  // (the rows likewise)
-  sa.dr.man_rows = ep_rows && e->dr.man_rows ? e->dr.man_rows + r0 : nullptr;
-  sa.dr.noise_rows = ep_rows && e->dr.noise_rows ? e->dr.noise_rows + r0 : nullptr;
+  sa.dr = e->dr;
+  sa.dr.man_rows = fr.maneuver_out;
+  sa.dr.noise_rows = fr.ou_noise_out;
   sa.flags = (c.flags & ~(TC_FI_CAM_BANK | TC_FI_DRIVE | TC_FI_INFO_EVERY)) | (e->cb.index ? TC_FI_CAM_BANK : 0u) |
              (e->dr.tab ? e->drive_flags : 0u) | (c.plan.info_every ? TC_FI_INFO_EVERY : 0u);
   sa.car_control = c.cc ? (const char*)c.cc + r0 * 2 * (c.cdtype == TC_F32 ? 4 : 8) : nullptr;  // (NULL: a controller acts)
@@ -2288,7 +2247,7 @@ static int launch_two(tc_env* e, const Call& c) {
 
 static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t* man, const int32_t* spawn,
                   const uint8_t* mask, uint32_t flags, void* stream, int nsteps = 1, const tc_rollout* roll = nullptr,
-                  bool ep_rows = false) {
+                  const tc_step_rows* rows = nullptr) {
   if (!e) return TC_E_INVALID;
   if (!e->bound) {
     set_err("tc_env_bind has not been called");
@@ -2310,7 +2269,7 @@ static int launch(tc_env* e, int mode, const void* cc, int cdtype, const int32_t
   // re-spawn draws the episode's maneuver)
   Call c;  // (filled by name: the order of the fields is free to change)
   c.mode = mode; c.cc = cc; c.cdtype = cdtype; c.man = man; c.spawn = spawn; c.mask = mask; c.flags = flags;
-  c.main = (hipStream_t)stream; c.nsteps = nsteps; c.roll = roll; c.ep_rows = ep_rows; c.feat = feat;
+  c.main = (hipStream_t)stream; c.nsteps = nsteps; c.roll = roll; c.rows = rows; c.feat = feat;
   c.all = roll && roll->obs;
   c.thick = e->k.cam.thickness > 1; c.fmt = e->k.cam.format;
   c.plan = plan_of(e, flags, nsteps, e->k.b.obs || c.all, c.all, roll);
@@ -2356,33 +2315,33 @@ extern "C" int tc_step(tc_env* e, const void* car_control, int32_t control_dtype
   return launch(e, MODE_STEP, car_control, control_dtype, maneuver, nullptr, nullptr, flags, stream);
 }
 
+// Why a call of n_steps steps cannot take these feature rows, or NULL when it can.  The struct's own faults come first:
+// they are refused whatever the handle is.
+static const char* rows_refusal(const tc_env* e, const tc_step_rows& r, int n_steps) {
+  const bool steer = r.steer_noise_in || r.steer_out, drive = r.maneuver_out || r.ou_noise_out;
+  const bool episode = r.episode_length_out || r.episode_return_out, any = steer || drive || episode || r.camera_out;
+  if (r.n_rows < 0) return "the rows' n_rows must not be negative";
+  if (any && r.n_rows < 1) return "rows given with n_rows = 0";
+  if (any && n_steps > r.n_rows) return "more steps than the call's rows hold (tc_step_rows.n_rows)";
+  if (!e) return nullptr;
+  if (steer && !e->ct.tab) return "steer rows without a controller (tc_env_set_controller)";
+  if (drive && !e->dr.tab) return "maneuver / OU noise rows without drive randomisation (tc_env_set_drive_randomization)";
+  if (episode && !e->ep.length) return "episode rows without episode buffers (tc_env_set_episodes)";
+  if (r.camera_out && !e->cb.index) return "camera rows without a camera bank (tc_env_set_camera_bank)";
+  return nullptr;
+}
+
 extern "C" int tc_step_multi(tc_env* e, const void* car_control, int32_t control_dtype, const int32_t* maneuver,
-                             int32_t n_steps, uint32_t flags, const tc_rollout* rollout, void* stream) {
+                             int32_t n_steps, uint32_t flags, const tc_rollout* rollout, const tc_step_rows* rows,
+                             void* stream) {
+  if (const char* why = rows ? rows_refusal(e, *rows, n_steps) : nullptr) {
+    set_err(std::string("tc_step_multi: ") + why);
+    return TC_E_INVALID;
+  }
   if (!e || (control_dtype != TC_F32 && control_dtype != TC_F64) || n_steps < 1) return TC_E_INVALID;
   if (!maneuver && !(e->dr.tab && (e->drive_flags & TC_FI_DRIVE_MAN))) return TC_E_INVALID;  // (device maneuvers replace it)
   if (!car_control && !e->ct.tab) return TC_E_INVALID;  // (a built-in controller replaces the action)
-  // (not left to launch(): the row checks below would answer first for an unbound handle whose rows are too short)
-  if (!e->bound) {
-    set_err("tc_env_bind has not been called");
-    return TC_E_UNBOUND;
-  }
-  if (e->ct.tab && (e->ct.noise || e->ct.rows) && n_steps > e->ctrl_rows) {
-    set_err("tc_step_multi: more steps than the controller's rows hold (tc_env_set_controller)");
-    return TC_E_INVALID;
-  }
-  if (e->dr.tab && (e->dr.man_rows || e->dr.noise_rows) && n_steps > e->drive_rows) {
-    set_err("tc_step_multi: more steps than the drive randomisation's rows hold (tc_env_set_drive_randomization)");
-    return TC_E_INVALID;
-  }
-  if (e->cb.index && e->cb.rows && n_steps > e->cam_rows) {
-    set_err("tc_step_multi: more steps than the camera index rows hold (tc_env_set_camera_bank)");
-    return TC_E_INVALID;
-  }
-  if ((e->ep.len_rows || e->ep.ret_rows) && n_steps > e->ep_rows) {
-    set_err("tc_step_multi: more steps than the episode rows hold (tc_env_set_episode_rollout)");
-    return TC_E_INVALID;
-  }
-  return launch(e, MODE_STEP, car_control, control_dtype, maneuver, nullptr, nullptr, flags, stream, n_steps, rollout, true);
+  return launch(e, MODE_STEP, car_control, control_dtype, maneuver, nullptr, nullptr, flags, stream, n_steps, rollout, rows);
 }
 
 // Workload descriptor for benchmark lines: what the most recent frames actually drew.  Waits for the device and copies

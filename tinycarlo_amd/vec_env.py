@@ -16,6 +16,7 @@ No CPU fallback exists: without the compiled library (or a GPU) construction rai
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import time
@@ -244,17 +245,13 @@ class TinyCarloVecEnv(gym.Env):
         self._episodes: Optional[Dict[str, torch.Tensor]] = None
         self._time_limit = 0                                   # shared max_episode_steps, 0 = none
         self._time_limit_per_env: Optional[torch.Tensor] = None  # [N] int32 device tensor, or None
-        self._ep_rows: Tuple[int, int] = (0, 0)                # data pointers of the episode rows installed last
-        # built-in controller (set_controller): its gains, or None = off; what the library holds of a call's rows
+        # built-in controller (set_controller): its gains, or None = off
         self._ctrl: Optional[Dict[str, float]] = None
-        self._ctrl_rows: Tuple[int, int, int] = (0, 0, 0)      # data pointers of the noise / steer rows installed last, rows
         self.steer_last: Optional[torch.Tensor] = None         # [N] f64: the controller's command of the last step
         # drive randomisation (randomize_drive): settings and the four live device tensors, or None = off
         self._drive: Optional[Dict[str, Any]] = None
-        self._drive_rows: Tuple[int, int, int] = (0, 0, 0)     # data pointers of the maneuver / noise rows installed last, rows
         # per-episode cameras (randomize_cameras): the bank's device tensors, settings and live index / episode, or None
         self._cam_bank: Optional[Dict[str, Any]] = None
-        self._cam_rows: Tuple[int, int] = (0, 0)               # data pointer and rows of the index rows installed last
         self._env_cams: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # static per-env E / K (set_env_cameras)
         self._setup_device()
         self._rngs: List[Optional[np.random.Generator]] = [None] * self.num_envs
@@ -365,7 +362,7 @@ class TinyCarloVecEnv(gym.Env):
         self._push_env_cameras(E, K)
 
     def _push_env_cameras(self, E, K) -> None:
-        self._cam_bank, self._cam_rows = None, (0, 0)  # (tc_env_set_camera_per_env removes a bank, whatever its arguments)
+        self._cam_bank = None  # (tc_env_set_camera_per_env removes a bank, whatever its arguments)
         if E is None:
             self._env_cams = None
             nat.check(nat.lib().tc_env_set_camera_per_env(self._h, None, None), "tc_env_set_camera_per_env")
@@ -392,22 +389,22 @@ class TinyCarloVecEnv(gym.Env):
         With no candidate list at all: back to the shared camera.  Removes the static rows of ``set_env_cameras``."""
         from .randomization import camera_bank
         if orientation is None and fov is None and position is None:
-            self._install_camera_bank(None)
+            self._set_camera_bank(None)
             return
         if not 0 <= int(env_offset) < 2 ** 32:
             raise ValueError("env_offset must be in [0, 2^32)")
         cfg = dict(self.config["camera"])
         cfg.update(orientation=list(self.camera.orientation), fov=self.camera.fov, position=list(self.camera.position))
         E, K, params = camera_bank(cfg, orientation=orientation, fov=fov, position=position)
-        self._install_camera_bank({"E": E, "K": K, "params": params, "seed": int(seed) & 0xFFFFFFFFFFFFFFFF,
+        self._set_camera_bank({"E": E, "K": K, "params": params, "seed": int(seed) & 0xFFFFFFFFFFFFFFFF,
                                    "env_offset": int(env_offset)})
 
-    def _install_camera_bank(self, bank: Optional[Dict[str, Any]], index=None, episode=None) -> None:
+    def _set_camera_bank(self, bank: Optional[Dict[str, Any]], index=None, episode=None) -> None:
         with torch.cuda.device(self.device):
             if bank is None:
                 if self._cam_bank is not None:
                     nat.check(nat.lib().tc_env_set_camera_bank(self._h, None), "tc_env_set_camera_bank")
-                self._cam_bank, self._cam_rows = None, (0, 0)
+                self._cam_bank = None
                 return
             E = torch.as_tensor(np.asarray(bank["E"], dtype=np.float64)).to(self.device).contiguous()
             K = torch.as_tensor(np.asarray(bank["K"], dtype=np.float64)).to(self.device).contiguous()
@@ -422,22 +419,14 @@ class TinyCarloVecEnv(gym.Env):
             self._cam_bank = {"E": E, "K": K, "params": np.array(bank["params"], dtype=np.float64), "seed": int(bank["seed"]),
                               "env_offset": int(bank["env_offset"]), "index": idx, "episode": ep}
             self._env_cams = None  # (the library drops the static rows)
-            self._push_camera_bank(0, 0)
+            self._push_camera_bank()
 
-    def _push_camera_bank(self, rows_ptr: int, n_rows: int) -> None:
+    def _push_camera_bank(self) -> None:
         b = self._cam_bank
         c = nat.CameraBankC(b["E"].data_ptr(), b["K"].data_ptr(), int(b["E"].shape[0]), b["env_offset"], b["seed"],
-                            b["index"].data_ptr(), b["episode"].data_ptr(), rows_ptr or None, n_rows if rows_ptr else 0)
+                            b["index"].data_ptr(), b["episode"].data_ptr())
         with torch.cuda.device(self.device):
             nat.check(nat.lib().tc_env_set_camera_bank(self._h, C.byref(c)), "tc_env_set_camera_bank")
-        self._cam_rows = (rows_ptr, n_rows if rows_ptr else 0)
-
-    def _install_camera_rows(self, rollout: Optional[Dict[str, torch.Tensor]], K: int) -> None:
-        """the index rows of the K-step call about to be issued (host-side bookkeeping only: the draw settings do not change)"""
-        t = rollout.get("camera") if rollout else None
-        want = (t.data_ptr(), K) if t is not None else (0, 0)
-        if want != self._cam_rows:
-            self._push_camera_bank(*want)
 
     @property
     def camera_index(self) -> Optional[torch.Tensor]:
@@ -493,11 +482,11 @@ class TinyCarloVecEnv(gym.Env):
                     max_steering_angle=max_steering_angle, steering_speed=steering_speed, max_acceleration=max_acceleration,
                     max_deceleration=max_deceleration, steering_shift=steering_shift)
         if all(v is None for v in vals.values()):
-            self._install_car_rows(None)
+            self._set_car_rows(None)
             return
-        self._install_car_rows(torch.as_tensor(car_rows(self.car_params, self.num_envs, vals), dtype=torch.float64))
+        self._set_car_rows(torch.as_tensor(car_rows(self.car_params, self.num_envs, vals), dtype=torch.float64))
 
-    def _install_car_rows(self, rows: Optional[torch.Tensor]) -> None:
+    def _set_car_rows(self, rows: Optional[torch.Tensor]) -> None:
         with torch.cuda.device(self.device):
             if rows is None:
                 nat.check(nat.lib().tc_env_set_car_per_env(self._h, None), "tc_env_set_car_per_env")
@@ -521,7 +510,7 @@ class TinyCarloVecEnv(gym.Env):
         if not 0 <= int(env_offset) < 2 ** 32:
             raise ValueError("env_offset must be in [0, 2^32)")
         if self._car_rows is None:
-            self._install_car_rows(torch.as_tensor(np.tile(config_row(self.car_params), (self.num_envs, 1))))
+            self._set_car_rows(torch.as_tensor(np.tile(config_row(self.car_params), (self.num_envs, 1))))
         with torch.cuda.device(self.device):
             if self._car_episode is None:
                 self._car_episode = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
@@ -554,7 +543,7 @@ class TinyCarloVecEnv(gym.Env):
             if self._episodes is not None:
                 with torch.cuda.device(self.device):
                     nat.check(nat.lib().tc_env_set_episodes(self._h, None, 0), "tc_env_set_episodes")
-            self._episodes, self._time_limit, self._time_limit_per_env, self._ep_rows = None, 0, None, (0, 0)
+            self._episodes, self._time_limit, self._time_limit_per_env = None, 0, None
             return
         if self._episodes is None:
             N, dev = self.num_envs, self.device
@@ -613,16 +602,6 @@ class TinyCarloVecEnv(gym.Env):
         ``length_sum`` / ``return_sum`` over all finished episodes of the env.  Sum them in torch for batch figures."""
         return self._episodes
 
-    def _install_episode_rows(self, rollout: Optional[Dict[str, torch.Tensor]], K: int) -> None:
-        """the per-step episode rows of the K-step call about to be issued (host-side bookkeeping only)"""
-        lt = rollout.get("episode_length") if rollout else None
-        rt = rollout.get("episode_return") if rollout else None
-        ptrs = (lt.data_ptr() if lt is not None else 0, rt.data_ptr() if rt is not None else 0)
-        if ptrs != self._ep_rows:
-            nat.check(nat.lib().tc_env_set_episode_rollout(self._h, ptrs[0] or None, ptrs[1] or None,
-                                                           K if (ptrs[0] or ptrs[1]) else 0), "tc_env_set_episode_rollout")
-            self._ep_rows = ptrs
-
     # ------------------------------------------------------------------ built-in controller (closed-loop K-step calls)
     CTRL_ROLLOUT_KEYS = ("steer",)
 
@@ -638,8 +617,8 @@ class TinyCarloVecEnv(gym.Env):
             if self._ctrl is not None:
                 with torch.cuda.device(self.device):
                     nat.check(nat.lib().tc_env_set_controller(self._h, None), "tc_env_set_controller")
-            self._ctrl, self._ctrl_rows, self.steer_last = None, (0, 0, 0), None
-            self._drive, self._drive_rows = None, (0, 0, 0)  # (the library drops the drive randomisation with the controller)
+            self._ctrl, self.steer_last = None, None
+            self._drive = None  # (the library drops the drive randomisation with the controller)
             return
         k, speed = float(k), float(speed)
         if not (np.isfinite(k) and np.isfinite(speed)):
@@ -647,23 +626,12 @@ class TinyCarloVecEnv(gym.Env):
         if self.steer_last is None:
             self.steer_last = torch.zeros(self.num_envs, dtype=torch.float64, device=self.device)
         self._ctrl = {"k": k, "speed": speed}
-        self._push_controller(0, 0, 0)  # (the rows belong to a call: the next drive / step_multi installs its own)
+        self._push_controller()
 
-    def _push_controller(self, noise_ptr: int, rows_ptr: int, n_rows: int) -> None:
-        c = nat.ControllerC(nat.CTRL_STANLEY, n_rows if (noise_ptr or rows_ptr) else 0, self._ctrl["k"], self._ctrl["speed"],
-                            noise_ptr or None, rows_ptr or None, self.steer_last.data_ptr())
+    def _push_controller(self) -> None:
+        c = nat.ControllerC(nat.CTRL_STANLEY, self._ctrl["k"], self._ctrl["speed"], self.steer_last.data_ptr())
         with torch.cuda.device(self.device):
             nat.check(nat.lib().tc_env_set_controller(self._h, C.byref(c)), "tc_env_set_controller")
-        self._ctrl_rows = (noise_ptr, rows_ptr, n_rows)
-
-    def _install_ctrl_rows(self, steer_noise: Optional[torch.Tensor], rollout: Optional[Dict[str, torch.Tensor]], K: int) -> None:
-        """the noise / label rows of the call about to be issued (host-side bookkeeping only: the gains do not change)"""
-        st = rollout.get("steer") if rollout else None
-        want = (steer_noise.data_ptr() if steer_noise is not None else 0, st.data_ptr() if st is not None else 0, K)
-        if not (want[0] or want[1]):
-            want = (0, 0, 0)
-        if want != self._ctrl_rows:
-            self._push_controller(*want)
 
     # ------------------------------------------------------------------ drive randomisation (per-episode maneuver, OU noise)
     DRIVE_ROLLOUT_KEYS = ("maneuver", "steer_noise")
@@ -684,7 +652,7 @@ class TinyCarloVecEnv(gym.Env):
             if self._drive is not None:
                 with torch.cuda.device(self.device):
                     nat.check(nat.lib().tc_env_set_drive_randomization(self._h, None), "tc_env_set_drive_randomization")
-            self._drive, self._drive_rows = None, (0, 0, 0)
+            self._drive = None
             return
         if self._ctrl is None:
             raise ValueError("randomize_drive() needs set_controller() first")
@@ -711,7 +679,7 @@ class TinyCarloVecEnv(gym.Env):
                        "env_offset": int(env_offset),
                        "maneuver": keep("maneuver", torch.int32), "episode": keep("episode", torch.int32),
                        "ou_state": keep("ou_state", torch.float64), "ou_draws": keep("ou_draws", torch.int32)}
-        self._push_drive(0, 0, 0)  # (the rows belong to a call: the next drive installs its own)
+        self._push_drive()
 
     def set_ou(self, theta: Optional[float] = None, mu: Optional[float] = None, sigma: Optional[float] = None,
                reset: Optional[bool] = None) -> None:
@@ -728,9 +696,9 @@ class TinyCarloVecEnv(gym.Env):
         if reset is not None:
             o["reset"] = bool(reset)
         self._drive["ou"] = o
-        self._push_drive(*self._drive_rows)
+        self._push_drive()
 
-    def _push_drive(self, man_ptr: int, noise_ptr: int, n_rows: int) -> None:
+    def _push_drive(self) -> None:
         d, c = self._drive, nat.DriveRandomizationC()
         c.seed, c.env_offset, c.n_maneuvers = d["seed"], d["env_offset"], len(d["maneuvers"])
         for i, m in enumerate(d["maneuvers"]):
@@ -742,21 +710,8 @@ class TinyCarloVecEnv(gym.Env):
             c.ou_state, c.ou_draws = d["ou_state"].data_ptr(), d["ou_draws"].data_ptr()
         if d["maneuvers"]:
             c.maneuver, c.episode = d["maneuver"].data_ptr(), d["episode"].data_ptr()
-        c.maneuver_rows, c.noise_rows = man_ptr or None, noise_ptr or None
-        c.n_rows = n_rows if (man_ptr or noise_ptr) else 0
         with torch.cuda.device(self.device):
             nat.check(nat.lib().tc_env_set_drive_randomization(self._h, C.byref(c)), "tc_env_set_drive_randomization")
-        self._drive_rows = (man_ptr, noise_ptr, n_rows)
-
-    def _install_drive_rows(self, rollout: Optional[Dict[str, torch.Tensor]], K: int) -> None:
-        """the maneuver / noise rows of the call about to be issued (host-side bookkeeping only: the settings do not change)"""
-        mr = rollout.get("maneuver") if rollout else None
-        nr = rollout.get("steer_noise") if rollout else None
-        want = (mr.data_ptr() if mr is not None else 0, nr.data_ptr() if nr is not None else 0, K)
-        if not (want[0] or want[1]):
-            want = (0, 0, 0)
-        if want != self._drive_rows:
-            self._push_drive(*want)
 
     @property
     def _device_maneuvers(self) -> bool:
@@ -795,8 +750,7 @@ class TinyCarloVecEnv(gym.Env):
 
     def prepare_drive(self, maneuver: Optional[torch.Tensor], rollout: Optional[Dict[str, torch.Tensor]] = None,
                       steer_noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None) -> "PreparedStepMulti":
-        """`drive` as a checked, reusable call object (see `prepare_step_multi`); its rows are installed at once, so the
-        object can be captured into a HIP graph right away."""
+        """`drive` as a checked, reusable call object (see `prepare_step_multi`)."""
         if self._ctrl is None:
             raise RuntimeError("drive() needs set_controller() first")
         if maneuver is None:
@@ -817,14 +771,10 @@ class TinyCarloVecEnv(gym.Env):
         if steer_noise is not None and (tuple(steer_noise.shape) != (K, self.num_envs) or steer_noise.dtype != torch.float64 or
                                         steer_noise.device != self.device or not steer_noise.is_contiguous()):
             raise ValueError(f"steer_noise must be a contiguous float64 tensor of shape ({K}, {self.num_envs}) on {self.device}")
-        r = self._check_rollout(rollout, K)
-        call = PreparedStepMulti(self, None, maneuver, rollout, r, K, steer_noise)
-        self._install_ctrl_rows(steer_noise, rollout, K)
-        if self._drive is not None:
-            self._install_drive_rows(rollout, K)
-        if self._cam_bank is not None:
-            self._install_camera_rows(rollout, K)
-        return call
+        r, rows = self._check_rollout(rollout, K)
+        if steer_noise is not None:
+            rows.steer_noise_in, rows.n_rows = steer_noise.data_ptr(), K
+        return PreparedStepMulti(self, None, maneuver, rollout, r, rows, K, steer_noise)
 
     def drive_step(self, maneuver: Optional[torch.Tensor] = None) -> None:
         """One closed-loop step (tc_step with the controller's action): `step_device` without a car_control."""
@@ -839,9 +789,6 @@ class TinyCarloVecEnv(gym.Env):
                 not maneuver.is_contiguous()):
             raise ValueError(f"drive_step takes a contiguous int32 device tensor of shape ({self.num_envs},) as maneuver")
         self._note_fresh()
-        self._install_ctrl_rows(None, None, 0)
-        if self._drive is not None:
-            self._install_drive_rows(None, 0)
         with torch.cuda.device(self.device):
             nat.check(nat.lib().tc_step(self._h, None, nat.F64, maneuver.data_ptr() if maneuver is not None else None,
                                         self._flags(), self._stream()), "tc_step")
@@ -1059,10 +1006,6 @@ class TinyCarloVecEnv(gym.Env):
         if not self._was_reset:
             raise RuntimeError("step() before reset()")
         self._note_fresh()
-        if self._ctrl is not None:  # (a controller acts: the rows of an earlier drive call are not this step's)
-            self._install_ctrl_rows(None, None, 0)
-            if self._drive is not None:
-                self._install_drive_rows(None, 0)
         dt = nat.F64 if car_control.dtype == torch.float64 else nat.F32
         with torch.cuda.device(self.device):
             nat.check(nat.lib().tc_step(self._h, car_control.data_ptr(), dt, maneuver.data_ptr(), self._flags(),
@@ -1172,14 +1115,21 @@ class TinyCarloVecEnv(gym.Env):
             raise ValueError("car_control must be float32|float64 and maneuver int32")
         if not (car_control.is_contiguous() and maneuver.is_contiguous()):
             raise ValueError("step_multi takes contiguous tensors")
-        call = PreparedStepMulti(self, car_control, maneuver, rollout, self._check_rollout(rollout, K), K)
-        if self._cam_bank is not None:  # (installed at once, so the object can be captured into a HIP graph right away)
-            self._install_camera_rows(rollout, K)
-        return call
+        r, rows = self._check_rollout(rollout, K)
+        return PreparedStepMulti(self, car_control, maneuver, rollout, r, rows, K)
 
-    def _check_rollout(self, rollout: Optional[Dict[str, torch.Tensor]], K: int) -> "nat.Rollout":
-        """the tc_rollout of a K-step call from its checked tensors; sizes the library's scratch for the call"""
-        r = nat.Rollout()
+    # the rollout keys that are feature rows of the call (tc_step_rows) and no members of tc_rollout: the member, the
+    # attribute that is None while the feature is off, and what switches it on
+    _STEP_ROWS = {"episode_length": ("episode_length_out", "_episodes", "track_episodes() / set_time_limit()"),
+                  "episode_return": ("episode_return_out", "_episodes", "track_episodes() / set_time_limit()"),
+                  "steer": ("steer_out", "_ctrl", "set_controller()"),
+                  "camera": ("camera_out", "_cam_bank", "randomize_cameras()"),
+                  "maneuver": ("maneuver_out", "_drive", "randomize_drive()"),
+                  "steer_noise": ("ou_noise_out", "_drive", "randomize_drive()")}  # (the OU value applied, an output)
+
+    def _check_rollout(self, rollout: Optional[Dict[str, torch.Tensor]], K: int) -> Tuple["nat.Rollout", "nat.StepRows"]:
+        """the tc_rollout and tc_step_rows of a K-step call from its checked tensors; sizes the library's scratch for the call"""
+        r, rows = nat.Rollout(), nat.StepRows()
         if rollout:
             want = self._shape_cache.get(K)
             if want is None:
@@ -1190,26 +1140,17 @@ class TinyCarloVecEnv(gym.Env):
                 shp, dt_ = want[k]
                 if t.dtype != dt_ or tuple(t.shape) != shp or t.device != self.device or not t.is_contiguous():
                     raise ValueError(f"rollout[{k!r}] must be a contiguous {dt_} tensor of shape {shp} on {self.device}")
-                if k in self.EPISODE_ROLLOUT_KEYS:  # not part of tc_rollout: installed per call (tc_env_set_episode_rollout)
-                    if self._episodes is None:
-                        raise ValueError(f"rollout[{k!r}] needs track_episodes() / set_time_limit() first")
-                    continue
-                if k in self.CTRL_ROLLOUT_KEYS:  # likewise: installed per call (tc_env_set_controller)
-                    if self._ctrl is None:
-                        raise ValueError(f"rollout[{k!r}] needs set_controller() first")
-                    continue
-                if k in self.CAMERA_ROLLOUT_KEYS:  # likewise: installed per call (tc_env_set_camera_bank)
-                    if self._cam_bank is None:
-                        raise ValueError(f"rollout[{k!r}] needs randomize_cameras() first")
-                    continue
-                if k in self.DRIVE_ROLLOUT_KEYS:  # likewise: installed per call (tc_env_set_drive_randomization)
-                    if self._drive is None:
-                        raise ValueError(f"rollout[{k!r}] needs randomize_drive() first")
+                if k in self._STEP_ROWS:
+                    member, feature, switch = self._STEP_ROWS[k]
+                    if getattr(self, feature) is None:
+                        raise ValueError(f"rollout[{k!r}] needs {switch} first")
+                    setattr(rows, member, t.data_ptr())
+                    rows.n_rows = K
                     continue
                 setattr(r, k, t.data_ptr())
         if K > 1 and not (self.no_observation and self.render_mode is None):
             self.reserve_steps(K)  # (no-op once the scratch covers K: the call itself never allocates)
-        return r
+        return r, rows
 
     def launch_info(self, n_steps: int = 1) -> Dict[str, Any]:
         """What a call of n_steps steps launches with the current settings (tc_env_launch_info): for benchmark labels."""
@@ -1306,12 +1247,12 @@ class TinyCarloVecEnv(gym.Env):
         cpe = sd.get("car_per_env")
         if cpe is None:
             if self._car_rows is not None:
-                self._install_car_rows(None)
+                self._set_car_rows(None)
         else:
             rows = cpe["rows"]
             if tuple(rows.shape) != (self.num_envs, nat.CAR_NP):
                 raise ValueError(f"car_per_env rows: shape {tuple(rows.shape)} does not fit ({self.num_envs}, {nat.CAR_NP})")
-            self._install_car_rows(rows)
+            self._set_car_rows(rows)
             rnd = cpe.get("randomization")
             if rnd is not None:
                 self.randomize_cars(None)  # (allocates the counters)
@@ -1344,9 +1285,9 @@ class TinyCarloVecEnv(gym.Env):
         bank = sd.get("camera_bank")  # (present only when a bank was installed)
         if bank is None:
             if self._cam_bank is not None:
-                self._install_camera_bank(None)
+                self._set_camera_bank(None)
         else:
-            self._install_camera_bank({"E": bank["E"].numpy(), "K": bank["K"].numpy(), "params": bank["params"],
+            self._set_camera_bank({"E": bank["E"].numpy(), "K": bank["K"].numpy(), "params": bank["params"],
                                        "seed": bank["seed"], "env_offset": bank["env_offset"]},
                                       index=bank["index"], episode=bank["episode"])
         self._step_serial += 1
@@ -1438,18 +1379,18 @@ class PreparedStepMulti:
     """A checked `step_multi` call (`TinyCarloVecEnv.prepare_step_multi`): calling it enqueues tc_step_multi with the
     tensors it was prepared with, on the stream current at that moment."""
 
-    __slots__ = ("env", "_keep", "_args", "_rollout_ref", "K", "_noise")
+    __slots__ = ("env", "_keep", "_args", "_structs", "K")
 
-    def __init__(self, env, car_control, maneuver, rollout, r, K, steer_noise=None):
+    def __init__(self, env, car_control, maneuver, rollout, r, rows, K, steer_noise=None):
         self.env = env
         self.K = K
-        self._keep = (car_control, maneuver, rollout)   # the tensors stay alive as long as the call can be issued
-        self._noise = steer_noise                       # `prepare_drive`: the controller's noise rows (car_control None)
-        self._rollout_ref = r
+        # the tensors stay alive as long as the call can be issued (steer_noise: `prepare_drive`'s noise rows, car_control None)
+        self._keep = (car_control, maneuver, rollout, steer_noise)
+        self._structs = (r, rows)  # the tc_rollout and tc_step_rows _args points to
         dt = nat.F32 if car_control is not None and car_control.dtype == torch.float32 else nat.F64
         self._args = (car_control.data_ptr() if car_control is not None else None, dt,
                       maneuver.data_ptr() if maneuver is not None else None, K,
-                      C.byref(r) if rollout else None)
+                      C.byref(r) if rollout else None, C.byref(rows) if rows.n_rows else None)
 
     def __call__(self) -> None:
         env = self.env
@@ -1463,26 +1404,15 @@ class PreparedStepMulti:
             t_dbg = time.perf_counter()
             env.profile(1)
         a = self._args
-        if env._episodes is not None:
-            env._install_episode_rows(self._keep[2], self.K)
-        if env._ctrl is not None:
-            env._install_ctrl_rows(self._noise, self._keep[2], self.K)
-            if env._drive is not None:
-                env._install_drive_rows(self._keep[2], self.K)
-        elif a[0] is None:
+        if a[0] is None and env._ctrl is None:
             raise RuntimeError("a drive() call needs the controller it was prepared with (set_controller)")
         if a[2] is None and not env._device_maneuvers:
             raise RuntimeError("a drive(maneuver=None) call needs the device maneuvers it was prepared with (randomize_drive)")
-        if env._cam_bank is not None:
-            env._install_camera_rows(self._keep[2], self.K)
-        if torch.cuda.current_device() == env.device.index:
-            rc = nat.lib().tc_step_multi(env._h, a[0], a[1], a[2], a[3], env._flags(), a[4], env._stream())
-        else:
-            with torch.cuda.device(env.device):
-                rc = nat.lib().tc_step_multi(env._h, a[0], a[1], a[2], a[3], env._flags(), a[4], env._stream())
+        with contextlib.nullcontext() if torch.cuda.current_device() == env.device.index else torch.cuda.device(env.device):
+            rc = nat.lib().tc_step_multi(env._h, *a[:4], env._flags(), a[4], a[5], env._stream())
         if rc != 0:
             nat.check(rc, "tc_step_multi")
-        env._keep = self._keep + (self._noise,)  # (the library holds their pointers until the next call installs its own)
+        env._keep = self._keep  # (the launches just enqueued read and write them; the library keeps none of their pointers)
         env._step_serial += 1
         if dbg:
             env._debug_print(f"step_multi[{self.K}]", t_dbg)
