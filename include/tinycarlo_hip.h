@@ -65,6 +65,8 @@ extern "C" {
 #define TC_HAS_COLLECT 1
 /* Likewise additive within ABI 6: tc_collect_link, tc_history_resolve, tc_gather_frames, TC_PAD_*. */
 #define TC_HAS_HISTORY 1
+/* Additive within ABI 7: tc_env_reserve_poses, tc_render_poses (deferred frames). */
+#define TC_HAS_RENDER_POSES 1
 #define TC_MAX_LAYERS 16
 
 /* error codes */
@@ -610,6 +612,43 @@ int tc_render_segments(tc_env* env, const int32_t* segments, const int32_t* coun
 
 /* Re-render the observation of the current state without stepping (Camera.capture_frame, camera.py:52). */
 int tc_render(tc_env* env, uint32_t flags, void* stream);
+
+/* Deferred frames: observations drawn from STORED poses, without the simulate stage and without touching the env.  A frame
+ * depends on the env's state only through (x, y, theta) and the camera, so the x / y / theta rows of a rollout (28 bytes per
+ * step with a camera index) are enough to draw any step's frame later -- only the rows a learner keeps, a replay sample, a
+ * handful of envs of a long call -- bit for bit what the call that produced the poses drew or would have drawn.
+ *
+ * tc_render_poses draws n_frames frames with the handle's own camera settings (resolution, format, thickness, max_range,
+ * packing); output frame m is at out + m * tc_env_obs_bytes and is what Camera.capture_frame (camera.py:52) gives for a car
+ * at element j = index ? index[m] : m of the arrays.  x, y, theta and camera are device arrays of n_src elements -- for
+ * instance the [K][N] rows of a tc_rollout --, index a device int64 array of n_frames elements (repeats and any order
+ * allowed) or NULL, then n_frames <= n_src.  An index outside [0, n_src) is clamped into it and a camera value into the
+ * camera rows: nothing is read or written out of bounds whatever the integers hold.
+ *   camera: NULL on a handle with the one shared camera; required on a handle with per-env cameras
+ *     (tc_env_set_camera_per_env), where it is the env whose camera the frame takes; required on a handle with a camera bank
+ *     (tc_env_set_camera_bank), where it is the bank index: the camera_out rows of the call that produced the poses.
+ *   noise: the fused observation noise of tc_env_set_noise is NOT applied -- a deferred frame has no place in the blob stream.
+ * Everything is enqueued on `stream`, in stream order, into a scratch of the call's own: the bound obs tensor, the env's
+ * state, the noise counter, the profile ring, the scratch of K-step calls and what tc_env_draw_list_stats reports are not
+ * touched (also on handles without a frame kernel, whose frames are drawn by the simulate kernel's camera stage in its render
+ * mode with tc_raster_kernel behind it, in rounds of N frames -- those handles must be bound), and every later call on the
+ * handle gives bit for bit what it would have given without the render.  Renders on one handle share that scratch: the caller
+ * keeps them in one stream's order (one stream, or its own events).  After tc_env_reserve_poses the call neither allocates nor synchronises and can be
+ * captured into a HIP graph; without a reservation it returns TC_E_INVALID (tc_last_error names tc_env_reserve_poses), the rule
+ * tc_step_multi has for tc_env_reserve_steps.  n_frames == 0 is TC_OK without a launch.
+ * TC_E_INVALID before any HIP call: NULL env / x / y / theta / out, n_src < 1, n_frames < 0, index == NULL with
+ * n_frames > n_src, camera given on a shared-camera handle or missing on the other two kinds, a misaligned pointer (out: 16
+ * bytes, as the obs rows of a rollout; x, y, theta, index: 8; camera: 4).
+ *
+ * tc_env_reserve_poses sizes that scratch for launches of up to max_frames frames; a longer list runs as several launches
+ * one after the other.  Per frame: a pose row (128 B), a draw-list length (4 B) and room for a draw list (20 B x lane-line
+ * edges of the map; only a frame's overflow beyond the LDS-resident head travels through it) -- simple_layout 5.4 KB,
+ * knuffingen 15 KB --, cut to the budget TC_STREAM_SCRATCH_MB.  Handles without a frame kernel keep N draw lists and N
+ * gathered poses whatever max_frames is.  Waits for the device only when it has to re-allocate; a request the scratch already
+ * covers returns at once.  max_frames < 1 is TC_E_INVALID. */
+int tc_env_reserve_poses(tc_env* env, int64_t max_frames);
+int tc_render_poses(tc_env* env, const double* x, const double* y, const double* theta, const int32_t* camera,
+                    const int64_t* index, int64_t n_src, int64_t n_frames, uint8_t* out, void* stream);
 
 /* Expands bit-packed class masks (TC_FMT_CLASSES_BITS) on the device; needs no env handle.  A "frame" is planes*H*W/8 packed
  * bytes -- the rows of a [K][N] rollout are simply K*N frames.  dst: [n_out][planes][H][W] of dst_dtype: TC_U8 gives 0 / 255,

@@ -45,13 +45,14 @@ HAS_COLLECT = 1  # TC_HAS_COLLECT: likewise (tc_collect; its descriptor is mirro
 
 HAS_HISTORY = 1  # TC_HAS_HISTORY: likewise (tc_collect_link, tc_history_resolve, tc_gather_frames; tinycarlo_amd/collect.py)
 PAD_ZERO, PAD_EDGE = 0, 1  # TC_PAD_*
+HAS_RENDER_POSES = 1  # TC_HAS_RENDER_POSES: additive within ABI 7 (tc_env_reserve_poses, tc_render_poses)
 
 EXPORTS = ["tc_abi_version", "tc_last_error", "tc_map_create", "tc_map_destroy", "tc_env_create", "tc_env_destroy",
            "tc_env_bind", "tc_env_set_camera", "tc_env_set_camera_per_env", "tc_env_set_camera_bank", "tc_env_set_car", "tc_env_set_car_per_env",
            "tc_env_set_car_randomization", "tc_env_set_episodes", "tc_env_set_controller", "tc_env_set_drive_randomization", "tc_draw_normals", "tc_env_set_terms", "tc_env_set_spawn_table", "tc_env_set_noise", "tc_noise", "tc_env_obs_bytes", "tc_env_lds_bytes", "tc_env_profile",
            "tc_env_profile_read", "tc_reset", "tc_step", "tc_step_multi", "tc_env_reserve_steps", "tc_env_launch_info", "tc_env_frame_lds_info", "tc_env_envg_lds_info", "tc_env_frame_bands", "tc_env_draw_list_stats", "tc_render",
            "tc_render_segments", "tc_unpack_bits", "tc_collect", "tc_collect_scratch_bytes",
-           "tc_collect_link", "tc_history_resolve", "tc_gather_frames"]
+           "tc_collect_link", "tc_history_resolve", "tc_gather_frames", "tc_env_reserve_poses", "tc_render_poses"]
 
 _dp, _ip, _bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
 
@@ -206,6 +207,9 @@ def lib():
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.tc_gather_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                    C.c_int32, C.c_void_p]
+    L.tc_env_reserve_poses.argtypes = [C.c_void_p, C.c_int64]
+    L.tc_render_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                  C.c_void_p, C.c_void_p]
     if L.tc_abi_version() != ABI_VERSION:
         raise NativeError(f"ABI mismatch: library {L.tc_abi_version()} vs binding {ABI_VERSION}")
     _lib = L

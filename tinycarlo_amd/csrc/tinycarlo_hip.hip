@@ -18,6 +18,7 @@
 //   k_frame.h    FrameArgs, tc_frame_kernel<..> (+ recover): camera + raster of one (step, env) frame per workgroup, from the
 //                pose the simulate launch left; tc_step_kernel<..> / tc_drive_step_kernel: simulate + camera + raster of an env
 //   k_misc.h     tc_order_kernel, tc_gate_kernel, tc_unpack_bits_kernel
+//   k_poses.h    PoseArgs, tc_pose_rows: stored poses -> pose rows, for frames drawn later (tc_render_poses)
 // This file holds no device code.  It holds what needs every kernel at once -- the instantiation lists of the parts (TC_INST_*,
 // TC_PART) and the tables from run-time choices to a kernel (the *_kernel_of functions) -- and then the host side (from
 // `// Host side: C ABI` down).
@@ -63,6 +64,7 @@
 #include "k_envg.h"
 #include "k_frame.h"
 #include "k_misc.h"
+#include "k_poses.h"
 
 // ---------------------------------------------------------------------------------------------
 // The instantiations of parts 1-5 (see TC_PART), D = `template` where they are compiled, `extern template` in part 0.
@@ -248,6 +250,7 @@ TC_INST_UNPACK(extern template)
 #include <utility>
 
 #include "tc_plan.h"
+#include "tc_poses.h"
 
 static thread_local std::string g_err;
 static void set_err(const std::string& s) { g_err = s; }
@@ -477,6 +480,14 @@ struct tc_env {
   Event start_ev;
   // scratch ring of chunked K-step calls (tc_env_reserve_steps): TC_RING_SLOTS chunks of ring.rows steps
   ScratchRows ring;
+  // Deferred frames (tc_render_poses; tc_env_reserve_poses): a scratch of its own for poses_cap frames per launch group --
+  // pose rows, draw-list lengths, overflow room -- so that a render between two K-step calls leaves theirs alone.  Handles
+  // without a frame kernel draw rounds of N frames instead: draw lists of N frames and the gathered poses as plain arrays.
+  ScratchRows poses;       // (rows: unused)
+  long long poses_cap = 0;  // frames per launch group; 0 = not reserved
+  DevPtr<double> poses_xyt;  // [3][N] gathered x, y, theta of a round (handles without a frame kernel), else NULL
+  DevPtr<int> poses_cam;     // [N] gathered camera rows of a round
+  DevPtr<CamDrawTab> poses_cam_tab;  // count = N: the clamp of the gathered rows of per-env cameras
   int step_lds = 0;  // tc_step_kernel: LDS bytes per workgroup (lds.total grown like frame_lds)
   // heaviest-first order of the frame workgroups of a K-step call (tune.frame_order = 0: env order), one buffer per frame stream
   DevPtr<int> frame_order[2];               // [N] each
@@ -2458,6 +2469,181 @@ extern "C" int tc_render_segments(tc_env* e, const int32_t* segments, const int3
 
 extern "C" int tc_render(tc_env* e, uint32_t flags, void* stream) {
   return launch(e, MODE_RENDER, nullptr, TC_F32, nullptr, nullptr, nullptr, flags & ~TC_F_NO_OBSERVATION, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Deferred frames: observations drawn from stored poses (k_poses.h, tc_poses.h; DESIGN.md "Deferred frames").
+
+// a handle whose K-step calls draw with a frame kernel (plan_call's can_frames); the others draw deferred frames the way
+// tc_render draws theirs: the camera stage inside tc_env_kernel, tc_raster_kernel behind it
+static bool has_frame_kernel(const tc_env* e) { return e->tune.fuse && e->kvar != 13; }
+
+extern "C" int tc_env_reserve_poses(tc_env* e, int64_t max_frames) {
+  if (!e || max_frames < 1) {
+    set_err("tc_env_reserve_poses: need an env and max_frames >= 1");
+    return TC_E_INVALID;
+  }
+  const bool frames = has_frame_kernel(e);
+  const size_t N = (size_t)e->k.N;
+  // per frame: a pose row (128 B), a draw-list length and room for a draw list (20 B x lane-line edges of the map), within
+  // the budget of the streamed calls' scratch (tune.scratch_bytes); handles without a frame kernel: rounds of N frames
+  const double per_frame = (double)e->k.seg_cap * 5 * sizeof(int) + sizeof(int) + TC_POSE_ROW * sizeof(double);
+  long long cap = max_frames < TC_POSES_MAX_CAPACITY ? (long long)max_frames : TC_POSES_MAX_CAPACITY;
+  if ((double)cap * per_frame > e->tune.scratch_bytes) cap = (long long)(e->tune.scratch_bytes / per_frame);
+  if (cap < 1) cap = 1;
+  if (!frames) cap = (long long)N;
+  if (e->poses_cap >= cap) return TC_OK;
+  HIP_TRY(hipDeviceSynchronize());  // an earlier render may still use the old arrays
+  e->poses = ScratchRows();
+  e->poses_cap = 0;
+  ScratchRows s;
+  DevPtr<double> xyt;
+  DevPtr<int> cam;
+  DevPtr<CamDrawTab> tab;
+  hipError_t he = s.seg_g.alloc((size_t)cap * e->k.seg_cap * 5);
+  if (he == hipSuccess) he = s.seg_n.alloc((size_t)cap);
+  if (he == hipSuccess) he = hipMemset(s.seg_n, 0, (size_t)cap * sizeof(int));
+  if (he == hipSuccess && frames) he = s.pose.alloc((size_t)cap * TC_POSE_ROW);
+  if (he == hipSuccess && !frames) he = xyt.alloc(3 * N);
+  if (he == hipSuccess && !frames) he = cam.alloc(N);
+  if (he == hipSuccess && !frames) he = tab.alloc(1);
+  if (he == hipSuccess && !frames) {
+    const CamDrawTab t = {0ull, (unsigned int)N, 0u};
+    he = hipMemcpy(tab, &t, sizeof(t), hipMemcpyHostToDevice);
+  }
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    set_err(std::string("hipMalloc(scratch of deferred frames): ") + hipGetErrorString(he));
+    return TC_E_NOMEM;
+  }
+  e->poses = std::move(s);
+  if (!frames) {
+    e->poses_xyt = std::move(xyt);
+    e->poses_cam = std::move(cam);
+    e->poses_cam_tab = std::move(tab);
+  }
+  e->poses_cap = cap;
+  return TC_OK;
+}
+
+// one launch group on a handle with a frame kernel: the pose rows, then one frame workgroup per row
+static int launch_pose_frames(tc_env* e, PoseArgs& pa, const PoseGroup& g, int cam_rows, uint8_t* out, hipStream_t st) {
+  pa.first = g.first;
+  pa.n = g.count;
+  pa.rows = e->poses.pose;
+  hipLaunchKernelGGL(tc_pose_rows, dim3((unsigned)g.pose_blocks), dim3(TC_POSES_NT), 0, st, pa);
+  HIP_TRY(hipGetLastError());
+  const DevCam& c = e->k.cam;
+  RArgs r = make_rargs(e, e->poses.seg_g, e->poses.seg_n, e->k.seg_cap, nullptr, 0, 0, out + (size_t)g.first * (size_t)e->obs_bytes, false);
+  r.N = g.count;
+  FrameArgs fa = frame_args_of(e, 0, r, false);
+  // one grid row as wide as the group: slot m of the scratch is workgroup m, and no workgroup stands for a frame beyond the list
+  fa.a.N = g.count;
+  fa.a.seg_g = e->poses.seg_g;
+  fa.a.seg_n = e->poses.seg_n;
+  fa.pose_rows = e->poses.pose;
+  fa.gate = 0;
+  fa.order = nullptr;
+  fa.bank = cam_rows;  // (per-env cameras too: the row comes from entry 12, not from the slot)
+  hipLaunchKernelGGL(frame_kernel_of(e->kframe, c.thickness > 1, c.format, false, frame_looped(e)), dim3((unsigned)g.count), dim3(TC_NT),
+                     e->frame_lds, st, fa);
+  HIP_TRY(hipGetLastError());
+  return TC_OK;
+}
+
+// one round on a handle without a frame kernel, the form tc_render has there: the poses gathered into plain arrays, a copy of
+// the launch arguments whose x / y / theta (and camera index) are those arrays, tc_env_kernel<K, CAM> in MODE_RENDER over the
+// round's slots and tc_raster_kernel behind it, both into the scratch's draw lists
+static int launch_pose_round(tc_env* e, PoseArgs& pa, const PoseGroup& g, int cam_rows, uint8_t* out, hipStream_t st) {
+  const size_t N = (size_t)e->k.N;
+  pa.first = g.first;
+  pa.n = g.count;
+  pa.rows = nullptr;
+  pa.gx = e->poses_xyt;
+  pa.gy = e->poses_xyt + N;
+  pa.gth = e->poses_xyt + 2 * N;
+  pa.gcam = e->poses_cam;
+  hipLaunchKernelGGL(tc_pose_rows, dim3((unsigned)g.pose_blocks), dim3(TC_POSES_NT), 0, st, pa);
+  HIP_TRY(hipGetLastError());
+  uint8_t* obs = out + (size_t)g.first * (size_t)e->obs_bytes;
+  StepArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.a = e->k;
+  sa.a.env0 = 0;
+  sa.a.b.x = pa.gx;
+  sa.a.b.y = pa.gy;
+  sa.a.b.theta = pa.gth;
+  sa.a.b.obs = obs;
+  sa.a.seg_g = e->poses.seg_g;
+  sa.a.seg_n = e->poses.seg_n;
+  sa.mode = MODE_RENDER;
+  sa.cdtype = TC_F32;
+  if (cam_rows > 0) {  // the slot's camera row is the gathered one: a bank's index, or the env of per-env cameras
+    sa.flags = TC_FI_CAM_BANK;
+    sa.cb.index = pa.gcam;
+    sa.cb.tab = e->cb.index ? (const CamDrawTab*)e->cam_tab : (const CamDrawTab*)e->poses_cam_tab;
+  }
+  sa.ma.nsteps = 1;
+  sa.ma.cam_here = 1;
+  hipLaunchKernelGGL(env_kernel_of(e->kvar, true, 0u), dim3((unsigned)g.count), dim3(TC_NT), e->k.lds.total, st, sa);
+  HIP_TRY(hipGetLastError());
+  return launch_raster(e, e->poses.seg_g, e->poses.seg_n, e->k.seg_cap, nullptr, 0, st, 0, g.count, obs, false);
+}
+
+extern "C" int tc_render_poses(tc_env* e, const double* x, const double* y, const double* theta, const int32_t* camera,
+                               const int64_t* index, int64_t n_src, int64_t n_frames, uint8_t* out, void* stream) {
+  // (every check comes before the first HIP call, and those of the arguments alone before the handle is looked at: a bad
+  // argument is reported on a machine without a device too)
+  auto bad = [](const char* what) {
+    set_err(std::string("tc_render_poses: ") + what);
+    return TC_E_INVALID;
+  };
+  auto mis = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+  if (!x || !y || !theta || !out) return bad("x, y, theta and out are required");
+  if (n_src < 1) return bad("n_src must be at least 1");
+  if (n_frames < 0) return bad("n_frames must not be negative");
+  if (!index && n_frames > n_src) return bad("without an index n_frames must not exceed n_src");
+  if (mis(out, 16)) return bad("out must be 16-byte aligned, like the obs rows of a rollout");
+  if (mis(x, 8) || mis(y, 8) || mis(theta, 8) || mis(index, 8) || mis(camera, 4)) return bad("x, y, theta and index must be 8-byte, camera 4-byte aligned");
+  if (!e) return bad("no env");
+  const int cam_rows = e->cb.index ? e->cam_count : (e->k.cam_E ? e->k.N : 0);
+  if (cam_rows == 0 && camera) return bad("camera given on a handle with the one shared camera");
+  if (cam_rows > 0 && !camera)
+    return bad(e->cb.index ? "a handle with a camera bank needs camera (the bank index of every pose)"
+                           : "a handle with per-env cameras needs camera (the env whose camera every pose takes)");
+  if (n_frames == 0) return TC_OK;
+  if (e->poses_cap < 1)
+    return bad("needs its scratch: call tc_env_reserve_poses(env, max_frames) once before (the call itself never allocates)");
+  const bool frames = has_frame_kernel(e);
+  if (!frames && !e->bound) {
+    set_err("tc_render_poses: a handle without a frame kernel draws with the simulate kernel's camera stage, which reads the bound buffers: tc_env_bind first");
+    return TC_E_UNBOUND;
+  }
+  int rc = check_stamp_buffer(e);
+  if (rc != TC_OK) return rc;
+#ifdef TC_TIMING
+  // (a frame workgroup stamps the row of its slot, and a group has up to poses_cap slots)
+  if (g_tstamp && frames && e->poses_cap > g_tstamp_n) return bad("timing build: the installed stamp buffer is smaller than a launch group");
+#endif
+  const hipStream_t st = (hipStream_t)stream;
+  // (the groups of a render reuse the scratch in stream order; renders on different streams are the caller's to order)
+  PoseArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.a = e->k;
+  pa.x = x;
+  pa.y = y;
+  pa.theta = theta;
+  pa.camera = camera;
+  pa.index = (const long long*)index;
+  pa.n_src = n_src;
+  pa.cam_rows = cam_rows;
+  const long long groups = pose_group_count(n_frames, e->poses_cap);
+  for (long long gi = 0; gi < groups; gi++) {
+    const PoseGroup g = pose_group_at(n_frames, e->poses_cap, gi, TC_POSES_NT);
+    rc = frames ? launch_pose_frames(e, pa, g, cam_rows, out, st) : launch_pose_round(e, pa, g, cam_rows, out, st);
+    if (rc != TC_OK) return rc;
+  }
+  return TC_OK;
 }
 
 extern "C" int tc_unpack_bits(const uint8_t* packed, int64_t n_src_frames, int32_t planes, int32_t H, int32_t W,

@@ -264,6 +264,7 @@ class TinyCarloVecEnv(gym.Env):
         self._shape_cache: Dict[int, Any] = {}
         self._step_serial = 0      # bumped by every reset / step launch: stale-info detection (LazyInfo)
         self._reserved_steps = 0   # tc_env_reserve_steps: scratch ring of K-step calls that render
+        self._reserved_poses = 0   # tc_env_reserve_poses: scratch of deferred frames (render_poses)
 
     def _setup_device(self) -> None:
         """Creates the native handles and the device tensors the HIP library works on (no CPU path)."""
@@ -1329,6 +1330,99 @@ class TinyCarloVecEnv(gym.Env):
                                                    self._stream()), "tc_render_segments")
         self._keep = (seg, cnt)
         return self.out["obs"]
+
+    # ------------------------------------------------------------------ deferred frames
+    def reserve_poses(self, max_frames: int) -> None:
+        """Sizes the library's scratch of deferred frames (tc_env_reserve_poses) for launches of up to `max_frames` frames; a
+        longer list runs as several launches.  `render_poses` calls this with min(M, 8192) on first use when nothing is reserved
+        yet; call it yourself before capturing a `render_poses` into a HIP graph -- the call itself never allocates."""
+        if int(max_frames) < 1:
+            raise ValueError("max_frames must be at least 1")
+        if int(max_frames) > self._reserved_poses:
+            with torch.cuda.device(self.device):
+                nat.check(nat.lib().tc_env_reserve_poses(self._h, int(max_frames)), "tc_env_reserve_poses")
+            self._reserved_poses = int(max_frames)
+
+    def render_poses(self, x: torch.Tensor, y: torch.Tensor, theta: torch.Tensor, camera: Optional[torch.Tensor] = None,
+                     index: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Observations drawn from stored poses on the device (tc_render_poses) -> uint8 [M, *obs_shape]: frame m is what
+        the camera sees from a car at element ``index[m]`` (or m) of the flattened ``x, y, theta`` -- float64 device tensors
+        of equal numel and any shape, for instance the x / y / theta rows of a rollout -- bit for bit the frame the call that
+        produced the poses drew or would have drawn.  The env's state, `self.out` and every later call are untouched.
+
+        camera: int32, same numel; not allowed with the one shared camera, required with per-env cameras (`set_env_cameras`:
+        the env whose camera the frame takes) and with a bank (`randomize_cameras`: the bank index, rollout["camera"]).
+        index: int64 over the flattened tensors (the convention of ``unpack_obs(..., index=)``), repeats and any order
+        allowed; a value outside [0, numel) is clamped.  out: reused when given.  With ``obs_packing="bits"`` the frames are
+        packed [M, C, H, W/8] and feed `unpack_obs`.  The frames are noise-free: the fused noise of `set_noise` is not
+        applied (a deferred frame has no place in the blob stream)."""
+        ts = {"x": x, "y": y, "theta": theta}
+        for k, t in ts.items():
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != self.device:
+                raise ValueError(f"{k} must be a float64 tensor on {self.device}")
+        n_src = int(x.numel())
+        if n_src < 1 or int(y.numel()) != n_src or int(theta.numel()) != n_src:
+            raise ValueError(f"x, y and theta must have the same, non-zero number of elements, got {int(x.numel())}, {int(y.numel())}, {int(theta.numel())}")
+        rows = self._cam_bank is not None or self._env_cams is not None
+        if camera is not None and not rows:
+            raise ValueError("camera= needs per-env cameras (set_env_cameras) or a bank (randomize_cameras): this env has the one shared camera")
+        if camera is None and rows:
+            raise ValueError("camera= is required: " + ("the bank index of every pose (rollout['camera'])" if self._cam_bank is not None
+                                                         else "the env whose camera every pose takes"))
+        if camera is not None and (not isinstance(camera, torch.Tensor) or camera.dtype != torch.int32 or camera.device != self.device
+                                   or int(camera.numel()) != n_src):
+            raise ValueError(f"camera must be an int32 tensor of {n_src} elements on {self.device}")
+        if index is not None and (not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.device != self.device):
+            raise ValueError(f"index must be an int64 tensor on {self.device}")
+        M = int(index.numel()) if index is not None else n_src
+        shape = (M,) + tuple(self._obs_shape)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device or tuple(out.shape) != shape \
+                or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape} on {self.device}")
+        if M == 0:
+            return out
+        if self._reserved_poses == 0:  # (a scratch somebody reserved is kept: a longer list runs as several launches)
+            self.reserve_poses(min(M, 8192))
+        x, y, theta = (t.contiguous() for t in (x, y, theta))
+        cam = camera.contiguous() if camera is not None else None
+        idx = index.contiguous() if index is not None else None
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().tc_render_poses(self._h, x.data_ptr(), y.data_ptr(), theta.data_ptr(),
+                                                cam.data_ptr() if cam is not None else None,
+                                                idx.data_ptr() if idx is not None else None, n_src, M, out.data_ptr(),
+                                                self._stream()), "tc_render_poses")
+        return out
+
+    def render_rollout(self, rollout: Dict[str, torch.Tensor], index: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The frames of a K-step call from its ``x, y, theta`` rows (`render_poses`): row k of a rollout is the state step k
+        returned, so ``render_rollout(roll)`` equals ``roll["obs"]`` of the same call when no noise is fused -- the frames
+        are noise-free.  With a bank the rollout's ``camera`` rows are required; with per-env cameras row (k, n) is drawn with
+        env n's camera.  index=None draws all K x N rows -> [K, N, *obs_shape]; else int64 indices over the flattened
+        [K * N] rows -> [M, *obs_shape] (a `drive()` without "obs" plus ``render_rollout(roll, index=kept_rows)`` draws only
+        what a learner keeps)."""
+        need = ("x", "y", "theta") + (("camera",) if self._cam_bank is not None else ())
+        missing = [k for k in need if k not in rollout]
+        if missing:
+            raise ValueError(f"render_rollout needs the rollout rows {missing} (alloc_rollout(K, keys=(..., {', '.join(repr(k) for k in need)})))")
+        x = rollout["x"]
+        if x.dim() != 2 or int(x.shape[1]) != self.num_envs:
+            raise ValueError(f"rollout['x'] must be [K, {self.num_envs}], got {tuple(x.shape)}")
+        K = int(x.shape[0])
+        camera = None
+        if self._cam_bank is not None:
+            camera = rollout["camera"]
+        elif self._env_cams is not None:
+            camera = torch.arange(self.num_envs, dtype=torch.int32, device=self.device).repeat(K)
+        if index is not None:
+            return self.render_poses(x, rollout["y"], rollout["theta"], camera=camera, index=index, out=out)
+        full = (K, self.num_envs) + tuple(self._obs_shape)
+        if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != full or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {full} on {self.device}")
+        flat = None if out is None else out.view((K * self.num_envs,) + tuple(self._obs_shape))
+        return self.render_poses(x, rollout["y"], rollout["theta"], camera=camera, out=flat).view(full)
 
     def render(self):
         """rgb_array of the class-agnostic camera view is only available in 'rgb' observation format."""
