@@ -1,6 +1,6 @@
 // k_common.h -- what every kernel stage shares: the TC_PART split of the build (TC_PLAIN_KERNEL), the launch modes, the LDS
 // layout and the env's LiveLds record, the kernel-argument blocks KArgs / MultiArgs / RollStep, and the wavefront helpers
-// (lds_sync, kernarg_again, d_readlane, uni_i / uni_d, wave_rank, wave_incl_scan, spread4).  Defines no kernel; the state
+// (lds_sync, kernarg_again, d_readlane, uni_i / uni_d, wave_rank, wave_incl_scan, wave_incl_max, spread4).  Defines no kernel; the state
 // it lays out is car.py's and env.py's per-env state.
 #ifndef K_COMMON_H
 #define K_COMMON_H
@@ -205,6 +205,21 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
   v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1 and 3
   v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2 and 3
   return v;
+}
+
+// Inclusive prefix MAXIMUM of non-negative values, the same DPP moves.  The maximum is taken unsigned: 0 -- what is shifted in,
+// and what a row outside the row mask receives -- is then the identity, as it is of +, and every step is one v_max_u32_dpp.
+// tc_deal.h's scan.
+__device__ __forceinline__ int wave_incl_max(int x) {
+  unsigned int v = (unsigned int)x;
+  auto mx = [](unsigned int a, unsigned int b) { return a > b ? a : b; };
+  v = mx(v, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true));   // row_shr:1
+  v = mx(v, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true));   // row_shr:2
+  v = mx(v, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true));   // row_shr:4
+  v = mx(v, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true));   // row_shr:8
+  v = mx(v, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));  // row_bcast:15 -> rows 1 and 3
+  v = mx(v, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));  // row_bcast:31 -> rows 2 and 3
+  return (int)v;
 }
 
 // Step k of a launch reads row k of the action arrays and writes row k of the rollout arrays ([nsteps][N] each).

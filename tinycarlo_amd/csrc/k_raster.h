@@ -4,11 +4,13 @@
 // (TC_FMT_CLASSES_BITS).  Holds the stage's argument block (RCam, RArgs), its tunables (TC_RASTER_WAVES, TC_BAND_VMCNT),
 // tc_obs_bytes_of, TC_FMT_IS_CLASSES, the packed-word stores, raster_body<THICK, FMT, LDSONLY, RB> and the kernel of the
 // stage alone, tc_raster_kernel<THICK, FMT>; tc_frame_kernel and tc_step_kernel (k_frame.h) run raster_body behind the
-// camera stage.  Includes k_common.h, tc_device.h and tc_rng.h (the noise blobs fused into the stage).
+// camera stage.  Includes k_common.h, tc_deal.h (how the FORM kernels deal pixel items to lanes), tc_device.h and tc_rng.h
+// (the noise blobs fused into the stage).
 #ifndef K_RASTER_H
 #define K_RASTER_H
 
 #include "k_common.h"
+#include "tc_deal.h"
 #include "tc_device.h"
 #include "tc_rng.h"
 
@@ -106,7 +108,8 @@ __device__ __forceinline__ void packed_copy_words(unsigned char* dst, const unsi
 }
 // FORM (the five-wave frame kernel, whose LDS plan is sized for it: plan_frame_lds): the outline tables hold the RB << sh items
 // of the handle's outline form -- sh = 2, the four edges of FillConvexPoly's quad, or 1, the two long ones (R_F_LONG_EDGES) --
-// and the bit-planes follow at RArgs::off_bits.  Otherwise the tables have their full size at compile-time offsets.
+// and the bit-planes follow at RArgs::off_bits; the pixel loops deal their items by scan (tc_deal.h) and the layers ride in
+// lt[..][3] and fm.  Otherwise the tables have their full size at compile-time offsets and the loops search the prefix tables.
 // ONE_BAND: the frame is known to be a single band (RCam::n_bands == 1, the caller's promise) -- the stage is then straight-line
 // code: no band loop, whose invariants the compiler would otherwise set up -- and spill -- in front of a loop that runs once.
 template <bool THICK, int FMT, bool LDSONLY = false, int RB = RB_MAX, bool FORM = false, bool ONE_BAND = false>
@@ -174,7 +177,7 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
   int* lc0 = lt0 + RB * 4 * 5;            // [RB*4] chunks per outline edge, then exclusive prefix
   int* fl = FORM ? (int*)(smem + R_OFF_TAB) : lc0 + RB * 4;  // [RB] first fill row of the segment in this band
   int* fc = fl + RB;                      // [RB] fill rows, then exclusive prefix
-  int* fm = fc + RB;                      // [RB] pieces | walker mask << 8 | quad valid << 16
+  int* fm = fc + RB;                      // [RB] pieces | walker mask << 8 | quad valid << 16 (FORM: | layer << 17)
   int* fd = fm + RB;                      // [RB][2] ThickLine's (dp.x, dp.y)
   int* fpy = fd + 2 * RB;                 // [RB][4] fill pieces: start row
   int* fpv = fpy + 4 * RB;                // [RB][4] fill pieces: polygon vertices idx0 | idx << 2
@@ -315,12 +318,13 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
         if (cam.thickness > 0) TSTAMP(24);  // (depends on a kernel argument re-read above: the scalar loads have returned)
 #endif
         if (tid < RB) {  // per segment: ThickLine's dp, fill walker pieces, fill rows of this band
-          int nrow = 0, lo = 0, np = 0, wm = 0, dpx = 0, dpy = 0, okq = 0;
+          int nrow = 0, lo = 0, np = 0, wm = 0, dpx = 0, dpy = 0, okq = 0, layer = 0;
 #ifdef TC_TIMING_LDS
           TSTAMP(25);
 #endif
           if (tid < nb) {
             const SegV sg = seg_get(base + tid);
+            layer = sg[0];
             long long qx0, qx1, qx2, qx3, qy0, qy1, qy2, qy3;
             TSTAMP(20);
             // Frames taller than one LDS band are rasterised band by band, and every band runs this set-up again.  A
@@ -350,7 +354,8 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
           }
           fl[tid] = lo;
           fc[tid] = nrow;
-          fm[tid] = np | (wm << 8) | (okq << 16);
+          // (FORM: the segment's layer rides in bits 17..21, so a fill row does not read the draw list for it)
+          fm[tid] = np | (wm << 8) | (okq << 16) | (FORM ? layer << 17 : 0);
           fd[2 * tid] = dpx;
           fd[2 * tid + 1] = dpy;
         }
@@ -402,8 +407,12 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
               o[0] = L.a;
               o[1] = L.b;
               o[2] = L.step;
-              o[3] = L.ecount | (L.xmajor << 30);
-              o[4] = sg[0];
+              if constexpr (FORM) {  // the layer in bits 16..20 (ecount has 16 bits); the stride stays 5 words
+                o[3] = L.ecount | (sg[0] << 16) | (L.xmajor << 30);
+              } else {
+                o[3] = L.ecount | (L.xmajor << 30);
+                o[4] = sg[0];
+              }
               nchunk = (L.ecount + LCH) / LCH;
             }
           }
@@ -412,6 +421,7 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
         lds_sync();
         MARK("prefix sums");
         int tot_l, tot_f;
+        int dl_p0 = 0, dl_n0 = 0, dl_p1 = 0, dl_n1 = 0, dl_t0 = 0, df_p = 0, df_n = 0;  // FORM: (prefix, count) of this lane's entries
         {  // exclusive prefix sums (RB*4 = 2 entries per lane, or 1 when RB = 16; RB entries on the low lanes)
           static_assert(RB * 4 == 2 * TC_NT || RB * 4 == TC_NT, "outline-edge chunk counts: one or two per lane");
           constexpr bool TWO = RB * 4 == 2 * TC_NT;
@@ -424,40 +434,91 @@ __device__ __forceinline__ void raster_body(const RArgs& a0, unsigned char* smem
           int f = tid < RB ? fc[tid] : 0;
           int finc = wave_incl_scan(f, tid);
           tot_f = __builtin_amdgcn_readlane(finc, TC_NT - 1);
-          if (two) {
-            lc[2 * tid] = inc - v0 - v1;  // each lane rewrites only the entries it read
-            lc[2 * tid + 1] = inc - v1;
-          } else if (mine) {
-            lc[tid] = inc - v0;
+          if constexpr (FORM) {
+            // the pixel loops deal by scan (tc_deal.h): prefix and count stay in the registers the scan left them in, and
+            // neither table is read again -- lc keeps the chunk counts and becomes the dealing's scratch, fc keeps the rows
+            dl_t0 = two ? 2 * tid : tid;
+            dl_p0 = inc - v0 - v1, dl_n0 = v0, dl_p1 = inc - v1, dl_n1 = v1;
+            df_p = finc - f, df_n = f;
+          } else {
+            if (two) {
+              lc[2 * tid] = inc - v0 - v1;  // each lane rewrites only the entries it read
+              lc[2 * tid + 1] = inc - v1;
+            } else if (mine) {
+              lc[tid] = inc - v0;
+            }
+            if (tid < RB) fc[tid] = finc - f;
           }
-          if (tid < RB) fc[tid] = finc - f;
         }
         lds_sync();
         TSTAMP(11);
-        for (int c = tid; c < tot_l && !DBG_ON(a.flags, DBG_SKIP_R2); c += TC_NT) {  // outline pixels, LCH steps per chunk
-          int lo = 0, hi = n_items;
-          while (hi - lo > 1) {
-            int mid = (lo + hi) >> 1;
-            if (lc[mid] <= c) lo = mid; else hi = mid;
+        if constexpr (FORM) {
+          static_assert(!FORM || (RB == 32 && RB * 4 <= TC_DEAL_IDS && TC_NT == TC_DEAL_LANES), "lc holds >= 64 words and a marker names every entry");
+          // One pass: zero the 64 slots (the head of lc, dead: see above), the entries that start in the window drop their
+          // markers, every lane picks its slot up and the max-scan spreads each marker over the items behind it.
+          auto deal = [&](const int c0, const int carry, const int p0, const int n0, const int t0, const int p1, const int n1) {
+            lc[tid] = 0;
+            if (tc_deal_starts(p0, n0, c0)) lc[p0 - c0] = tc_deal_word(p0, t0);
+            if (tc_deal_starts(p1, n1, c0)) lc[p1 - c0] = tc_deal_word(p1, t0 + 1);
+            lds_sync();
+            const int w = wave_incl_max(lc[tid]);
+            return w > carry ? w : carry;
+          };
+          int carry = 0;
+          for (int c0 = 0; c0 < tot_l && !DBG_ON(a.flags, DBG_SKIP_R2); c0 += TC_NT) {  // outline pixels, LCH steps per chunk
+            const int w = deal(c0, carry, dl_p0, dl_n0, dl_t0, dl_p1, dl_n1);
+            carry = __builtin_amdgcn_readlane(w, TC_NT - 1);
+            const int c = c0 + tid;
+            if (c < tot_l) {
+              const int* o = lt + 5 * tc_deal_owner(w);
+              const int o3 = o[3];
+              const int ecount = o3 & 0xffff, xmajor = (o3 >> 30) & 1;
+              const int k0 = tc_deal_offset(w, c) * LCH;
+              const int k1 = k0 + LCH - 1 < ecount ? k0 + LCH - 1 : ecount;
+              r.bits = bits + ((o3 >> 16) & 31) * plane;  // (the layer rides in the word: see the set-up)
+              r_line2_pixels(r, o[0], o[1], o[2], xmajor, k0, k1);
+            }
           }
-          const int* o = lt + 5 * lo;
-          const int ecount = o[3] & 0xffff, xmajor = (o[3] >> 30) & 1;
-          const int k0 = (c - lc[lo]) * LCH;
-          const int k1 = k0 + LCH - 1 < ecount ? k0 + LCH - 1 : ecount;
-          r.bits = bits + o[4] * plane;
-          r_line2_pixels(r, o[0], o[1], o[2], xmajor, k0, k1);
-        }
-        MARK("fill rows");
-        for (int c = tid; c < tot_f && !DBG_ON(a.flags, DBG_SKIP_R3); c += TC_NT) {  // scanline fill, one row per item
-          int lo = 0, hi = RB;
-          while (hi - lo > 1) {
-            int mid = (lo + hi) >> 1;
-            if (fc[mid] <= c) lo = mid; else hi = mid;
+          MARK("fill rows");
+          carry = 0;
+          for (int c0 = 0; c0 < tot_f && !DBG_ON(a.flags, DBG_SKIP_R3); c0 += TC_NT) {  // scanline fill, one row per item
+            const int w = deal(c0, carry, df_p, df_n, tid, 0, 0);
+            carry = __builtin_amdgcn_readlane(w, TC_NT - 1);
+            const int c = c0 + tid;
+            if (c < tot_f) {
+              const int lo = tc_deal_owner(w);
+              const int row = fl[lo] + tc_deal_offset(w, c);
+              const int mm = fm[lo];
+              r.bits = bits + ((mm >> 17) & 31) * plane;  // (likewise)
+              r_fill_row(r, row, mm & 0xff, (mm >> 8) & 0xff, fpy + 4 * lo, fpx + 4 * lo, fpd + 4 * lo);
+            }
           }
-          const int row = fl[lo] + (c - fc[lo]);
-          const int mm = fm[lo];
-          r.bits = bits + seg_layer(base + lo) * plane;
-          r_fill_row(r, row, mm & 0xff, (mm >> 8) & 0xff, fpy + 4 * lo, fpx + 4 * lo, fpd + 4 * lo);
+        } else {  // every other kernel: the binary search through the prefix tables (tc_deal_search's form)
+          for (int c = tid; c < tot_l && !DBG_ON(a.flags, DBG_SKIP_R2); c += TC_NT) {  // outline pixels, LCH steps per chunk
+            int lo = 0, hi = n_items;
+            while (hi - lo > 1) {
+              int mid = (lo + hi) >> 1;
+              if (lc[mid] <= c) lo = mid; else hi = mid;
+            }
+            const int* o = lt + 5 * lo;
+            const int ecount = o[3] & 0xffff, xmajor = (o[3] >> 30) & 1;
+            const int k0 = (c - lc[lo]) * LCH;
+            const int k1 = k0 + LCH - 1 < ecount ? k0 + LCH - 1 : ecount;
+            r.bits = bits + o[4] * plane;
+            r_line2_pixels(r, o[0], o[1], o[2], xmajor, k0, k1);
+          }
+          MARK("fill rows");
+          for (int c = tid; c < tot_f && !DBG_ON(a.flags, DBG_SKIP_R3); c += TC_NT) {  // scanline fill, one row per item
+            int lo = 0, hi = RB;
+            while (hi - lo > 1) {
+              int mid = (lo + hi) >> 1;
+              if (fc[mid] <= c) lo = mid; else hi = mid;
+            }
+            const int row = fl[lo] + (c - fc[lo]);
+            const int mm = fm[lo];
+            r.bits = bits + seg_layer(base + lo) * plane;
+            r_fill_row(r, row, mm & 0xff, (mm >> 8) & 0xff, fpy + 4 * lo, fpx + 4 * lo, fpd + 4 * lo);
+          }
         }
         MARK("caps");
         for (int t = tid; t < nb * 2 && !DBG_ON(a.flags, DBG_SKIP_R4); t += TC_NT) {  // round caps (flags = 3: both ends)
